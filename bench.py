@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ganon read classification on MI355X: Mreads/s classified + IBF-lookup GB/s vs the HBM roofline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -17,8 +17,12 @@ resident in HBM; the filter is resident too.  Workloads (BASELINE.json `configs`
                         every pair, sparse matches go to the read's owner over RCCL (world 1 on one GPU)
 
 The 128 GiB filters are generated on the device (gn_filter_fill_random); nothing that large exists on the host.
-Output (rank 0): everything measured goes to `bench_detail.json` (next to this file, and under gpurun_out/ when that
-exists) and to ONE EARLIER stdout line `bench_detail: {...}`; the LAST stdout line is the driver's record -- one
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs DIR if asked (dump_outputs: what the last
+timed step computed, as float64 .npy files) and prints the record; `cpu_baseline` is then null and `roofline.frac` is
+measured on the product kernel.  Everything else below -- the early-exit-ablated roofline pass, `variants`, the oracle
+spot check, the match checksums, `cpu_baseline`, `other_workloads`, `e2e` and the detail file -- runs under --full.
+Output (rank 0): with --full everything measured goes to `bench_detail.json` (next to this file, and to the copy-back
+folder when there is one) and to ONE EARLIER stdout line `bench_detail: {...}`; the LAST stdout line is the driver's record -- one
 compact JSON object (a few KB, never more than 8 KB: tests/test_bench_line.py) holding exactly
   metric value unit n_gpus steps warmup ms_per_step higher_is_better scaling vs_baseline dtype data
   config        {workload, reads_per_gpu, parallelism, oracle_mismatching_reads, <= 20 flat scalars}
@@ -108,7 +112,7 @@ def log(*a):
 
 def run_extra(name: str, timeout: int):
     """another BASELINE config at full size in a child process (a crash or a timeout there cannot lose the main line)"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-extra", "--no-variants"]
     t0 = time.time()
     try:
@@ -266,9 +270,10 @@ def compact_line(result: dict) -> dict:
     return line
 
 
-def emit(result: dict, write_files: bool = True) -> None:
-    """detail file + an earlier stdout line, then the compact record as the LAST stdout line"""
+def emit(result: dict, write_files: bool = True, full: bool = True) -> None:
+    """detail file + an earlier stdout line (--full), then the compact record as the LAST stdout line"""
     detail = json.dumps(result)
+    write_files = write_files and full
     for d in (ROOT, os.path.join(ROOT, "gpurun_out")) if write_files else ():
         if os.path.isdir(d):
             try:
@@ -276,11 +281,61 @@ def emit(result: dict, write_files: bool = True) -> None:
                     f.write(detail + "\n")
             except OSError as e:
                 log("bench.py: could not write", os.path.join(d, "bench_detail.json"), repr(e))
-    sys.stdout.write("bench_detail: " + detail + "\n")
-    text = json.dumps(compact_line(result), separators=(",", ":"))
+    if full:
+        sys.stdout.write("bench_detail: " + detail + "\n")
+    record = compact_line(result)
+    if not full:
+        record["detail"] = None
+    text = json.dumps(record, separators=(",", ":"))
     assert len(text) < LINE_CAP, f"driver line is {len(text)} bytes"
     sys.stdout.write(text + "\n")
     sys.stdout.flush()
+
+
+DUMP_CAP_BYTES = 64_000_000    # --dump-outputs writes at most this much
+DUMP_SAMPLE_READS = 1 << 19   # reads sampled when a batch has more
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir: str, n_hashes, status, match_off, matches, cap_bytes: int = DUMP_CAP_BYTES,
+                 sample_reads: int = DUMP_SAMPLE_READS) -> dict:
+    """What a caller of the timed path receives (HipStream.fetch: minimisers and status per read, matches grouped by read, ascending
+    target) as float64 .npy files, so that two builds can be compared output for output:
+      totals            reads, classified reads, matches, minimisers, and the order-independent checksum of every match record
+                        (bench_workload.checksum_matches) as its low and high 32 bits -- the whole batch
+      read_index        the reads sampled (all of them when there are at most `sample_reads`; else a fixed seeded sample, halved
+                        until everything fits `cap_bytes`), ascending
+      n_hashes, status, matches_per_read                              per sampled read
+      match_read, match_target, match_count                           the sampled reads' match records, in the order fetched
+    -> {name: bytes written}"""
+    import bench_workload as bw
+    nh = np.asarray(n_hashes)
+    mo = np.asarray(match_off).astype(np.int64)
+    n = len(nh)
+    csum = bw.checksum_matches(matches)
+    counts = np.diff(mo)
+    totals = np.array([n, np.count_nonzero(counts), len(matches), int(nh.astype(np.int64).sum()), csum & 0xFFFFFFFF, csum >> 32],
+                      dtype=np.float64)
+    idx = np.arange(n, dtype=np.int64)
+    if n > sample_reads:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, sample_reads, replace=False))
+    while True:
+        per_read = counts[idx]
+        n_m = int(per_read.sum())
+        if 8 * (4 * len(idx) + 3 * n_m + len(totals)) + 8 * 128 <= cap_bytes or len(idx) <= 1:   # (+ the .npy headers)
+            break
+        idx = idx[::2]
+    first = np.repeat(mo[idx] - (np.cumsum(per_read) - per_read), per_read)
+    rec = matches[first + np.arange(n_m, dtype=np.int64)] if n_m else matches[:0]
+    arrays = {"totals": totals, "read_index": idx, "n_hashes": nh[idx], "status": np.asarray(status)[idx], "matches_per_read": per_read,
+              "match_read": rec["read"], "match_target": rec["target"], "match_count": rec["count"]}
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        written[name] = os.path.getsize(path)
+    return written
 
 
 def slim(name: str, r: dict, wall: float) -> dict:
@@ -380,9 +435,14 @@ def main() -> int:
     ap.add_argument("--no-e2e", action="store_true", help="do not run the product binary end to end after the kernels (bench_e2e.py)")
     ap.add_argument("--e2e-budget", type=int, default=200, help="seconds the end-to-end leg may take")
     ap.add_argument("--cpu-sample", type=int, default=0, help="reads in the CPU baseline sample (0 = auto, ~15 s)")
-    ap.add_argument("--check", type=int, default=2000, help="reads re-checked against the oracle (rank 0)")
+    ap.add_argument("--check", type=int, default=2000, help="reads re-checked against the oracle (rank 0, --full)")
     ap.add_argument("--emit-from", default="", help="dry run without a GPU: read a full result (a bench_detail.json) and print it the "
                                                      "way a real run does (tests/test_bench_line.py)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything besides the headline (the legs the --no-* "
+                                                        "options switch off, the oracle spot check, match checksums, bench_detail.json); "
+                                                        "a plain run sets up, warms up, times the steps and prints the record")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what their last step computed as "
+                                                                      "DIR/<name>.npy (float64, a seeded sample of the reads: dump_outputs)")
     args = ap.parse_args()
     if args.emit_from:
         with open(args.emit_from) as f:
@@ -546,6 +606,16 @@ def main() -> int:
                     "ms_per_step": round(float(np.mean(tms)), 3), "mreads_per_s": round(n_reads / float(np.mean(tms)) / 1e3, 2)}
 
         elapsed, count_ms, mini_ms, total_ms, tm = timed(args.rel_cutoff, steps, warmup)
+        outputs = None   # what the last timed step computed, as a caller receives it
+        if args.full or (headline and args.dump_outputs and rank == 0):
+            if part is None:
+                outputs = st.fetch()
+            else:
+                matches = part.fetch_owned()
+                outputs = st.fetch_read_info() + (np.searchsorted(matches["read"], np.arange(n_reads + 1)).astype(np.uint64), matches)
+        if headline and args.dump_outputs and rank == 0:
+            written = dump_outputs(args.dump_outputs, *outputs)
+            log(f"bench.py: wrote {len(written)} arrays, {sum(written.values())} bytes, to {args.dump_outputs}")
         per_rank_ms = [e * 1e3 / max(1, steps) for e in gdist.all_gather_float(elapsed, device=red_dev)]   # every rank's own clock
         elapsed = gdist.max_over_ranks(elapsed, device=red_dev)       # slowest rank defines the step time
         exchange = None
@@ -556,23 +626,23 @@ def main() -> int:
         # SURVEY 8(d)'s fraction belongs to the instantiation that fetches every algorithmic row: the same resident batch
         # with the early exit ablated (3 steps, outside `value`).  Split-bin and HIBF kernels have no early exit.
         full, full_tms = ee, total_ms
-        if kind in ("flat", "slice") and spec.get("bins_per_target", 1) == 1 and not args.no_every_row:
+        every_row = kind in ("flat", "slice") and spec.get("bins_per_target", 1) == 1
+        if every_row and args.full and not args.no_every_row:
             with ganon_amd.ablate("early_exit"):
                 _, cms0, _, full_tms, tm0 = timed(args.rel_cutoff, 3, 1)
             full = rates(tm0, cms0)
-            step(args.rel_cutoff)                                     # the product result is what the checks below fetch
+            step(args.rel_cutoff)                                     # the product result stays in the stream
         if kind == "slice":
             total_reads = n_reads                                      # every rank classifies the same reads against its columns
         else:
             total_reads = gdist.sum_over_ranks(n_reads, device=red_dev)    # whole-job reads per step
-        if part is None:
-            nh, status, mo, matches = st.fetch()
-        else:
+        if part is not None:
             lo, hi = owned["out"][:2]
-            nh, status = st.fetch_read_info()
-            matches = part.fetch_owned()
-            mo = np.searchsorted(matches["read"], np.arange(n_reads + 1)).astype(np.uint64)
-        n_class = int(np.count_nonzero(np.diff(mo.astype(np.int64))))
+        n_class = n_matches = None
+        if outputs is not None:
+            nh, status, mo, matches = outputs
+            n_class = int(np.count_nonzero(np.diff(mo.astype(np.int64))))
+            n_matches = int(len(matches))
         ms_per_step = elapsed * 1e3 / max(1, steps)
         value = total_reads / (elapsed / max(1, steps)) / 1e6  # Mreads/s (M pairs/s for paired workloads), whole job
 
@@ -589,7 +659,9 @@ def main() -> int:
                 "algo_bytes_per_launch": ee["algo_bytes"] // ee["launches"],
                 "fetched_bytes_per_launch": ee["fetched_bytes"] // ee["launches"],
                 "frac_measured_on": ("early exit ablated (every algorithmic row fetched), 3 steps on the same resident batch" if full is not ee
-                                     else ("the product kernel (--no-every-row)" if args.no_every_row else "the product kernel (it has no early exit)")),
+                                     else ("the product kernel (--no-every-row)" if args.no_every_row else
+                                           "the product kernel (the early-exit-ablated pass runs under --full)" if every_row else
+                                           "the product kernel (it has no early exit)")),
                 "note": "algo_over_peak may exceed 1: rows the exact early exit skips are never fetched"}
         if kind == "hibf":
             # The roofline per tree level: a level's rows are gathered from the IBFs at that depth, and whether those sit in
@@ -637,7 +709,7 @@ def main() -> int:
                                 else f"read-sharded x{world}, filter replicated"),
                 "mean_minimisers_per_read": round(tm["n_hashes"] / max(1, n_reads), 3),
                 "classified_reads_rank0": n_class,
-                "matches_rank0": int(len(matches)),
+                "matches_rank0": n_matches,
                 "kernel_ms": {"minimiser": round(float(np.mean(mini_ms)), 3), "count_select": round(float(np.mean(count_ms)), 3),
                               "device_total": round(float(np.mean(total_ms)), 3)},
             },
@@ -666,7 +738,7 @@ def main() -> int:
                 log("bench.py: could not read", pmc_path, repr(e))
 
         # the same resident batch under the two conditions the headline does not show (not part of `value`)
-        if headline and not args.no_variants and part is None and kind == "flat":
+        if headline and args.full and not args.no_variants and part is None and kind == "flat":
             variants = {}
             bpt = spec.get("bins_per_target", 1)
             if bpt == 1:  # (the split-bin kernel has no early exit); measured above for the roofline
@@ -696,7 +768,7 @@ def main() -> int:
             step(args.rel_cutoff)  # leave the headline batch in the stream for the checks below
 
         p001 = kind == "hibf" and spec.get("fill") == "3/16"
-        if kind == "hibf" and (p001 or (headline and not args.no_variants and os.environ.get("GANON_BENCH_HIBF_LOW_CUTOFF"))):
+        if kind == "hibf" and args.full and (p001 or (headline and not args.no_variants and os.environ.get("GANON_BENCH_HIBF_LOW_CUTOFF"))):
             # The binary's own --rel-cutoff 0.2, plain and under the filter rules `ganon classify` passes.  At the reference's HIBF defaults
             # (p^h = 0.0012) chance matches are rare and this always runs; on the h = 3 / p^h = 0.05..0.125 workloads it is an A/B on request
             # (needs --reads <= 500000: 3 000 chance matches per read there): --rel-cutoff 0.2 plain, with the filter_matches pre-pass judging
@@ -719,6 +791,18 @@ def main() -> int:
             st.set_postfilter(None)
             result["variants"] = variants
             step(args.rel_cutoff)
+
+        def release():
+            if part is not None:
+                part.close()
+            else:
+                st.destroy()
+            flt.free()
+
+        if not args.full:   # a plain run ends at the headline
+            result["cpu_baseline"] = None
+            release()
+            return result
 
         # Every rank re-derives a sample of ITS OWN shard / owned range with the oracle (a wrong shard on rank 5 must not pass
         # because rank 0's was right); the mismatch counts are summed over the ranks into the line, and so are the per-rank
@@ -765,19 +849,15 @@ def main() -> int:
                     result["cpu_baseline"] = None
             if headline:
                 result.setdefault("cpu_baseline", None)
-        if part is not None:
-            part.close()
-        else:
-            st.destroy()
-        flt.free()
+        release()
         return result
 
     result = run_one(args.workload, True)
-    default_run = not args.no_extra and args.workload == "flat8g" and not args.reads and not args.rows
+    default_run = args.full and not args.no_extra and args.workload == "flat8g" and not args.reads and not args.rows
     extras_multi = EXTRA_WORKLOADS_MULTI
     if os.environ.get("GANON_BENCH_EXTRAS"):   # dry runs: small stand-ins for the extras, e.g. "tiny,slice_tiny"
         extras_multi = [w for w in os.environ["GANON_BENCH_EXTRAS"].split(",") if w in WORKLOADS]
-        default_run = not args.no_extra
+        default_run = args.full and not args.no_extra
     if default_run and world == 1 and rank == 0:
         result["other_workloads"] = [run_extra(w, args.extra_timeout) for w in EXTRA_WORKLOADS]
         if not args.no_e2e:
@@ -794,7 +874,7 @@ def main() -> int:
             log(f"[rank {rank}] bench.py: the in-job extras did not finish within {args.extra_timeout} s -- leaving without them")
             if rank == 0:
                 result["other_workloads"] = others + [{"workload": "(in-job extras)", "error": f"timeout after {args.extra_timeout}s"}]
-                emit(result)
+                emit(result, full=args.full)
             os._exit(0)
 
         watchdog = threading.Timer(args.extra_timeout, give_up)
@@ -825,7 +905,7 @@ def main() -> int:
         out_of_step = any("error" in o for o in result.get("other_workloads", [])) if world > 1 else False
         if out_of_step:   # (an extra failed on some rank: a barrier could wait for ever)
             if rank == 0:
-                emit(result)
+                emit(result, full=args.full)
             sys.stdout.flush()
             os._exit(0)
         gdist.barrier()
@@ -842,7 +922,7 @@ def main() -> int:
             # (16 M reads as at N = 1: writing and compressing the input files is most of this leg's time, and the scaling run has a clock too)
             result["e2e"] = run_e2e(min(args.e2e_budget, 150), devices=dev_list, only="fastq,gz",
                                     reads=int(os.environ.get("GANON_BENCH_E2E_READS", "0")) or 16_000_000)
-        emit(result)
+        emit(result, full=args.full)
     return 0
 
 

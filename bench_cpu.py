@@ -276,9 +276,11 @@ def cpu_baseline(wl, flt, n_sample: int = 0, gpu_result=None):
             ref = reference_baseline(binary, wl, flt, nh, mo, matches, min(n, max(100_000, int(port["value"] * 1e6 * 10))), threads)
             return {"value": ref["value"], "unit": "Mreads/s", "cores": threads, "kind": "reference", "agrees_with_ours": ref["agrees_with_ours"],
                     "port_value": port["value"],
-                    "sample": f"{ref['binary']} --threads {threads} --output-all on the first {ref['reads']} reads of the same workload (FASTQ) and an .ibf of the "
-                              f"same bits written by this repo's writer: {ref['seconds']} s by {ref['timed_by']} (process wall {ref['process_wall_s']} s), "
-                              f"{ref['matches']} .all lines {'==' if ref['agrees_with_ours'] else '!='} the GPU's matches; the CPU port: {port['value']} Mreads/s"}
+                    # (the verdict first: the record cuts this text at 300 characters, and the binary's path has any length)
+                    "sample": f"{ref['matches']} .all lines {'==' if ref['agrees_with_ours'] else '!='} the GPU's matches, --threads {threads} "
+                              f"--output-all on the first {ref['reads']} reads of the same workload (FASTQ) and an .ibf of the same bits written by "
+                              f"this repo's writer: {ref['seconds']} s by {ref['timed_by']} (process wall {ref['process_wall_s']} s); "
+                              f"the CPU port: {port['value']} Mreads/s; binary {ref['binary']}"}
         except Exception as e:  # noqa: BLE001 -- the port's figure is still a baseline
             port["sample"] += f"; reference binary {binary} failed: {e!r}"[:300]
     else:

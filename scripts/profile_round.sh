@@ -14,7 +14,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py --workload $WL --steps 5 --warmup 1 --no-cpu-baseline --no-extra --no-variants --no-every-row --check 0"
 cd /tmp
-python $ROOT/bench.py --workload $WL --steps 10 --warmup 2 --no-extra > $OUT/bench.json 2> $OUT/bench.log
+python $ROOT/bench.py --workload $WL --steps 10 --warmup 2 --full --no-extra > $OUT/bench.json 2> $OUT/bench.log
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
 timeout 420 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH > $OUT/pmc_fetch.log 2>&1
 if [ "$WL" = flat8g ] || [ "$WL" = flat128g ]; then

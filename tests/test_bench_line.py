@@ -85,6 +85,56 @@ def test_compact_line_of_an_eight_rank_run_carries_the_proof_and_the_scalars_of_
     assert line["roofline"]["traffic_from"].startswith("profiles/") and " " not in line["roofline"]["traffic_from"]
 
 
+def _fake_outputs(n_reads: int, seed: int = 5):
+    """n_hashes, status, match offsets and MATCH_DTYPE records shaped like HipStream.fetch()'s"""
+    import numpy as np
+    from ganon_amd import MATCH_DTYPE
+    rng = np.random.default_rng(seed)
+    per = rng.integers(0, 4, size=n_reads)
+    mo = np.concatenate([[0], np.cumsum(per)]).astype(np.uint64)
+    m = np.zeros(int(per.sum()), dtype=MATCH_DTYPE)
+    m["read"] = np.repeat(np.arange(n_reads), per)
+    m["target"] = np.concatenate([np.sort(rng.choice(4096, k, replace=False)) for k in per]) if n_reads else []
+    m["count"] = rng.integers(1, 30, size=len(m))
+    return rng.integers(0, 40, size=n_reads).astype(np.uint32), (rng.random(n_reads) < 0.1).astype(np.uint8), mo, m
+
+
+def test_dump_outputs_holds_the_batch_totals_and_exactly_the_sampled_reads_records(tmp_path):
+    import numpy as np
+    import bench
+    import bench_workload as bw
+    nh, status, mo, m = _fake_outputs(3000)
+    written = bench.dump_outputs(str(tmp_path / "all"), nh, status, mo, m)
+    d = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in written}
+    assert all(a.dtype == np.float64 for a in d.values())
+    csum = bw.checksum_matches(m)
+    assert d["totals"].tolist() == [3000, np.count_nonzero(np.diff(mo.astype(np.int64))), len(m), int(nh.sum()), csum & 0xFFFFFFFF, csum >> 32]
+    assert np.array_equal(d["read_index"], np.arange(3000)) and np.array_equal(d["n_hashes"], nh) and np.array_equal(d["status"], status)
+    for f in ("read", "target", "count"):
+        assert np.array_equal(d["match_" + f], m[f])
+    # more reads than the sample: a fixed seeded sample, the same every time, and every record of those reads and no other
+    a = bench.dump_outputs(str(tmp_path / "s1"), nh, status, mo, m, sample_reads=500)
+    bench.dump_outputs(str(tmp_path / "s2"), nh, status, mo, m, sample_reads=500)
+    for k in a:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")), k
+    idx = np.load(tmp_path / "s1" / "read_index.npy").astype(np.int64)
+    assert len(idx) == 500 and np.all(np.diff(idx) > 0) and idx[-1] < 3000
+    want = np.concatenate([m[int(mo[r]):int(mo[r + 1])] for r in idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "match_read.npy"), want["read"])
+    assert np.array_equal(np.load(tmp_path / "s1" / "match_target.npy"), want["target"])
+    assert np.array_equal(np.load(tmp_path / "s1" / "matches_per_read.npy"), np.diff(mo.astype(np.int64))[idx])
+    # the size cap halves the sample until everything fits
+    c = bench.dump_outputs(str(tmp_path / "cap"), nh, status, mo, m, cap_bytes=40_000)
+    assert sum(c.values()) <= 40_000 and 0 < len(np.load(tmp_path / "cap" / "read_index.npy")) < 3000
+
+
+def test_full_and_dump_outputs_are_options_and_plain_is_the_default():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
+    import bench
+    assert bench.DUMP_CAP_BYTES <= 64_000_000
+
+
 def _run_bench(argv, env_extra=None, timeout=300):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GANON_BENCH_ALLOW_SHARED_GPU")}
     env.update(env_extra or {})
@@ -124,7 +174,8 @@ def test_bench_prints_detail_first_and_the_compact_record_last():
 @pytest.mark.gpu
 def test_real_run_ends_with_a_short_parsable_line():
     env = dict(os.environ, GANON_BENCH_EXTRAS="hibf_tiny")   # (one child process stands for the five of a default run)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-e2e", "--cpu-sample", "20000"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-e2e",
+                        "--cpu-sample", "20000"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
@@ -146,7 +197,8 @@ def test_reference_binary_leg_with_our_binary_standing_in():
     import bench_cpu
     assert bench_cpu.find_reference_classify()[0] is None or "mi355x" not in bench_cpu.find_reference_classify()[0]
     env = dict(os.environ, GANON_REFERENCE_CLASSIFY=os.path.join(ROOT, "ganon_amd", "host", "ganon-classify"))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-e2e", "--no-extra"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-e2e",
+                        "--no-extra"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.splitlines()[-1])
@@ -160,7 +212,7 @@ def test_gpus_2_starts_two_ranks_itself_and_proves_them():
     """`python bench.py --gpus 2`, no torchrun: on this one-GPU box only with the explicit dry-run override (two ranks share the
     GPU and talk gloo -- RCCL refuses duplicate devices); the record says n_gpus 2, ranks_seen 2 and that the GPU was shared.
     The in-job extras stand for flat128g / slice1t: the read-sharded and the bin-range partitioned path with the exchange step."""
-    args = ["--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-e2e"]
+    args = ["--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-e2e"]
     p = _run_bench(args, timeout=600)
     assert p.returncode == 2 and "refusing" in p.stderr and p.stdout.strip() == "", (p.returncode, p.stderr[-1500:])
     p = _run_bench(args, {"GANON_BENCH_ALLOW_SHARED_GPU": "1", "GANON_BENCH_EXTRAS": "tiny,slice_tiny"}, timeout=900)
@@ -181,7 +233,7 @@ def test_gpus_2_under_torchrun_and_a_wrong_gpus_flag():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
     env.update(GANON_BENCH_ALLOW_SHARED_GPU="1", GANON_BENCH_EXTRAS="tiny")
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29611",
-            os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-e2e"]
+            os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full", "--no-e2e"]
     p = subprocess.run(base + ["--gpus", "2"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.splitlines()[-1])
@@ -189,3 +241,35 @@ def test_gpus_2_under_torchrun_and_a_wrong_gpus_flag():
     p = subprocess.run(base + ["--gpus", "3"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode != 0 and "--gpus 3 but the launcher started WORLD_SIZE=2" in p.stderr
     assert not any(ln.startswith('{"metric"') for ln in p.stdout.splitlines())
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_full_run_checks(tmp_path):
+    """A plain run (the command every change is timed with) sets up, warms up, times --steps steps, writes --dump-outputs and prints
+    the record: no detail line, no CPU baseline, no oracle leg.  What it dumps is what a --full run of the same arguments dumps, and
+    that run's oracle spot check and match checksum vouch for it."""
+    import numpy as np
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    args = ["--workload", "tiny", "--steps", "3", "--warmup", "1"]
+    p = _run_bench(args + ["--dump-outputs", str(plain)], timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.splitlines()
+    assert not any(ln.startswith("bench_detail: ") for ln in lines)
+    line = json.loads(lines[-1])
+    _check(line, lines[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "Mreads/s" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(100_000 / line["ms_per_step"] / 1e3, rel=0.02)
+    assert line["cpu_baseline"] is None and line["detail"] is None and "oracle_reads_checked" not in line["config"]
+    p = _run_bench(args + ["--full", "--no-e2e", "--no-extra", "--no-cpu-baseline", "--no-variants", "--dump-outputs", str(full)], timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    fl = json.loads(p.stdout.splitlines()[-1])
+    assert fl["config"]["oracle_mismatching_reads"] == 0 and fl["config"]["oracle_reads_checked"] > 0
+    names = sorted(os.listdir(plain))
+    assert names == sorted(os.listdir(full)) and "totals.npy" in names
+    for n in names:
+        a, b = np.load(plain / n), np.load(full / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    assert sum(os.path.getsize(plain / n) for n in names) <= 64_000_000
+    t = np.load(plain / "totals.npy")
+    assert t[0] == 100_000 and t[1] > 0 and t[2] == len(np.load(plain / "match_read.npy"))   # (tiny: every read is in the dump)
+    assert f"{int(t[4]) + (int(t[5]) << 32):016x}" == fl["config"]["match_checksum_all_ranks"]
