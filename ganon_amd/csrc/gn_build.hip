@@ -8,15 +8,7 @@
 #include "gn_internal.h"
 #include <hipcub/hipcub.hpp>
 
-// seqan3::interleaved_bloom_filter hash seeds and hash_and_fit, as in gn_kernels.hip
-__constant__ uint64_t GN_BUILD_SEEDS[GN_IBF_MAX_HASH_FUNS] = GN_IBF_SEED_LIST;   // include/ganon_ibf_hash.h
-__device__ __forceinline__ uint32_t gn_build_row(uint64_t v, uint32_t i, uint32_t shift, uint64_t S)
-{
-    uint64_t x = v * GN_BUILD_SEEDS[i];
-    x ^= x >> shift;
-    x *= GN_IBF_MULTIPLIER;
-    return (uint32_t)__umul64hi(x, S);
-}
+#include "gn_build_row.h" // gn_build_row: seqan3::interleaved_bloom_filter's hash_and_fit
 
 // hashes live in per-read slots (one slot per window, gn_slot_count_kernel); read r used the first nh[r] of them
 __global__ void gn_pack_hashes_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ slot_off,

@@ -32,7 +32,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_get_stats", "gn_inflate_cuts", "gn_inflate_set_carry", "gn_stream_upload_text_device", "gn_stream_fastq_headers",
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
-               "gn_stream_upload_text_pair_devices"]
+               "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -159,6 +159,8 @@ def load_library():
     L.gn_stream_fetch_hashes.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.gn_stream_distinct_hashes.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_split.argtypes = [vp, vp, u64, u32, u64]
+    L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
+    L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
@@ -471,6 +473,25 @@ class HipGather:
             pass
 
 
+PATH_DTYPE = np.dtype([("ibf", "<u4"), ("first_bin", "<u4"), ("n_bins", "<u4"), ("reserved", "<u4"), ("hashes_per_bin", "<u8")])  # gn_path_entry
+
+
+def hashes_union(sets: Sequence[np.ndarray], device: int = 0, size_only: bool = False):
+    """gn_hashes_union: the ascending union of ascending uint64 sets (or, size_only, its size alone)"""
+    sets = [np.ascontiguousarray(a, dtype=np.uint64) for a in sets]
+    n = len(sets)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in sets])
+    sizes = np.array([len(a) for a in sets], dtype=np.uint64)
+    nu = C.c_uint64(0)
+    L = load_library()
+    if size_only:
+        _check(L.gn_hashes_union(device, ptrs, _p(sizes), n, None, 0, C.byref(nu)))
+        return nu.value
+    out = np.empty(int(sizes.sum()), dtype=np.uint64)
+    _check(L.gn_hashes_union(device, ptrs, _p(sizes), n, _p(out), len(out), C.byref(nu)))
+    return out[: nu.value].copy()
+
+
 class HipFilter:
     """Device-resident, immutable IBF / HIBF (gn_filter)."""
 
@@ -511,6 +532,16 @@ class HipFilter:
         bins = np.ascontiguousarray(bins, dtype=np.uint32)
         assert len(hashes) == len(bins)
         _check(load_library().gn_filter_emplace_ibf(self._h, ibf_idx, _p(hashes), _p(bins), len(hashes)))
+
+    def emplace_path(self, sets: Sequence[np.ndarray], paths: np.ndarray) -> None:
+        """gn_filter_emplace_path: sets[s] (ascending uint64) along paths[s] (PATH_DTYPE, shape [len(sets), depth]) of an HIBF"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(sets)
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(a) for a in sets])
+        hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        _check(load_library().gn_filter_emplace_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1]))
 
     def probe(self, hashes: np.ndarray, bins: np.ndarray) -> Tuple[int, int, int]:
         """gn_filter_probe -> (hits summed over the bins, hashes in none of the bins, index of the first such hash or -1)"""

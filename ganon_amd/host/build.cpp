@@ -14,6 +14,13 @@
 // --tmp-output-folder is accepted and validated, nothing is written there) and does the sizing arithmetic.
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
 //
+// --hibf (this project's extension, like --device): the same hash sets go into a hierarchical filter instead, written as the
+// raptor 3.0.1 index `ganon build --filter-type hibf` gets from `raptor prepare / layout / build`
+// (/root/reference/src/ganon/build_update.py:411-518; read at src/ganon-classify/GanonClassify.cpp:875-938):
+//   one user bin per target -> tree of IBFs (hibf_layout.hpp) -> exact cardinalities of the merged bins (gn_hashes_union)
+//   -> rows per IBF (gnbuild::hibf_run_bits) -> zero-filled HIBF in HBM -> every user bin ORed in along its whole path
+//   (gn_filter_emplace_path) -> IBF after IBF streamed into the file (save_hibf: the twin of ganon_amd/ibf_file.py:save_hibf).
+//
 // Differences from the reference that cannot be avoided here: targets are laid out in the order of
 // their first appearance in the input file and a target's hashes in ascending order -- the reference uses the iteration
 // order of robin_hood maps/sets, which is not reproducible without that library; which bin of a split target holds
@@ -22,6 +29,7 @@
 // seqan3::views::minimiser does when the range is shorter than its window (recollection of SeqAn3 3.3.0, unpinned).
 #include "build_params.hpp"
 #include "hasher.hpp"
+#include "hibf_layout.hpp"
 #include "hostmem.hpp"
 #include "seq_io.hpp"
 #include "tunables.hpp"
@@ -65,6 +73,9 @@ struct Config // Config.hpp:10-27
     uint16_t    threads = 1;
     bool        verbose = false, quiet = false;
     int         device = 0; // (not in the reference: which GPU)
+    bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
+    uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
+    bool        tmax_given = false, filter_size_given = false;
 };
 
 bool validate(Config& c) // Config.hpp:29-107, same messages
@@ -74,6 +85,19 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
             std::cerr << m << std::endl;
         return false;
     };
+    if (c.tmax_given && !c.hibf)
+        return say("--tmax needs --hibf");
+    if (c.hibf)
+    {
+        if (c.filter_size_given)
+            return say("--filter-size cannot be used with --hibf (the IBFs are sized from --max-fp)");
+        if (c.mode != "avg")
+            return say("--mode cannot be used with --hibf");
+        if (c.tmax_given && (c.tmax < 2 || c.tmax > 0xFFFFFFFFull))
+            return say("--tmax has to be >= 2");
+        if (!(c.max_fp > 0 && c.max_fp < 1))
+            return say("--max-fp has to be above 0 and below 1 with --hibf");
+    }
     if (c.input_file.empty())
         return say("--input-file is mandatory");
     if (!fs::exists(c.input_file))
@@ -123,8 +147,10 @@ void print_config(const Config& c) // Config.hpp:110-133
               << "--min-length        " << c.min_length << '\n'
               << "--threads           " << c.threads << '\n'
               << "--verbose           " << c.verbose << '\n'
-              << "--quiet             " << c.quiet << '\n'
-              << sep << '\n';
+              << "--quiet             " << c.quiet << '\n';
+    if (c.hibf)
+        std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
+    std::cerr << sep << '\n';
 }
 
 const char* kHelp =
@@ -144,6 +170,10 @@ const char* kHelp =
     "  -m, --tmp-output-folder arg  Folder to write temporary files (accepted; this build keeps the hashes in memory)\n"
     "  -t, --threads arg            Number of threads (parser threads, one device stream each)\n"
     "      --device arg             HIP device index. Default: 0\n"
+    "      --hibf                   Write a hierarchical filter (raptor 3.0.1 index, one user bin per target) sized from\n"
+    "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
+    "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
+    "                               Default: ceil(sqrt(targets) / 64) * 64\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -186,14 +216,14 @@ int parse_args(int argc, char** argv, Config& c)
         auto s = shorts.find(a);
         if (s != shorts.end())
             a = s->second;
-        if (a == "--help" || a == "--version" || a == "--verbose" || a == "--quiet")
+        if (a == "--help" || a == "--version" || a == "--verbose" || a == "--quiet" || a == "--hibf")
         {
             vals[a] = has ? v : "true";
             continue;
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -251,7 +281,10 @@ int parse_args(int argc, char** argv, Config& c)
         if (vals.count("--max-fp"))
             c.max_fp = d("--max-fp");
         if (vals.count("--filter-size"))
-            c.filter_size = d("--filter-size");
+            c.filter_size = d("--filter-size"), c.filter_size_given = true;
+        if (vals.count("--tmax"))
+            c.tmax = u("--tmax", ~0ull), c.tmax_given = true;
+        c.hibf = vals.count("--hibf") && vals["--hibf"] != "false";
         if (vals.count("--mode"))
             c.mode = vals["--mode"];
         if (vals.count("--min-length"))
@@ -278,6 +311,7 @@ struct Target
     std::string              name;
     std::vector<std::string> files;
     std::vector<uint64_t>    hashes; // per file: its distinct hashes, ascending; files behind each other (:236-238)
+    std::vector<uint64_t>    file_ends; // where each file's hashes end in `hashes` (--hibf unites the files of a target)
 };
 
 struct Totals // :52-59
@@ -390,6 +424,7 @@ void hash_targets(const Config& c, std::vector<Target>& targets, std::atomic<siz
                     file_hashes.erase(std::unique(file_hashes.begin(), file_hashes.end()), file_hashes.end());
                 }
                 tg.hashes.insert(tg.hashes.end(), file_hashes.begin(), file_hashes.end());
+                tg.file_ends.push_back(tg.hashes.size());
             }
         }
     }
@@ -536,6 +571,317 @@ struct Lap
     double seconds() const { return std::chrono::duration<double>(e - b).count(); }
 };
 
+// ---- --hibf ----------------------------------------------------------------------------------------------------------------------
+
+struct HibfShape // IBF i of the tree as it is created and written
+{
+    uint64_t             bins = 0, rows = 0;
+    std::vector<int64_t> next_ibf_id, bin_to_user;
+};
+
+// The raptor 3.0.1 index (reader: GanonClassify.cpp:875-938 with hibf.hpp:163-169,293-298), field for field what
+// ganon_amd/ibf_file.py:save_hibf writes; the matrices streamed IBF after IBF out of HBM.
+bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions, const std::vector<std::string>& files,
+               std::string& err)
+{
+    const int fd = ::open(c.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0)
+    {
+        err = "cannot write " + c.output_file;
+        return false;
+    }
+    uint64_t at    = 0;
+    bool     ok    = true;
+    auto     flush = [&](Writer& w) {
+        ok = ok && pwrite_all(fd, w.buf.data(), w.buf.size(), at);
+        at += w.buf.size();
+        w.buf.clear();
+    };
+    Writer w;
+    w.raw<uint32_t>(1);                                     // raptor index version
+    w.raw<uint64_t>(c.window_size);
+    w.raw<uint64_t>(c.kmer_size);                           // seqan3::shape: size, bits
+    w.raw<uint64_t>(c.kmer_size >= 64 ? ~0ull : (1ull << c.kmer_size) - 1);
+    w.raw<uint8_t>(1);                                      // parts
+    w.raw<uint8_t>(0);                                      // compressed
+    w.raw<uint64_t>(files.size());                          // bin_path: one file per user bin
+    for (const std::string& f : files)
+    {
+        w.raw<uint64_t>(1);
+        w.str(f);
+    }
+    w.raw<double>(c.max_fp);                                // fpr
+    w.raw<uint8_t>(1);                                      // is_hibf
+    w.raw<uint64_t>(ibfs.size());                           // ibf_vector
+    flush(w);
+    constexpr uint64_t kChunk = 256ull << 20;
+    uint64_t           stage_bytes = 0;
+    for (const HibfShape& s : ibfs)
+        stage_bytes = std::max(stage_bytes, std::max<uint64_t>(1, std::min<uint64_t>(kChunk, s.rows * ((s.bins + 63) >> 6) * 8) / (((s.bins + 63) >> 6) * 8)) *
+                                                (((s.bins + 63) >> 6) * 8));
+    void* stage = nullptr;
+    if (ok && gn_pinned_alloc(stage_bytes, &stage) != GN_OK)
+    {
+        err = gnhost::hip_error();
+        ok  = false;
+    }
+    for (uint32_t i = 0; ok && i < ibfs.size(); ++i)
+    {
+        const HibfShape& s = ibfs[i];
+        const uint64_t   W = (s.bins + 63) >> 6, row_bytes = W * 8;
+        // seqan3::interleaved_bloom_filter: bins, technical_bins, bin_size, hash_shift, bin_words, hash_funs, sdsl bit_vector
+        w.raw<uint64_t>(s.bins);
+        w.raw<uint64_t>(W * 64);
+        w.raw<uint64_t>(s.rows);
+        w.raw<uint64_t>((uint64_t)__builtin_clzll(s.rows));
+        w.raw<uint64_t>(W);
+        w.raw<uint64_t>(hash_functions);
+        w.raw<uint8_t>(1);
+        w.raw<float>(1.5f);
+        w.raw<uint64_t>(W * 64 * s.rows);
+        flush(w);
+        const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(kChunk, s.rows * row_bytes) / row_bytes);
+        for (uint64_t row = 0; ok && row < s.rows; row += per)
+        {
+            const uint64_t n = std::min<uint64_t>(per, s.rows - row);
+            if (gn_filter_download_rows(flt, i, row, n, static_cast<uint64_t*>(stage)) != GN_OK)
+            {
+                err = gnhost::hip_error();
+                ok  = false;
+                break;
+            }
+            if (!pwrite_all(fd, stage, n * row_bytes, at))
+                ok = false;
+            at += n * row_bytes;
+        }
+    }
+    auto tables = [&](bool next) {
+        w.raw<uint64_t>(ibfs.size());
+        for (const HibfShape& s : ibfs)
+        {
+            const std::vector<int64_t>& v = next ? s.next_ibf_id : s.bin_to_user;
+            w.raw<uint64_t>(v.size());
+            w.buf.append(reinterpret_cast<const char*>(v.data()), v.size() * 8);
+        }
+    };
+    tables(true);                                           // next_ibf_id
+    w.raw<uint64_t>(files.size());                          // user_bins: user_bin_filenames
+    for (const std::string& f : files)
+        w.str(f);
+    tables(false);                                          //            ibf_bin_to_filename_position
+    flush(w);
+    if (stage)
+        gn_pinned_free(stage);
+    ::close(fd);
+    if (!ok && err.empty())
+        err = "write error on " + c.output_file;
+    return ok;
+}
+
+bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
+{
+    Lap            uniting, filling, writing;
+    const uint8_t  h = c.hash_functions == 0 ? 4 : c.hash_functions; // (what `ganon build` passes to raptor, config.py:138-145)
+    auto           fail = [](const std::string& m) {
+        std::cerr << m << std::endl;
+        return false;
+    };
+
+    // one user bin per target with a hash, in first-appearance order; its set = the union of its files' sets
+    uniting.start();
+    std::vector<uint32_t>    user_target;
+    std::vector<uint64_t>    counts;
+    std::vector<std::string> files;
+    const std::string        dir = !c.tmp_output_folder.empty() ? c.tmp_output_folder
+                                   : fs::path(c.output_file).has_parent_path() ? fs::path(c.output_file).parent_path().string()
+                                                                               : std::string(".");
+    for (uint32_t t = 0; t < targets.size(); ++t)
+    {
+        Target& tg = targets[t];
+        if (tg.hashes.empty())
+            continue;
+        if (tg.file_ends.size() > 1)
+        {
+            std::vector<const uint64_t*> sets;
+            std::vector<uint64_t>        sizes;
+            uint64_t                     a = 0;
+            for (uint64_t e : tg.file_ends)
+            {
+                sets.push_back(tg.hashes.data() + a);
+                sizes.push_back(e - a);
+                a = e;
+            }
+            std::vector<uint64_t> all(tg.hashes.size());
+            uint64_t              n = 0;
+            if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), all.data(), all.size(), &n) != GN_OK)
+                return fail(gn_last_error());
+            all.resize(n);
+            tg.hashes.swap(all);
+        }
+        user_target.push_back(t);
+        counts.push_back(tg.hashes.size());
+        std::string name = tg.name;
+        for (size_t p = 0; (p = name.find(' ', p)) != std::string::npos; p += 3)
+            name.replace(p, 1, "---");
+        files.push_back(dir + "/" + name + ".minimiser");
+    }
+    if (counts.empty())
+        return fail("No valid sequences to build");
+    const uint64_t n_user = counts.size();
+    uint64_t       tmax   = c.tmax;
+    if (!c.tmax_given)
+        tmax = (uint64_t)std::ceil(std::sqrt((double)n_user) / 64.0) * 64; // build_update.py:487
+    const gnhibf::Layout lay = gnhibf::lay_out(counts, (uint32_t)tmax);
+
+    // rows per IBF: the largest need of its runs; a merged bin holds the union of the sets below it
+    std::vector<HibfShape> ibfs(lay.ibfs.size());
+    uint64_t               device_bits = 0;
+    for (uint32_t i = 0; i < lay.ibfs.size(); ++i)
+    {
+        const gnhibf::Ibf& f = lay.ibfs[i];
+        uint64_t           rows = 0;
+        for (const gnhibf::Run& r : f.runs)
+        {
+            uint64_t n = 0;
+            if (r.user >= 0)
+                n = counts[r.user];
+            else
+            {
+                std::vector<const uint64_t*> sets;
+                std::vector<uint64_t>        sizes;
+                for (uint32_t u : lay.ibfs[r.child].members)
+                {
+                    sets.push_back(targets[user_target[u]].hashes.data());
+                    sizes.push_back(counts[u]);
+                }
+                if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), nullptr, 0, &n) != GN_OK)
+                    return fail(gn_last_error());
+            }
+            rows = std::max(rows, gnbuild::hibf_run_bits(n, r.n_bins, c.max_fp, h));
+        }
+        ibfs[i].bins = f.bins;
+        ibfs[i].rows = rows;
+        gnhibf::tables_of(lay, i, ibfs[i].next_ibf_id, ibfs[i].bin_to_user);
+        device_bits += rows * gn_hibf_row_stride_words((f.bins + 63) >> 6) * 64;
+    }
+    uniting.stop();
+    if (c.verbose)
+    {
+        std::cerr << "hibf_config:" << '\n'
+                  << "user_bins      " << n_user << '\n'
+                  << "tmax           " << tmax << '\n'
+                  << "ibfs           " << ibfs.size() << '\n'
+                  << "levels         " << lay.levels << '\n'
+                  << "hash_functions " << unsigned(h) << '\n'
+                  << "max_fp         " << c.max_fp << '\n';
+        std::cerr << "Filter size: " << device_bits << " Bits (" << device_bits / static_cast<double>(8388608u) << " Megabytes)" << std::endl;
+    }
+
+    filling.start();
+    gn_filter* flt = nullptr;
+    {
+        std::vector<gn_ibf_desc>    descs(ibfs.size());
+        std::vector<const int64_t*> nx(ibfs.size()), bu(ibfs.size());
+        for (uint32_t i = 0; i < ibfs.size(); ++i)
+        {
+            gn_ibf_desc& d = descs[i];
+            d.rows = nullptr, d.bins = ibfs[i].bins, d.bin_words = (ibfs[i].bins + 63) >> 6, d.bin_size = ibfs[i].rows, d.hash_funs = h;
+            d.hash_shift = (uint32_t)__builtin_clzll(ibfs[i].rows);
+            nx[i] = ibfs[i].next_ibf_id.data(), bu[i] = ibfs[i].bin_to_user.data();
+        }
+        if (gn_filter_upload_hibf(c.device, (uint32_t)ibfs.size(), descs.data(), nx.data(), bu.data(), n_user, &flt) != GN_OK)
+            return fail(gn_last_error());
+    }
+    {
+        // every user bin's path: its run in its leaf IBF, then the merged bin that leads there in each IBF above
+        const uint32_t             depth = lay.levels;
+        std::vector<gn_path_entry> path_of(n_user * depth, gn_path_entry{ 0, 0, 0, 0, 0 });
+        for (uint32_t i = 0; i < lay.ibfs.size(); ++i)
+            for (const gnhibf::Run& r : lay.ibfs[i].runs)
+            {
+                if (r.user < 0)
+                    continue;
+                gn_path_entry* p = &path_of[(size_t)r.user * depth];
+                *p++             = gn_path_entry{ i, r.first, r.n_bins, 0, (counts[r.user] + r.n_bins - 1) / r.n_bins };
+                for (uint32_t at = i; lay.ibfs[at].parent >= 0; at = (uint32_t)lay.ibfs[at].parent)
+                    *p++ = gn_path_entry{ (uint32_t)lay.ibfs[at].parent, lay.ibfs[at].parent_bin, 1, 0, 1 };
+            }
+        // large sets go as they lie; small ones are gathered so that a launch has enough of them
+        constexpr uint64_t         kBatch = 16ull << 20, kAlone = 4ull << 20;
+        std::vector<uint64_t>      pool, off{ 0 };
+        std::vector<gn_path_entry> paths;
+        bool                       ok    = true;
+        auto                       flush = [&] {
+            if (off.size() > 1 && gn_filter_emplace_path(flt, pool.data(), off.data(), (uint32_t)off.size() - 1, paths.data(), depth) != GN_OK)
+                ok = false;
+            pool.clear(), paths.clear(), off.assign(1, 0);
+        };
+        for (uint64_t u = 0; ok && u < n_user; ++u)
+        {
+            const std::vector<uint64_t>& hs = targets[user_target[u]].hashes;
+            if (hs.size() >= kAlone)
+            {
+                const uint64_t one[2] = { 0, hs.size() };
+                ok = gn_filter_emplace_path(flt, hs.data(), one, 1, &path_of[u * depth], depth) == GN_OK;
+                continue;
+            }
+            pool.insert(pool.end(), hs.begin(), hs.end());
+            off.push_back(pool.size());
+            paths.insert(paths.end(), path_of.begin() + u * depth, path_of.begin() + (u + 1) * depth);
+            if (pool.size() >= kBatch)
+                flush();
+        }
+        if (ok)
+            flush();
+        if (!ok)
+        {
+            const std::string m = gn_last_error();
+            gn_filter_free(flt);
+            return fail(m);
+        }
+    }
+    filling.stop();
+
+    writing.start();
+    std::string err;
+    const bool  saved = save_hibf(c, flt, ibfs, h, files, err);
+    gn_filter_free(flt);
+    if (!saved)
+        return fail(err);
+    writing.stop();
+    whole.stop();
+
+    if (!c.quiet)
+    {
+        if (c.verbose)
+        {
+            auto block = [](const char* a, const char* pad, const Lap& l) {
+                std::cerr << a << stamp(l.b) << '\n' << pad << "    end: " << stamp(l.e) << '\n' << pad << "elapsed (s): " << l.seconds() << '\n';
+            };
+            block("Count/save hashes start: ", "                ", counting);
+            block("Layout and unions start: ", "                ", uniting);
+            block("Building filter   start: ", "                ", filling);
+            block("Saving filer      start: ", "                ", writing);
+            block("ganon-build       start: ", "                ", whole);
+            std::cerr << std::endl;
+        }
+        const double elapsed = whole.seconds();
+        std::cerr << "ganon-build processed " << totals.sequences << " sequences / " << totals.files << " files ("
+                  << totals.length_bp / 1000000.0 << " Mbp) in " << elapsed << " seconds ("
+                  << (totals.length_bp / 1000000.0) / (elapsed / 60.0) << " Mbp/m)" << std::endl;
+        if (totals.invalid_files > 0)
+            std::cerr << " - " << totals.invalid_files << " invalid files skipped" << std::endl;
+        if (totals.skipped_sequences > 0)
+            std::cerr << " - " << totals.skipped_sequences << " sequences skipped" << std::endl;
+        std::cerr << " - hibf: " << n_user << " user bins in " << ibfs.size() << " IBFs on " << lay.levels << " level(s), tmax " << tmax << std::endl;
+        std::cerr << std::fixed << std::setprecision(2) << " - filter size: " << device_bits / static_cast<double>(8388608u) << "MB" << std::endl;
+        // (one line a caller can parse: where the time went)
+        std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
+                  << " write " << writing.seconds() << std::endl;
+    }
+    return true;
+}
+
 bool run(Config c)
 {
     if (!validate(c))
@@ -593,6 +939,9 @@ bool run(Config c)
         }
     }
     counting.stop();
+
+    if (c.hibf)
+        return run_hibf(c, targets, totals, whole, counting);
 
     sizing.start();
     IbfParams p;

@@ -215,4 +215,11 @@ std::vector<BinSpan> lay_out_bins(const IbfParams& p, const std::vector<uint64_t
     return bins;
 }
 
+uint64_t hibf_run_bits(uint64_t hashes, uint64_t splits, double max_fp, uint8_t hash_functions)
+{
+    const uint64_t share   = (hashes + splits - 1) / splits;
+    const double   per_bin = 1.0 - std::exp(std::log(1.0 - max_fp) / splits);
+    return bits_for(per_bin, share, hash_functions);
+}
+
 } // namespace gnbuild

@@ -47,4 +47,11 @@ void true_fp(const std::vector<uint64_t>& counts, IbfParams& p);
 // create_bin_map_hash (:619-653), targets in the order given; shares[t] = hashes per bin of target t
 std::vector<BinSpan> lay_out_bins(const IbfParams& p, const std::vector<uint64_t>& counts, std::vector<uint64_t>* shares = nullptr);
 
+
+// --hibf: rows a run of `splits` technical bins needs when it holds `hashes` distinct hashes in equal shares and the user bin
+// (all its bins together) may answer falsely at rate max_fp: bits_for(1 - (1 - max_fp)^(1/splits), ceil(hashes / splits), h), the
+// per-bin rate written as split_correction writes it.  A merged bin is a run of one bin holding the union of the sets below it.
+// An IBF has the largest figure of its runs.  No counterpart in the reference: raptor sizes its IBFs from sketches.
+uint64_t hibf_run_bits(uint64_t hashes, uint64_t splits, double max_fp, uint8_t hash_functions);
+
 } // namespace gnbuild

@@ -7,6 +7,8 @@ minimal device-side build.
         kept -- one rank's column slice of a bin-range partitioned filter (ganon_amd.partition) -- so that no rank ever
         materialises the whole matrix, on the host or on the device
   save_ibf(path, ...)                       the same layout written from a device filter (rows are downloaded in chunks)
+  save_hibf(path, ...) / read_hibf_meta(path)  a raptor 3.0.1 index written from a device-resident HIBF, and everything of such a
+        file but the bits (what `ganon-build --hibf` writes as well)
   build_ibf(targets, k, w, ...)             minimisers of the target sequences on the device (gn_stream_minimisers), distinct
         hashes per target, bins assigned like create_bin_map_hash (GanonBuild.cpp:619-653), bits set by gn_filter_emplace
         (GanonBuild.cpp:694).  The size optimiser of ganon-build (:428-616) is NOT restated: bin size and number of hash
@@ -276,6 +278,90 @@ def save_hibf(path: str, flt, ibfs: Sequence[Tuple[int, int, int]], next_ibf_id,
         f.write(struct.pack("<Q", len(bin_to_user)))
         for a in bin_to_user:
             f.write(struct.pack("<Q", len(a)) + np.ascontiguousarray(a, dtype="<i8").tobytes())
+
+
+@dataclass
+class HibfFileMeta:
+    version: int = 0
+    window_size: int = 0
+    kmer_size: int = 0
+    shape_bits: int = 0
+    parts: int = 0
+    compressed: int = 0
+    fpr: float = 0.0
+    is_hibf: int = 0
+    bin_path: List[List[str]] = field(default_factory=list)          # per user bin: its files, as written
+    ibfs: List[Tuple[int, int, int, int]] = field(default_factory=list)  # per IBF: (bins, rows, hash_funs, payload offset)
+    next_ibf_id: List[np.ndarray] = field(default_factory=list)
+    bin_to_user: List[np.ndarray] = field(default_factory=list)
+    user_bin_filenames: List[str] = field(default_factory=list)
+    names: List[str] = field(default_factory=list)                    # target of every user bin (GanonClassify.cpp:910-935)
+
+    def payload(self, path: str, i: int) -> np.ndarray:
+        """the bit matrix of IBF i: [rows, ceil(bins / 64)] uint64"""
+        bins, rows, _, at = self.ibfs[i]
+        W = (bins + 63) >> 6
+        return np.fromfile(path, dtype="<u8", offset=at, count=rows * W).reshape(rows, W)
+
+
+def read_hibf_meta(path: str) -> HibfFileMeta:
+    """everything of a raptor 3.0.1 index but the bits (the layout save_hibf writes; reader GanonClassify.cpp:875-938)"""
+    m = HibfFileMeta()
+    size = os.path.getsize(path)
+
+    def vec_i64(f):
+        out = []
+        (n,) = _rd(f, "<Q")
+        if n > size:
+            raise IbfFormatError(f"{path}: implausible container size {n}")
+        for _ in range(n):
+            (c,) = _rd(f, "<Q")
+            if c * 8 > size:
+                raise IbfFormatError(f"{path}: implausible container size {c}")
+            out.append(np.frombuffer(f.read(c * 8), dtype="<i8").copy())
+        return out
+
+    with open(path, "rb") as f:
+        (m.version,) = _rd(f, "<I")
+        m.window_size, m.kmer_size, m.shape_bits = _rd(f, "<QQQ")
+        m.parts, m.compressed = _rd(f, "<BB")
+        (n,) = _rd(f, "<Q")
+        if n > size:
+            raise IbfFormatError(f"{path}: implausible container size {n}")
+        for _ in range(n):
+            (c,) = _rd(f, "<Q")
+            m.bin_path.append([_rd_str(f) for _ in range(c)])
+        (m.fpr,) = _rd(f, "<d")
+        (m.is_hibf,) = _rd(f, "<B")
+        (n,) = _rd(f, "<Q")
+        if n == 0 or n > size // 48:
+            raise IbfFormatError(f"{path}: implausible number of IBFs {n}")
+        for _ in range(n):
+            bins, tech, rows, shift, W, h = _rd(f, "<6Q")
+            if bins == 0 or rows == 0 or W != (bins + 63) >> 6 or tech != 64 * W or shift != 64 - rows.bit_length() or not 1 <= h <= 5:
+                raise IbfFormatError(f"{path}: not a SeqAn3 IBF (inconsistent shape fields)")
+            width, _, bits = _rd(f, "<BfQ")
+            if width != 1 or bits != tech * rows:
+                raise IbfFormatError(f"{path}: unexpected sdsl bit_vector header")
+            m.ibfs.append((bins, rows, h, f.tell()))
+            f.seek(rows * W * 8, 1)
+        m.next_ibf_id = vec_i64(f)
+        (n,) = _rd(f, "<Q")
+        if n > size:
+            raise IbfFormatError(f"{path}: implausible container size {n}")
+        m.user_bin_filenames = [_rd_str(f) for _ in range(n)]
+        m.bin_to_user = vec_i64(f)
+        if f.tell() != size:
+            raise IbfFormatError(f"{path}: {size - f.tell()} trailing bytes after the HIBF")
+    if len(m.next_ibf_id) != len(m.ibfs) or len(m.bin_to_user) != len(m.ibfs):
+        raise IbfFormatError(f"{path}: next_ibf_id / ibf_bin_to_filename_position do not cover every IBF")
+    for lst in m.bin_path:
+        name = os.path.basename(lst[0]) if lst else ""
+        at = name.find(".minimiser")
+        if at >= 0:
+            name = name[:at]
+        m.names.append(name.replace("|||", ".").replace("---", " "))
+    return m
 
 
 def bloom_bin_size(n_hashes: int, max_fp: float, hash_funs: int) -> int:

@@ -399,6 +399,30 @@ int gn_filter_emplace_split(gn_filter* f, const uint64_t* hashes, uint64_t n, ui
 int gn_filter_probe(gn_filter* f, const uint64_t* hashes, uint64_t n, const uint32_t* bins, uint32_t n_bins, uint64_t* hits,
                     uint64_t* missing, uint64_t* first_missing);
 
+/* `ganon-build --hibf` (no counterpart in the reference's own sources: `ganon build --filter-type hibf` runs `raptor prepare / layout /
+ * build`, /root/reference/src/ganon/build_update.py:411-518; the index it leaves is what GanonClassify.cpp:875-938 reads).
+ * gn_hashes_union: the ascending union of n_sets ASCENDING hash sets in host memory (sets[i][0 .. sizes[i])) and its size -- the exact
+ * cardinality of a merged bin.  out may be NULL for the size alone (GN_EOVERFLOW with *n_union set when cap is too small).  At most
+ * 2^31 - 1 hashes over all sets of one call (GN_ERANGE beyond).
+ * gn_filter_emplace_path: inserts n_sets hash sets -- set s = hashes[set_off[s] .. set_off[s + 1]), ascending -- into an HIBF created
+ * with rows == NULL, each along its whole root-to-leaf path in one launch: paths[s * depth + d] says where set s goes in one IBF of
+ * the tree -- hash i of the set into bin first_bin + i / hashes_per_bin (a user bin's run of n_bins bins in its leaf IBF, the rule
+ * of gn_filter_emplace_split), or, with n_bins == 1, every hash into first_bin (a single bin; a merged bin above the user bin:
+ * inserting every member sets the bits their union would).  n_bins == 0 ends a path shorter than `depth`.  Order of the entries
+ * is free; every bin is checked against its IBF before anything is launched. */
+typedef struct
+{
+    uint32_t ibf;            /* index of the IBF in the filter */
+    uint32_t first_bin;
+    uint32_t n_bins;         /* 0: unused entry */
+    uint32_t reserved;
+    uint64_t hashes_per_bin; /* ignored when n_bins == 1 */
+} gn_path_entry;
+int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* sizes, uint32_t n_sets, uint64_t* out, uint64_t cap,
+                    uint64_t* n_union);
+int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                           uint32_t depth);
+
 /* Parity / debugging taps (tests only): minimiser hashes of the resident batch in emission order
  * (hash_off[n_reads+1]; hashes[cap]) and dense per-bin counts of reads [read_begin, read_end)
  * (flat IBF: uint16[bins] per read == counting_agent::bulk_count; HIBF: uint16[n_user_bins] per read

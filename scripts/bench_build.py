@@ -1,6 +1,9 @@
 """Throughput of the product's ganon-build on synthetic genomes: N FASTA files of L random bases each (70-column lines) are
 written to a tmpfs, then `ganon-build` runs start to finish (parse -> device minimisers + sort/unique -> sizing -> device
-insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_files=512] [len=4000000] [threads=16] [dir=/dev/shm]"""
+insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_files=512] [len=4000000] [threads=16] [dir=/dev/shm]
+  --hibf          the same FASTA built flat AND as HIBF (`ganon-build --hibf`), alternating, one run each to warm up and then the median
+                  of --runs (5) each, both at --max-fp (0.05) and --hash-functions (4); the HIBF time split into hash / union / emplace /
+                  write; --tmax N is passed on.  Prints one JSON object with "flat" and "hibf"."""
 import json
 import os
 import re
@@ -11,10 +14,20 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-n_files = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-L = int(sys.argv[2]) if len(sys.argv) > 2 else 4_000_000
-threads = int(sys.argv[3]) if len(sys.argv) > 3 else 16
-d = os.path.join(sys.argv[4] if len(sys.argv) > 4 else "/dev/shm", "ganon_build_bench")
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": ""}
+pos, hibf, argv = [], False, sys.argv[1:]
+while argv:
+    a = argv.pop(0)
+    if a == "--hibf":
+        hibf = True
+    elif a in opts:
+        opts[a] = argv.pop(0)
+    else:
+        pos.append(a)
+n_files = int(pos[0]) if len(pos) > 0 else 512
+L = int(pos[1]) if len(pos) > 1 else 4_000_000
+threads = int(pos[2]) if len(pos) > 2 else 16
+d = os.path.join(pos[3] if len(pos) > 3 else "/dev/shm", "ganon_build_bench")
 os.makedirs(d, exist_ok=True)
 rng = np.random.default_rng(1)
 lut = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -31,27 +44,77 @@ with open(os.path.join(d, "in.tsv"), "w") as tsv:
         tsv.write(f"{f}\tT{i}\n")
 out = {"files": n_files, "bases_per_file": L, "total_gbp": round(n_files * L / 1e9, 3), "threads": threads}
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
-t0 = time.time()
-p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", "0.05"],
-                   capture_output=True, text=True)
-out["rc"], out["wall_s"] = p.returncode, round(time.time() - t0, 2)
-for key, pat in (("count_hashes_s", r"Count/save hashes start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
-                 ("sizing_s", r"Estimate params   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
-                 ("fill_s", r"Building filter   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
-                 ("write_s", r"Saving filer      start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
-                 ("total_s", r"ganon-build       start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)")):
-    m = re.search(pat, p.stderr)
+
+
+def flat_run(max_fp="0.05", extra=()):
+    res = {}
+    t0 = time.time()
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", max_fp] + list(extra),
+                       capture_output=True, text=True)
+    res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    for key, pat in (("count_hashes_s", r"Count/save hashes start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
+                     ("sizing_s", r"Estimate params   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
+                     ("fill_s", r"Building filter   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
+                     ("write_s", r"Saving filer      start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
+                     ("total_s", r"ganon-build       start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)")):
+        m = re.search(pat, p.stderr)
+        if m:
+            res[key] = float(m.group(1))
+    m = re.search(r"ganon-build processed .*", p.stderr)
+    res["summary"] = m.group(0) if m else p.stderr[-300:]
+    for key in ("n_bins", "max_hashes_bin", "bin_size_bits", "hash_functions"):
+        m = re.search(key + r"\s+(\d+)", p.stderr)
+        if m:
+            res[key] = int(m.group(1))
+    if p.returncode == 0:
+        res["ibf_bytes"] = os.path.getsize(os.path.join(d, "db.ibf"))
+        res["ibf_gib"] = round(res["ibf_bytes"] / 2**30, 3)
+        res["mbp_per_s"] = round(n_files * L / 1e6 / res.get("total_s", res["wall_s"]), 1)
+    return res
+
+
+def hibf_run():
+    res = {}
+    t0 = time.time()
+    cmd = [exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.hibf"), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else [])
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    m = re.search(r" - seconds: hash ([0-9.eE+-]+) union ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
     if m:
-        out[key] = float(m.group(1))
-m = re.search(r"ganon-build processed .*", p.stderr)
-out["summary"] = m.group(0) if m else p.stderr[-300:]
-for key in ("n_bins", "max_hashes_bin", "bin_size_bits", "hash_functions"):
-    m = re.search(key + r"\s+(\d+)", p.stderr)
+        res["hash_s"], res["union_s"], res["emplace_s"], res["write_s"] = (float(x) for x in m.groups())
+    m = re.search(r"ganon-build       start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)", p.stderr)
     if m:
-        out[key] = int(m.group(1))
-if p.returncode == 0:
-    out["ibf_gib"] = round(os.path.getsize(os.path.join(d, "db.ibf")) / 2**30, 3)
-    out["mbp_per_s"] = round(n_files * L / 1e6 / out.get("total_s", out["wall_s"]), 1)
+        res["total_s"] = float(m.group(1))
+    m = re.search(r" - hibf: .*", p.stderr)
+    res["summary"] = m.group(0).strip() if m else p.stderr[-300:]
+    if p.returncode == 0:
+        res["hibf_bytes"] = os.path.getsize(os.path.join(d, "db.hibf"))
+        res["mbp_per_s"] = round(n_files * L / 1e6 / res.get("total_s", res["wall_s"]), 1)
+    return res
+
+
+def median_of(runs):
+    """the run with the median total time, and every run's total"""
+    good = sorted((r for r in runs if r["rc"] == 0), key=lambda r: r.get("total_s", r["wall_s"]))
+    if not good:
+        return runs[-1]
+    mid = dict(good[len(good) // 2])
+    mid["totals_s"] = [r.get("total_s", r["wall_s"]) for r in runs]
+    return mid
+
+
+if not hibf:
+    out.update(flat_run())
+else:
+    flat_extra = ["-s", opts["--hash-functions"]]
+    flat_run(opts["--max-fp"], flat_extra), hibf_run()  # one run each to warm up
+    flats, hibfs = [], []
+    for _ in range(int(opts["--runs"])):
+        flats.append(flat_run(opts["--max-fp"], flat_extra))
+        hibfs.append(hibf_run())
+    out["max_fp"], out["hash_functions"], out["runs"] = float(opts["--max-fp"]), int(opts["--hash-functions"]), int(opts["--runs"])
+    out["flat"], out["hibf"] = median_of(flats), median_of(hibfs)
 for f in os.listdir(d):
     os.remove(os.path.join(d, f))
 os.rmdir(d)
