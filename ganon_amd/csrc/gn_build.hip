@@ -32,46 +32,25 @@ __global__ void gn_pack_hashes_kernel(const uint64_t* __restrict__ hashes, const
 
 static int gn_build_reserve(gn_stream* s, uint64_t n)
 {
-    if (s->build_cap >= n && s->d_build[0])
+    if (s->build.cap >= n)
         return GN_OK;
-    for (auto& p : s->d_build)
-    {
-        if (p)
-            hipFree(p);
-        p = nullptr;
-    }
-    if (s->d_build_tmp)
-        hipFree(s->d_build_tmp);
-    s->d_build_tmp = nullptr;
+    // built aside and moved into the stream when it is whole: a failed allocation leaves the stream without the group
+    GnBuildBufs b;
+    b.d_ctr  = std::move(s->build.d_ctr); // (the counters do not grow)
+    s->build = GnBuildBufs{};             // free before malloc
     const uint64_t cap = n + n / 8 + 1024;
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_build[0]), cap * 8));
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_build[1]), cap * 8));
-    if (!s->d_build_ctr)
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_build_ctr), 2 * sizeof(unsigned long long)));
-    size_t a = 0, b = 0;
-    hipcub::DeviceRadixSort::SortKeys(nullptr, a, s->d_build[0], s->d_build[1], (int)cap, 0, 64, s->st);
-    hipcub::DeviceSelect::Unique(nullptr, b, s->d_build[1], s->d_build[0], s->d_build_ctr + 1, (int)cap, s->st);
-    s->build_tmp_bytes = a > b ? a : b;
-    GN_HIP(hipMalloc(&s->d_build_tmp, s->build_tmp_bytes ? s->build_tmp_bytes : 1));
-    s->build_cap = cap;
+    GN_HIP(b.d_build[0].alloc(cap));
+    GN_HIP(b.d_build[1].alloc(cap));
+    if (!b.d_ctr)
+        GN_HIP(b.d_ctr.alloc(2));
+    size_t x = 0, y = 0;
+    hipcub::DeviceRadixSort::SortKeys(nullptr, x, b.d_build[0].get(), b.d_build[1].get(), (int)cap, 0, 64, s->st);
+    hipcub::DeviceSelect::Unique(nullptr, y, b.d_build[1].get(), b.d_build[0].get(), b.d_ctr + 1, (int)cap, s->st);
+    b.tmp_bytes = x > y ? x : y;
+    GN_HIP(b.d_tmp.alloc(b.tmp_bytes));
+    b.cap    = cap;
+    s->build = std::move(b);
     return GN_OK;
-}
-
-void gn_build_release(gn_stream* s)
-{
-    for (auto& p : s->d_build)
-    {
-        if (p)
-            hipFree(p);
-        p = nullptr;
-    }
-    if (s->d_build_tmp)
-        hipFree(s->d_build_tmp);
-    if (s->d_build_ctr)
-        hipFree(s->d_build_ctr);
-    s->d_build_tmp = nullptr;
-    s->d_build_ctr = nullptr;
-    s->build_cap   = 0;
 }
 
 extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t cap, uint64_t* n_distinct)
@@ -92,7 +71,7 @@ extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t c
             return GN_OK;
         if (cap < s->build_distinct)
             return gn_fail(GN_EOVERFLOW, "hash buffer too small: need %llu", (unsigned long long)s->build_distinct);
-        GN_HIP(hipMemcpy(out, s->d_build[0], s->build_distinct * 8, hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(out, s->build.d_build[0], s->build_distinct * 8, hipMemcpyDeviceToHost));
         return GN_OK;
     }
     // every read's count is at most its window count, so the slot total bounds the packed size
@@ -109,25 +88,25 @@ extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t c
     int rc = gn_build_reserve(s, slots);
     if (rc)
         return rc;
-    GN_HIP(hipMemsetAsync(s->d_build_ctr, 0, 2 * sizeof(unsigned long long), s->st));
+    GN_HIP(hipMemsetAsync(s->build.d_ctr, 0, 2 * sizeof(unsigned long long), s->st));
     hipLaunchKernelGGL(gn_pack_hashes_kernel, dim3((unsigned)(((uint64_t)n * 64 + 255) / 256)), dim3(256), 0, s->st, s->d_hashes,
-                       s->d_slot_off, s->d_nh, n, s->d_build[0], s->d_build_ctr);
+                       s->d_slot_off, s->d_nh, n, s->build.d_build[0], s->build.d_ctr);
     GN_HIP(hipGetLastError());
     unsigned long long total = 0;
-    GN_HIP(hipMemcpyAsync(&total, s->d_build_ctr, 8, hipMemcpyDeviceToHost, s->st));
+    GN_HIP(hipMemcpyAsync(&total, s->build.d_ctr, 8, hipMemcpyDeviceToHost, s->st));
     GN_HIP(hipStreamSynchronize(s->st));
     if (total == 0)
     {
         s->build_distinct = 0;
         return GN_OK;
     }
-    size_t    tmp      = s->build_tmp_bytes;
+    size_t    tmp      = s->build.tmp_bytes;
     const int end_bit  = (int)(2 * s->k > 64 ? 64 : 2 * s->k); // values are below 4^k
-    GN_HIP(hipcub::DeviceRadixSort::SortKeys(s->d_build_tmp, tmp, s->d_build[0], s->d_build[1], (int)total, 0, end_bit, s->st));
-    tmp = s->build_tmp_bytes;
-    GN_HIP(hipcub::DeviceSelect::Unique(s->d_build_tmp, tmp, s->d_build[1], s->d_build[0], s->d_build_ctr + 1, (int)total, s->st));
+    GN_HIP(hipcub::DeviceRadixSort::SortKeys(s->build.d_tmp, tmp, s->build.d_build[0].get(), s->build.d_build[1].get(), (int)total, 0, end_bit, s->st));
+    tmp = s->build.tmp_bytes;
+    GN_HIP(hipcub::DeviceSelect::Unique(s->build.d_tmp, tmp, s->build.d_build[1].get(), s->build.d_build[0].get(), s->build.d_ctr + 1, (int)total, s->st));
     unsigned long long nd = 0;
-    GN_HIP(hipMemcpyAsync(&nd, s->d_build_ctr + 1, 8, hipMemcpyDeviceToHost, s->st));
+    GN_HIP(hipMemcpyAsync(&nd, s->build.d_ctr + 1, 8, hipMemcpyDeviceToHost, s->st));
     GN_HIP(hipStreamSynchronize(s->st));
     *n_distinct       = nd;
     s->build_distinct = nd;
@@ -135,7 +114,7 @@ extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t c
         return GN_OK;
     if (cap < nd)
         return gn_fail(GN_EOVERFLOW, "hash buffer too small: need %llu", nd);
-    GN_HIP(hipMemcpy(out, s->d_build[0], nd * 8, hipMemcpyDeviceToHost));
+    GN_HIP(hipMemcpy(out, s->build.d_build[0], nd * 8, hipMemcpyDeviceToHost));
     return GN_OK;
 }
 
@@ -170,15 +149,7 @@ extern "C" int gn_filter_emplace_split(gn_filter* f, const uint64_t* hashes, uin
     // staged through a device buffer that stays with the filter (grown to the largest request so far), at most 32 M hashes
     // at a time
     const uint64_t step = n < (32ull << 20) ? n : (32ull << 20);
-    if (f->emplace_stage_cap < step)
-    {
-        if (f->d_emplace_stage)
-            hipFree(f->d_emplace_stage);
-        f->d_emplace_stage   = nullptr;
-        f->emplace_stage_cap = 0;
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_emplace_stage), step * 8));
-        f->emplace_stage_cap = step;
-    }
+    GN_HIP(f->d_emplace_stage.reserve(step, step));
     for (uint64_t done = 0; done < n; done += step)
     {
         const uint64_t c = n - done < step ? n - done : step;
@@ -246,45 +217,25 @@ extern "C" int gn_filter_probe(gn_filter* f, const uint64_t* hashes, uint64_t n,
     if (!f->load_st)
         GN_HIP(hipStreamCreateWithFlags(&f->load_st, hipStreamNonBlocking));
     const uint64_t step = n < (32ull << 20) ? n : (32ull << 20);
-    if (f->emplace_stage_cap < step)
-    {
-        if (f->d_emplace_stage)
-            hipFree(f->d_emplace_stage);
-        f->d_emplace_stage   = nullptr;
-        f->emplace_stage_cap = 0;
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_emplace_stage), step * 8));
-        f->emplace_stage_cap = step;
-    }
-    uint32_t*           d_bins = nullptr;
-    unsigned long long* d_out  = nullptr;
-    unsigned long long  init[3] = { 0, 0, ~0ull };
-    hipError_t          e = hipMalloc(reinterpret_cast<void**>(&d_bins), (size_t)(n_bins ? n_bins : 1) * 4);
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(init));
-    if (e == hipSuccess && n_bins)
-        e = hipMemcpyAsync(d_bins, bins, (size_t)n_bins * 4, hipMemcpyHostToDevice, f->load_st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, f->load_st);
-    for (uint64_t done = 0; done < n && e == hipSuccess; done += step)
+    GN_HIP(f->d_emplace_stage.reserve(step, step));
+    GnDev<uint32_t>           d_bins;
+    GnDev<unsigned long long> d_out;
+    unsigned long long        init[3] = { 0, 0, ~0ull };
+    GN_HIP(d_bins.alloc(n_bins));
+    GN_HIP(d_out.alloc(3));
+    if (n_bins)
+        GN_HIP(hipMemcpyAsync(d_bins, bins, (size_t)n_bins * 4, hipMemcpyHostToDevice, f->load_st));
+    GN_HIP(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, f->load_st));
+    for (uint64_t done = 0; done < n; done += step)
     {
         const uint64_t c = n - done < step ? n - done : step;
-        e = hipMemcpyAsync(f->d_emplace_stage, hashes + done, c * 8, hipMemcpyHostToDevice, f->load_st);
-        if (e != hipSuccess)
-            break;
+        GN_HIP(hipMemcpyAsync(f->d_emplace_stage, hashes + done, c * 8, hipMemcpyHostToDevice, f->load_st));
         hipLaunchKernelGGL(gn_probe_kernel, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, f->load_st, ib.d_rows, ib.S, (uint32_t)ib.Ws, ib.shift,
                            ib.h, f->d_emplace_stage, c, d_bins, n_bins, done, d_out);
-        e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(f->load_st); // (the staging buffer is reused, and `hashes` may be pageable)
+        GN_HIP(hipGetLastError());
+        GN_HIP(hipStreamSynchronize(f->load_st)); // (the staging buffer is reused, and `hashes` may be pageable)
     }
-    if (e == hipSuccess)
-        e = hipMemcpy(init, d_out, sizeof(init), hipMemcpyDeviceToHost);
-    if (d_bins)
-        (void)hipFree(d_bins);
-    if (d_out)
-        (void)hipFree(d_out);
-    if (e != hipSuccess)
-        return gn_fail(GN_ENODEV, "gn_filter_probe: %s", hipGetErrorString(e));
+    GN_HIP(hipMemcpy(init, d_out, sizeof(init), hipMemcpyDeviceToHost));
     *hits          = init[0];
     *missing       = init[1];
     *first_missing = init[2];

@@ -34,63 +34,49 @@ extern "C" int gn_hashes_union(int device, const uint64_t* const* sets, const ui
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
         return gn_fail(GN_ENODEV, "gn_hashes_union: no HIP device %d", device);
     GN_HIP(hipSetDevice(device));
-    uint64_t *          d_a = nullptr, *d_b = nullptr;
-    unsigned long long* d_n = nullptr;
-    void*               d_tmp = nullptr;
-    hipError_t          e   = hipMalloc(reinterpret_cast<void**>(&d_a), total * 8);
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&d_b), total * 8);
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&d_n), sizeof(unsigned long long));
+    GnDev<uint64_t>           d_a, d_b;
+    GnDev<unsigned long long> d_n;
+    GnDev<uint8_t>            d_tmp;
+    GN_HIP(d_a.alloc(total));
+    GN_HIP(d_b.alloc(total));
+    GN_HIP(d_n.alloc(1));
     size_t ta = 0, tb = 0;
-    if (e == hipSuccess)
-        e = hipcub::DeviceRadixSort::SortKeys(nullptr, ta, d_a, d_b, (int)total, 0, 64, nullptr);
-    if (e == hipSuccess)
-        e = hipcub::DeviceSelect::Unique(nullptr, tb, d_b, d_a, d_n, (int)total, nullptr);
+    GN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, ta, d_a.get(), d_b.get(), (int)total, 0, 64, nullptr));
+    GN_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_b.get(), d_a.get(), d_n.get(), (int)total, nullptr));
     const size_t tmp_bytes = ta > tb ? ta : tb;
-    if (e == hipSuccess)
-        e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1);
+    GN_HIP(d_tmp.alloc(tmp_bytes));
     uint64_t at = 0, top = 0;
-    for (uint32_t i = 0; i < n_sets && e == hipSuccess; ++i)
+    for (uint32_t i = 0; i < n_sets; ++i)
     {
         if (sizes[i] == 0)
             continue;
-        e = hipMemcpy(d_a + at, sets[i], sizes[i] * 8, hipMemcpyHostToDevice);
+        GN_HIP(hipMemcpy(d_a + at, sets[i], sizes[i] * 8, hipMemcpyHostToDevice));
         at += sizes[i];
         top = std::max(top, sets[i][sizes[i] - 1]); // ascending sets: the last value is the largest
     }
     int end_bit = 1;
     while (end_bit < 64 && (top >> end_bit))
         ++end_bit;
-    unsigned long long nu = 0;
-    if (n_sets == 1 && e == hipSuccess) // one ascending set is its own union
-        nu = total;
-    else
+    unsigned long long nu = total; // one ascending set is its own union
+    if (n_sets != 1)
     {
         size_t t = tmp_bytes;
-        if (e == hipSuccess)
-            e = hipcub::DeviceRadixSort::SortKeys(d_tmp, t, d_a, d_b, (int)total, 0, end_bit, nullptr);
+        GN_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.get(), t, d_a.get(), d_b.get(), (int)total, 0, end_bit, nullptr));
         t = tmp_bytes;
-        if (e == hipSuccess)
-            e = hipcub::DeviceSelect::Unique(d_tmp, t, d_b, d_a, d_n, (int)total, nullptr);
-        if (e == hipSuccess)
-            e = hipMemcpy(&nu, d_n, sizeof(nu), hipMemcpyDeviceToHost);
+        GN_HIP(hipcub::DeviceSelect::Unique(d_tmp.get(), t, d_b.get(), d_a.get(), d_n.get(), (int)total, nullptr));
+        GN_HIP(hipMemcpy(&nu, d_n, sizeof(nu), hipMemcpyDeviceToHost));
     }
-    int rc = GN_OK;
-    if (e == hipSuccess && out)
+    if (out)
     {
         if (cap < nu)
-            rc = gn_fail(GN_EOVERFLOW, "gn_hashes_union: hash buffer too small: need %llu", nu);
-        else
-            e = hipMemcpy(out, d_a, nu * 8, hipMemcpyDeviceToHost);
+        {
+            *n_union = nu; // (the caller sizes its buffer from it)
+            return gn_fail(GN_EOVERFLOW, "gn_hashes_union: hash buffer too small: need %llu", nu);
+        }
+        GN_HIP(hipMemcpy(out, d_a, nu * 8, hipMemcpyDeviceToHost));
     }
-    for (void* p : { (void*)d_a, (void*)d_b, (void*)d_n, d_tmp })
-        if (p)
-            (void)hipFree(p);
-    if (e != hipSuccess)
-        return gn_fail(e == hipErrorOutOfMemory ? GN_ENOMEM : GN_ENODEV, "gn_hashes_union: %s", hipGetErrorString(e));
     *n_union = nu;
-    return rc;
+    return GN_OK;
 }
 
 // ---- gn_filter_emplace_path ---------------------------------------------------------------------------------------------------
@@ -206,26 +192,16 @@ extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, cons
         GN_HIP(hipStreamCreateWithFlags(&f->load_st, hipStreamNonBlocking));
     // staged through the device buffer that stays with the filter, at most 32 M hashes at a time (as gn_filter_emplace_split)
     const uint64_t step = total < (32ull << 20) ? total : (32ull << 20);
-    if (f->emplace_stage_cap < step)
-    {
-        if (f->d_emplace_stage)
-            (void)hipFree(f->d_emplace_stage);
-        f->d_emplace_stage   = nullptr;
-        f->emplace_stage_cap = 0;
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_emplace_stage), step * 8));
-        f->emplace_stage_cap = step;
-    }
-    const uint64_t max_items = step / GN_PATH_CHUNK + n_sets + 2;
-    GnPathDev*     d_paths   = nullptr;
-    GnPathItem*    d_items   = nullptr;
-    hipError_t     e         = hipMalloc(reinterpret_cast<void**>(&d_paths), dev.size() * sizeof(GnPathDev));
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&d_items), max_items * sizeof(GnPathItem));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_paths, dev.data(), dev.size() * sizeof(GnPathDev), hipMemcpyHostToDevice, f->load_st);
-    std::vector<GnPathItem> items;
-    uint32_t                seg = 0;
-    for (uint64_t done = 0; done < total && e == hipSuccess; done += step)
+    GN_HIP(f->d_emplace_stage.reserve(step, step));
+    const uint64_t          max_items = step / GN_PATH_CHUNK + n_sets + 2;
+    std::vector<GnPathItem> items; // (before the buffers it is copied into: they are freed, which waits for the device, first)
+    GnDev<GnPathDev>        d_paths;
+    GnDev<GnPathItem>       d_items;
+    GN_HIP(d_paths.alloc(dev.size()));
+    GN_HIP(d_items.alloc(max_items));
+    GN_HIP(hipMemcpyAsync(d_paths, dev.data(), dev.size() * sizeof(GnPathDev), hipMemcpyHostToDevice, f->load_st));
+    uint32_t seg = 0;
+    for (uint64_t done = 0; done < total; done += step)
     {
         const uint64_t c = total - done < step ? total - done : step;
         items.clear();
@@ -237,28 +213,15 @@ extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, cons
             for (uint64_t a = lo; a < hi; a += GN_PATH_CHUNK)
                 items.push_back(GnPathItem{ s, (uint32_t)std::min<uint64_t>(GN_PATH_CHUNK, hi - a), a - set_off[s], a - done });
         }
-        if (items.size() > max_items)
-        {
-            e = hipErrorInvalidValue; // (cannot happen: a round holds at most step / chunk full items and one short one per set)
-            break;
-        }
-        e = hipMemcpyAsync(f->d_emplace_stage, hashes + done, c * 8, hipMemcpyHostToDevice, f->load_st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GnPathItem), hipMemcpyHostToDevice, f->load_st);
-        if (e != hipSuccess)
-            break;
+        if (items.size() > max_items) // (cannot happen: a round holds at most step / chunk full items and one short one per set)
+            GN_HIP(hipErrorInvalidValue);
+        GN_HIP(hipMemcpyAsync(f->d_emplace_stage, hashes + done, c * 8, hipMemcpyHostToDevice, f->load_st));
+        GN_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GnPathItem), hipMemcpyHostToDevice, f->load_st));
         const uint32_t n_items = (uint32_t)items.size();
         hipLaunchKernelGGL(gn_emplace_path_kernel, dim3((n_items + 3) / 4), dim3(256), 0, f->load_st, f->d_emplace_stage, d_items, n_items,
                            d_paths, depth, f->ibfs[0].h);
-        e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(f->load_st); // (the staging buffer and `items` are reused, and `hashes` may be pageable)
+        GN_HIP(hipGetLastError());
+        GN_HIP(hipStreamSynchronize(f->load_st)); // (the staging buffer and `items` are reused, and `hashes` may be pageable)
     }
-    if (d_paths)
-        (void)hipFree(d_paths);
-    if (d_items)
-        (void)hipFree(d_items);
-    if (e != hipSuccess)
-        return gn_fail(e == hipErrorOutOfMemory ? GN_ENOMEM : GN_ENODEV, "gn_filter_emplace_path: %s", hipGetErrorString(e));
     return GN_OK;
 }

@@ -211,8 +211,8 @@ static int gn_upload_ibf_rows(const gn_ibf_desc* d, GnIbfHost* out, uint64_t* by
         return gn_fail(GN_ERANGE, "too many bins");
     const uint64_t Ws    = pad_rows ? gn_pad_row_words(d->bin_words) : d->bin_words;
     const uint64_t bytes = d->bin_size * Ws * 8ull;
-    uint64_t*      dp    = nullptr;
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&dp), bytes + 64)); // +64: tail pad for 16-byte loads
+    GnDev<uint64_t> dp;
+    GN_HIP(dp.alloc(bytes / 8 + 8)); // +64 bytes: tail pad for 16-byte loads
     if (d->rows && Ws != d->bin_words)
     {
         // padded rows: zero everything, then the source's words row by row (in rounds of <= 1 GiB of source)
@@ -224,10 +224,7 @@ static int gn_upload_ibf_rows(const gn_ibf_desc* d, GnIbfHost* out, uint64_t* by
             const uint64_t nr = std::min(per, d->bin_size - r);
             hipError_t     e  = hipMemcpy2D(dp + r * Ws, Ws * 8, d->rows + r * d->bin_words, d->bin_words * 8, d->bin_words * 8, nr, hipMemcpyHostToDevice);
             if (e != hipSuccess)
-            {
-                hipFree(dp);
                 return gn_fail(GN_ENODEV, "filter upload failed: %s", hipGetErrorString(e));
-            }
         }
     }
     else if (d->rows)
@@ -237,29 +234,26 @@ static int gn_upload_ibf_rows(const gn_ibf_desc* d, GnIbfHost* out, uint64_t* by
         for (uint64_t o = 0; o < bytes; o += chunk)
         {
             const uint64_t nb = std::min(chunk, bytes - o);
-            hipError_t     e  = hipMemcpy(reinterpret_cast<uint8_t*>(dp) + o, reinterpret_cast<const uint8_t*>(d->rows) + o,
+            hipError_t     e  = hipMemcpy(reinterpret_cast<uint8_t*>(dp.get()) + o, reinterpret_cast<const uint8_t*>(d->rows) + o,
                                           nb, hipMemcpyHostToDevice);
             if (e != hipSuccess)
-            {
-                hipFree(dp);
                 return gn_fail(GN_ENODEV, "filter upload failed: %s", hipGetErrorString(e));
-            }
         }
-        GN_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(dp) + bytes, 0, 64, nullptr));
+        GN_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(dp.get()) + bytes, 0, 64, nullptr));
     }
     else
     {
         GN_HIP(hipMemsetAsync(dp, 0, bytes + 64, nullptr));
     }
     if (d->rows && (d->bins & 63))
-        hipLaunchKernelGGL(gn_clear_padding_kernel, dim3((unsigned)((d->bin_size + 255) / 256)), dim3(256), 0, nullptr, dp,
+        hipLaunchKernelGGL(gn_clear_padding_kernel, dim3((unsigned)((d->bin_size + 255) / 256)), dim3(256), 0, nullptr, dp.get(),
                            d->bin_size, d->bin_words, Ws, (1ull << (d->bins & 63)) - 1ull);
     // A memset of device memory returns before the fill has run, and everything that touches the filter afterwards --
     // gn_filter_write_rows' load stream, every gn_stream -- runs on streams created hipStreamNonBlocking, which take no
     // implicit order against the null stream the fill is queued on.  Without this wait the zero fill of a streamed filter
     // could land AFTER the first row chunks (round 3's intermittent "0 of 7 minimisers found": DESIGN 7-5b).
     GN_HIP(hipDeviceSynchronize());
-    out->d_rows = dp;
+    out->d_rows = std::move(dp);
     out->S      = d->bin_size;
     out->W      = d->bin_words;
     out->Ws     = Ws;
@@ -362,29 +356,30 @@ extern "C" int gn_filter_upload_ibf(int device, const gn_ibf_desc* ibf, const ui
         std::vector<uint32_t> lds_idx(bins.size());
         for (size_t x = 0; x < bins.size(); ++x)
             lds_idx[x] = gn_count_lds_index(geom, bins[x]);
-        hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&f->d_tgt_off), off.size() * 4);
-        hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&f->d_tgt_bins), bins.size() * 4);
-        hipError_t e3 = hipMalloc(reinterpret_cast<void**>(&f->d_tgt_lds), bins.size() * 4);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
-        {
+        // (every table: allocated and copied, the first failure of either kept)
+        hipError_t e  = hipSuccess;
+        auto       up = [&](GnDev<uint32_t>& d, const std::vector<uint32_t>& v) {
+            if (e == hipSuccess)
+                e = d.upload(v.data(), v.size());
+        };
+        auto failed = [&]() {
             gn_filter_free(f);
-            return gn_fail(GN_ENOMEM, "target map allocation failed");
-        }
-        hipMemcpy(f->d_tgt_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
-        hipMemcpy(f->d_tgt_bins, bins.data(), bins.size() * 4, hipMemcpyHostToDevice);
-        hipMemcpy(f->d_tgt_lds, lds_idx.data(), lds_idx.size() * 4, hipMemcpyHostToDevice);
+            return e == hipErrorOutOfMemory ? gn_fail(GN_ENOMEM, "target map allocation failed")
+                                            : gn_fail(GN_ENODEV, "target map upload failed: %s", hipGetErrorString(e));
+        };
+        up(f->d_tgt_off, off);
+        up(f->d_tgt_bins, bins);
+        up(f->d_tgt_lds, lds_idx);
+        if (e != hipSuccess)
+            return failed();
         std::vector<uint4> rec(n_targets ? n_targets : 1);
         for (uint32_t t = 0; t < n_targets; ++t)
         {
             const uint32_t len = off[t + 1] - off[t];
             rec[t] = make_uint4(off[t], len, len >= 1 ? lds_idx[off[t]] : 0u, len >= 2 ? lds_idx[off[t] + 1] : 0u);
         }
-        if (hipMalloc(reinterpret_cast<void**>(&f->d_tgt_rec), rec.size() * sizeof(uint4)) != hipSuccess)
-        {
-            gn_filter_free(f);
-            return gn_fail(GN_ENOMEM, "target map allocation failed");
-        }
-        hipMemcpy(f->d_tgt_rec, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice);
+        if ((e = f->d_tgt_rec.upload(rec.data(), rec.size())) != hipSuccess)
+            return failed();
         // candidate-driven select of the generic kernel: bin -> target, and bins-per-target of every bin (one byte;
         // 0 for bins of no target and of targets with more than GN_CAND_NBIG bins, which go to big_list); the bytes
         // of count dwords 2j and 2j+1 (gn_count_lds_index: u16 pairs at dword q*(Gp+1)+gl) share dword
@@ -415,16 +410,11 @@ extern "C" int gn_filter_upload_ibf(int device, const gn_ibf_desc* ibf, const ui
             f->n_big = (uint32_t)big.size();
             if (big.empty())
                 big.push_back(0);
-            if (hipMalloc(reinterpret_cast<void**>(&f->d_bin_tgt), bin_tgt.size() * 4) != hipSuccess
-                || hipMalloc(reinterpret_cast<void**>(&f->d_bin_nb2), nb2.size() * 4) != hipSuccess
-                || hipMalloc(reinterpret_cast<void**>(&f->d_big_list), big.size() * 4) != hipSuccess)
-            {
-                gn_filter_free(f);
-                return gn_fail(GN_ENOMEM, "target map allocation failed");
-            }
-            hipMemcpy(f->d_bin_tgt, bin_tgt.data(), bin_tgt.size() * 4, hipMemcpyHostToDevice);
-            hipMemcpy(f->d_bin_nb2, nb2.data(), nb2.size() * 4, hipMemcpyHostToDevice);
-            hipMemcpy(f->d_big_list, big.data(), big.size() * 4, hipMemcpyHostToDevice);
+            up(f->d_bin_tgt, bin_tgt);
+            up(f->d_bin_nb2, nb2);
+            up(f->d_big_list, big);
+            if (e != hipSuccess)
+                return failed();
             // split kernel (register counters + byte image): the same bytes in the layout of the byte counters --
             // register r = (d*4+j)*2+pp of lane l at [(slice*8*nd + r)*64 + l], byte y <-> bit 8y + 4pp + j of dword d
             const size_t split_lds = gn_split_lds_bytes(geom, ibf->hash_funs);
@@ -445,12 +435,9 @@ extern "C" int gn_filter_upload_ibf(int device, const gn_ibf_desc* ibf, const ui
                     const uint32_t r  = (d * 4u + (bit & 3u)) * 2u + ((bit >> 2) & 1u);
                     nbr[((size_t)sl * 8u * nd + r) * 64u + lane] |= len << (8u * (bit >> 3));
                 }
-                if (hipMalloc(reinterpret_cast<void**>(&f->d_sl_nbr), nbr.size() * 4) != hipSuccess)
-                {
-                    gn_filter_free(f);
-                    return gn_fail(GN_ENOMEM, "target map allocation failed");
-                }
-                hipMemcpy(f->d_sl_nbr, nbr.data(), nbr.size() * 4, hipMemcpyHostToDevice);
+                up(f->d_sl_nbr, nbr);
+                if (e != hipSuccess)
+                    return failed();
                 f->split_bpc = (uint32_t)((160u * 1024u) / split_lds);
             }
         }
@@ -504,33 +491,6 @@ extern "C" int gn_filter_free(gn_filter* f)
     if (!f)
         return GN_OK;
     hipSetDevice(f->device);
-    if (f->ibf.d_rows)
-        hipFree(f->ibf.d_rows);
-    if (f->d_tgt_off)
-        hipFree(f->d_tgt_off);
-    if (f->d_tgt_bins)
-        hipFree(f->d_tgt_bins);
-    if (f->d_tgt_lds)
-        hipFree(f->d_tgt_lds);
-    if (f->d_tgt_rec)
-        hipFree(f->d_tgt_rec);
-    if (f->d_bin_tgt)
-        hipFree(f->d_bin_tgt);
-    if (f->d_bin_nb2)
-        hipFree(f->d_bin_nb2);
-    if (f->d_big_list)
-        hipFree(f->d_big_list);
-    if (f->d_sl_nbr)
-        hipFree(f->d_sl_nbr);
-    for (auto& i : f->ibfs)
-        if (i.d_rows)
-            hipFree(i.d_rows);
-    for (void* p : f->hibf_allocs)
-        hipFree(p);
-    if (f->d_hibf)
-        hipFree(f->d_hibf);
-    if (f->d_emplace_stage)
-        hipFree(f->d_emplace_stage);
     if (f->load_st)
         hipStreamDestroy(f->load_st);
     delete f;
@@ -590,21 +550,12 @@ extern "C" int gn_filter_emplace_ibf(gn_filter* f, uint32_t ibf_idx, const uint6
         if (bins[i] >= ib->B)
             return gn_fail(GN_EINVAL, "bin %u out of range", bins[i]);
     GN_HIP(hipSetDevice(f->device));
-    uint64_t* dh = nullptr;
-    uint32_t* db = nullptr;
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&dh), n * 8));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&db), n * 4);
-    if (e != hipSuccess)
-    {
-        hipFree(dh);
-        return gn_fail(GN_ENOMEM, "emplace staging allocation failed");
-    }
-    hipMemcpy(dh, hashes, n * 8, hipMemcpyHostToDevice);
-    hipMemcpy(db, bins, n * 4, hipMemcpyHostToDevice);
-    e = gn_launch_emplace(ib->d_rows, ib->S, (uint32_t)ib->Ws, ib->shift, ib->h, dh, db, n, nullptr); // (the kernel's W is the row stride)
+    GnDev<uint64_t> dh;
+    GnDev<uint32_t> db;
+    GN_HIP(dh.upload(hashes, n));
+    GN_HIP(db.upload(bins, n));
+    hipError_t e  = gn_launch_emplace(ib->d_rows, ib->S, (uint32_t)ib->Ws, ib->shift, ib->h, dh, db, n, nullptr); // (the kernel's W is the row stride)
     hipError_t e2 = hipDeviceSynchronize();
-    hipFree(dh);
-    hipFree(db);
     if (e != hipSuccess || e2 != hipSuccess)
         return gn_fail(GN_ENODEV, "emplace kernel failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return GN_OK;
@@ -667,27 +618,16 @@ extern "C" int gn_filter_download_row_list(const gn_filter* f, uint32_t ibf_idx,
     GN_HIP(hipSetDevice(f->device));
     const uint64_t per = std::max<uint64_t>(1, (256ull << 20) / (ib->W * 8)); // rows per 256 MiB staging round
     const uint64_t cap = std::min(per, n);
-    uint64_t *     d_idx = nullptr, *d_out = nullptr;
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), cap * 8));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), cap * ib->W * 8);
-    if (e != hipSuccess)
-    {
-        hipFree(d_idx);
-        return gn_fail(GN_ENOMEM, "row gather staging allocation failed");
-    }
-    for (uint64_t o = 0; o < n && e == hipSuccess; o += cap)
+    GnDev<uint64_t> d_idx, d_out;
+    GN_HIP(d_idx.alloc(cap));
+    GN_HIP(d_out.alloc(cap * ib->W));
+    for (uint64_t o = 0; o < n; o += cap)
     {
         const uint64_t m = std::min(cap, n - o);
-        e                = hipMemcpy(d_idx, row_idx + o, m * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            break;
+        GN_HIP(hipMemcpy(d_idx, row_idx + o, m * 8, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(gn_gather_rows_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, ib->d_rows, ib->W, ib->Ws, d_idx, d_out);
-        e = hipMemcpy(out + o * ib->W, d_out, m * ib->W * 8, hipMemcpyDeviceToHost);
+        GN_HIP(hipMemcpy(out + o * ib->W, d_out, m * ib->W * 8, hipMemcpyDeviceToHost));
     }
-    hipFree(d_idx);
-    hipFree(d_out);
-    if (e != hipSuccess)
-        return gn_fail(GN_ENODEV, "row gather failed: %s", hipGetErrorString(e));
     return GN_OK;
 }
 
@@ -698,13 +638,13 @@ extern "C" int gn_filter_download_row_list(const gn_filter* f, uint32_t ibf_idx,
 // sets), so this is most of its start-up.  Falls back to hipHostMalloc where the mapping or the registration is refused.
 namespace
 {
-struct GnPinned
+struct GnPinnedBlock
 {
     void*  raw;
     size_t raw_bytes;
 };
 std::mutex                           g_pinned_mutex;
-std::unordered_map<void*, GnPinned> g_pinned; // blocks that came from mmap + hipHostRegister
+std::unordered_map<void*, GnPinnedBlock> g_pinned; // blocks that came from mmap + hipHostRegister
 } // namespace
 
 extern "C" int gn_pinned_alloc(size_t bytes, void** out)
@@ -729,7 +669,7 @@ extern "C" int gn_pinned_alloc(size_t bytes, void** out)
             if (hipHostRegister(p, len, hipHostRegisterPortable) == hipSuccess)
             {
                 std::lock_guard<std::mutex> lk(g_pinned_mutex);
-                g_pinned[p] = GnPinned{ raw, len + huge };
+                g_pinned[p] = GnPinnedBlock{ raw, len + huge };
                 *out        = p;
                 return GN_OK;
             }
@@ -747,7 +687,7 @@ extern "C" int gn_pinned_free(void* p)
 {
     if (!p)
         return GN_OK;
-    GnPinned blk{ nullptr, 0 };
+    GnPinnedBlock blk{ nullptr, 0 };
     {
         std::lock_guard<std::mutex> lk(g_pinned_mutex);
         auto                        it = g_pinned.find(p);
@@ -905,12 +845,6 @@ extern "C" int gn_filter_fill_random(gn_filter* f, uint32_t ibf_idx, uint64_t se
 // ------------------------------------------------------------------------------------------------
 // streams
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static hipError_t gn_dmalloc(T** p, size_t n)
-{
-    return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
-}
-
 extern "C" int gn_stream_destroy(gn_stream* s)
 {
     if (!s)
@@ -918,23 +852,9 @@ extern "C" int gn_stream_destroy(gn_stream* s)
     hipSetDevice(s->device); // (not s->f->device: a caller may have freed the filter first)
     if (s->st)
         hipStreamSynchronize(s->st);
-    void* ptrs[] = { s->d_bases,  s->d_off1,    s->d_off2,      s->d_slot_cnt,  s->d_slot_off, s->d_hashes, s->d_nh,
-                     s->d_status, s->d_matches, s->d_sorted,    s->d_ctr,       s->d_seg_begin, s->d_seg_count,
-                     s->d_seg_off, s->d_deferred, s->d_mdeferred, s->d_scan_tmp, s->d_work[0], s->d_work[1], s->d_hdefer, s->d_hdefer2, s->d_hctr, s->d_hsub, s->d_keys[0], s->d_keys[1], s->d_vals[0],
-                     s->d_vals[1], s->d_sort_tmp };
-    for (void* p : ptrs)
-        if (p)
-            hipFree(p);
-    gn_postfilter_release(s);
-    gn_build_release(s);
-    gn_fastq_release(s);
-    for (void* q : { (void*)s->d_long_list, (void*)s->d_long_count, (void*)s->d_long_scratch })
-        if (q)
-            hipFree(q);
-    if (s->h_ctr)
-        hipHostFree(s->h_ctr);
-    if (s->h_hctr)
-        hipHostFree(s->h_hctr);
+    if (s->fq_probe[3] > 0)
+        fprintf(stderr, "[hip call timing] gn_stream_upload_text x%.0f: initial sync %.3f ms, copy call %.3f ms, other calls %.3f ms per batch\n", s->fq_probe[3],
+                s->fq_probe[0] / s->fq_probe[3] * 1e3, s->fq_probe[1] / s->fq_probe[3] * 1e3, s->fq_probe[2] / s->fq_probe[3] * 1e3);
     for (auto& e : s->ev)
         if (e)
             hipEventDestroy(e);
@@ -1001,39 +921,39 @@ extern "C" int gn_stream_create(gn_filter* f, uint32_t max_reads, uint64_t max_b
     ok(hipEventCreate(&s->ev_count0));
     for (auto& ev : s->ev_chunk)
         ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    ok(gn_dmalloc(&s->d_bases, max_bases + 64));
-    ok(gn_dmalloc(&s->d_off1, (size_t)max_reads + 1));
-    ok(gn_dmalloc(&s->d_off2, (size_t)max_reads + 1));
-    ok(gn_dmalloc(&s->d_slot_cnt, (size_t)max_reads + 1));
-    ok(gn_dmalloc(&s->d_slot_off, (size_t)max_reads + 1));
-    ok(gn_dmalloc(&s->d_hashes, max_bases)); // #windows <= #bases
-    ok(gn_dmalloc(&s->d_nh, max_reads));
-    ok(gn_dmalloc(&s->d_status, (size_t)max_reads + 8)); // (+8: the HIBF level-0 kernel reads status bytes as aligned dwords)
-    ok(gn_dmalloc(&s->d_matches, s->match_cap));
-    ok(gn_dmalloc(&s->d_sorted, s->match_cap));
-    ok(gn_dmalloc(&s->d_ctr, GN_NCTR));
-    ok(gn_dmalloc(&s->d_seg_begin, nseg));
-    ok(gn_dmalloc(&s->d_seg_count, nseg + 1));
-    ok(gn_dmalloc(&s->d_seg_off, nseg + 1));
-    ok(gn_dmalloc(&s->d_deferred, max_reads));
-    ok(gn_dmalloc(&s->d_mdeferred, max_reads));
+    ok(s->d_bases.alloc(max_bases + 64));
+    ok(s->d_off1.alloc((size_t)max_reads + 1));
+    ok(s->d_off2.alloc((size_t)max_reads + 1));
+    ok(s->d_slot_cnt.alloc((size_t)max_reads + 1));
+    ok(s->d_slot_off.alloc((size_t)max_reads + 1));
+    ok(s->d_hashes.alloc(max_bases)); // #windows <= #bases
+    ok(s->d_nh.alloc(max_reads));
+    ok(s->d_status.alloc((size_t)max_reads + 8)); // (+8: the HIBF level-0 kernel reads status bytes as aligned dwords)
+    ok(s->d_matches.alloc(s->match_cap));
+    ok(s->d_sorted.alloc(s->match_cap));
+    ok(s->d_ctr.alloc(GN_NCTR));
+    ok(s->d_seg_begin.alloc(nseg));
+    ok(s->d_seg_count.alloc(nseg + 1));
+    ok(s->d_seg_off.alloc(nseg + 1));
+    ok(s->d_deferred.alloc(max_reads));
+    ok(s->d_mdeferred.alloc(max_reads));
     size_t tmp1 = 0, tmp2 = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, s->d_slot_cnt, s->d_slot_off, (int)(max_reads + 1), s->st);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, s->d_slot_cnt.get(), s->d_slot_off.get(), (int)(max_reads + 1), s->st);
     gn_scan_counts(nullptr, tmp2, s->d_seg_count, s->d_seg_off, (int)(nseg + 1), s->st);
     s->scan_tmp_bytes = std::max(tmp1, tmp2) + 256;
-    ok(hipMalloc(&s->d_scan_tmp, s->scan_tmp_bytes));
+    ok(s->d_scan_tmp.alloc(s->scan_tmp_bytes));
     if (f->is_hibf)
     {
         s->work_cap = max_reads * 4u > 1024u ? max_reads * 4u : 1024u;
-        ok(gn_dmalloc(&s->d_work[0], s->work_cap));
-        ok(gn_dmalloc(&s->d_work[1], s->work_cap));
-        ok(gn_dmalloc(&s->d_hdefer, s->work_cap));
-        ok(gn_dmalloc(&s->d_hdefer2, s->work_cap));
-        ok(gn_dmalloc(&s->d_hctr, 37 * (GN_HIBF_MAXDEPTH + 1) + 2));
-        ok(gn_dmalloc(&s->d_hsub, 384 * (GN_HIBF_MAXDEPTH + 1))); // per level: counts, bases, cursors of the 128 (class, n-bin) keys
-        ok(hipHostMalloc(reinterpret_cast<void**>(&s->h_hctr), (5 * (GN_HIBF_MAXDEPTH + 1) + 2) * sizeof(unsigned long long), hipHostMallocDefault));
+        ok(s->d_work[0].alloc(s->work_cap));
+        ok(s->d_work[1].alloc(s->work_cap));
+        ok(s->d_hdefer.alloc(s->work_cap));
+        ok(s->d_hdefer2.alloc(s->work_cap));
+        ok(s->d_hctr.alloc(37 * (GN_HIBF_MAXDEPTH + 1) + 2));
+        ok(s->d_hsub.alloc(384 * (GN_HIBF_MAXDEPTH + 1))); // per level: counts, bases, cursors of the 128 (class, n-bin) keys
+        ok(s->h_hctr.alloc(5 * (GN_HIBF_MAXDEPTH + 1) + 2));
     }
-    ok(hipHostMalloc(reinterpret_cast<void**>(&s->h_ctr), GN_NCTR * sizeof(unsigned long long), hipHostMallocDefault));
+    ok(s->h_ctr.alloc(GN_NCTR));
     if (e != hipSuccess)
     {
         gn_stream_destroy(s);
@@ -1346,19 +1266,19 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     const bool fast = f->identity;
     // with a filter_matches pre-pass on the stream the fast and the split-bin kernel do not write matches the --rel-filter rule is bound to
     // drop (not for a merging level: there the minimum follows the entries that got in, which only the merge knows)
-    const bool predrop = (fast || split) && s->pf_on && !s->pf_merge && s->d_pf_segmin && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
-                         (uint64_t)hi * f->geom.wpr <= s->pf_segmin_cap && !gn_sw().predrop;
+    const bool predrop = (fast || split) && s->pf_on && !s->pf_merge && s->pf.d_segmin && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
+                         (uint64_t)hi * f->geom.wpr <= s->pf.segmin_cap && !gn_sw().predrop;
     if (lo == 0)
         s->pf_predrop = predrop;
     if (predrop)
     {
         if (lo == 0)
-            GN_HIP(hipMemsetAsync(s->d_pf_pre, 0, sizeof(unsigned long long), s->st));
-        GN_HIP(hipMemsetAsync(s->d_pf_segmin + (size_t)lo * f->geom.wpr, 0xFF, (size_t)(hi - lo) * f->geom.wpr * 4, s->st));
+            GN_HIP(hipMemsetAsync(s->pf.d_pre, 0, sizeof(unsigned long long), s->st));
+        GN_HIP(hipMemsetAsync(s->pf.d_segmin + (size_t)lo * f->geom.wpr, 0xFF, (size_t)(hi - lo) * f->geom.wpr * 4, s->st));
         p.pre_mode = s->pf_joint ? 2u : 1u;
         p.pre_rel  = s->pf_rel_filter;
-        p.seg_min  = s->d_pf_segmin;
-        p.pre_ctr  = s->d_pf_pre;
+        p.seg_min  = s->pf.d_segmin;
+        p.pre_ctr  = s->pf.d_pre;
     }
     if (split)
     {
@@ -1488,7 +1408,7 @@ static int gn_prepare_batch(gn_stream* s, uint32_t w, hipStream_t st)
     hipLaunchKernelGGL(gn_slot_count_kernel, dim3((s->n_reads + 1 + 255) / 256), dim3(256), 0, st, s->d_off1,
                        s->paired ? s->d_off2 : nullptr, s->n_reads, w, s->d_slot_cnt);
     size_t tmp = s->scan_tmp_bytes;
-    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->d_scan_tmp, tmp, s->d_slot_cnt, s->d_slot_off, (int)(s->n_reads + 1), st));
+    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->d_scan_tmp, tmp, s->d_slot_cnt.get(), s->d_slot_off.get(), (int)(s->n_reads + 1), st));
     return GN_OK;
 }
 
@@ -1721,8 +1641,8 @@ static int gn_finish(gn_stream* s)
             if (s->pf_on && (!s->pf_joint || s->pf_joint_done)) // the batch's result is what the device-side filter_matches pre-pass left
             {
                 if (stale)
-                    GN_HIP(hipMemcpy(s->h_pf_ctr, s->d_pf_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                s->n_matches = s->h_pf_ctr[2];
+                    GN_HIP(hipMemcpy(s->pf.h_ctr, s->pf.d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+                s->n_matches = s->pf.h_ctr[2];
             }
             if (!s->f->is_hibf)
             {
@@ -1733,21 +1653,17 @@ static int gn_finish(gn_stream* s)
             return GN_OK;
         }
         const uint64_t ncap = need + need / 8 + 1024, ocap = s->match_cap;
-        hipFree(s->d_matches);
-        hipFree(s->d_sorted);
-        s->d_matches = s->d_sorted = nullptr;
-        if (gn_dmalloc(&s->d_matches, ncap) != hipSuccess || gn_dmalloc(&s->d_sorted, ncap) != hipSuccess)
+        s->d_matches.reset(); // (both freed before the first is allocated)
+        s->d_sorted.reset();
+        if (s->d_matches.alloc(ncap) != hipSuccess || s->d_sorted.alloc(ncap) != hipSuccess)
         {
             // no room for this batch's matches: the stream goes back to the buffers it had (so that a smaller batch can follow)
             (void)hipGetLastError();
-            if (s->d_matches)
-                hipFree(s->d_matches);
-            if (s->d_sorted)
-                hipFree(s->d_sorted);
-            s->d_matches = s->d_sorted = nullptr;
+            s->d_matches.reset();
+            s->d_sorted.reset();
             s->match_cap  = 0;
             s->classified = false;
-            if (gn_dmalloc(&s->d_matches, ocap) == hipSuccess && gn_dmalloc(&s->d_sorted, ocap) == hipSuccess)
+            if (s->d_matches.alloc(ocap) == hipSuccess && s->d_sorted.alloc(ocap) == hipSuccess)
                 s->match_cap = ocap;
             return gn_fail(GN_ENOMEM, "the batch has %llu matches: 2 x %.1f GB of match records do not fit into device memory next to the filter -- "
                                       "submit fewer reads per batch (or raise the cutoff)",
@@ -1860,9 +1776,9 @@ extern "C" int gn_stream_set_long_reads(gn_stream* s, int on)
     }
     if (!s->d_long_list)
     {
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_long_list), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_long_count), sizeof(unsigned long long)));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_long_scratch), (size_t)GN_LONG_BLOCKS * ((size_t)s->f->ibf.B + 64) * 4));
+        GN_HIP(s->d_long_list.alloc((size_t)s->max_reads + 1));
+        GN_HIP(s->d_long_count.alloc(1));
+        GN_HIP(s->d_long_scratch.alloc((size_t)GN_LONG_BLOCKS * ((size_t)s->f->ibf.B + 64)));
     }
     s->long_reads = true;
     return GN_OK;
@@ -1878,11 +1794,11 @@ extern "C" int gn_fetch_postfilter(gn_stream* s, uint32_t* max_count, uint64_t* 
     if (rc)
         return rc;
     if (max_count && s->n_reads)
-        GN_HIP(hipMemcpy(max_count, s->d_pf_max, (size_t)s->n_reads * 4, hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(max_count, s->pf.d_max, (size_t)s->n_reads * 4, hipMemcpyDeviceToHost));
     if (dropped_rel_filter)
-        *dropped_rel_filter = s->h_pf_ctr[0];
+        *dropped_rel_filter = s->pf.h_ctr[0];
     if (dropped_fpr_query)
-        *dropped_fpr_query = s->h_pf_ctr[1];
+        *dropped_fpr_query = s->pf.h_ctr[1];
     return GN_OK;
 }
 
@@ -1956,13 +1872,10 @@ extern "C" int gn_stream_dense_counts(gn_stream* s, uint32_t read_begin, uint32_
     if (f->is_hibf)
         return gn_hibf_dense(s, read_begin, read_end, counts);
     const size_t nel = (size_t)(read_end - read_begin) * f->ibf.B;
-    uint16_t*    dd  = nullptr;
-    GN_HIP(gn_dmalloc(&dd, nel));
+    GnDev<uint16_t> dd;
+    GN_HIP(dd.alloc(nel));
     if (hipMemsetAsync(dd, 0, nel * 2, s->st) != hipSuccess) // (skipped reads write nothing)
-    {
-        (void)hipFree(dd);
         return gn_fail(GN_ENODEV, "gn_stream_dense_counts: clearing the count matrix failed");
-    }
     // re-run the count kernel with the dense tap on (matches of this run are discarded)
     unsigned long long saved[GN_NCTR];
     memcpy(saved, s->h_ctr, sizeof(saved));
@@ -1973,21 +1886,20 @@ extern "C" int gn_stream_dense_counts(gn_stream* s, uint32_t read_begin, uint32_
     p.n_reads = s->n_reads; p.rel_cutoff = s->rel_cutoff; p.wpr = f->geom.wpr; p.gp_log2 = f->geom.gp_log2;
     p.slice_dwords = f->geom.slice_dwords;
     p.matches = s->d_matches; p.match_cap = 0; // no writes
-    unsigned long long* dctr = nullptr;
-    hipError_t e = gn_dmalloc(&dctr, 1);
-    if (e != hipSuccess) { hipFree(dd); return gn_fail(GN_ENOMEM, "alloc failed"); }
+    GnDev<unsigned long long> dctr;
+    GnDev<uint64_t>           segb;
+    GnDev<uint32_t>           segc;
+    if (dctr.alloc(1) != hipSuccess || segb.alloc((size_t)s->n_reads * f->geom.wpr) != hipSuccess
+        || segc.alloc((size_t)s->n_reads * f->geom.wpr) != hipSuccess)
+        return gn_fail(GN_ENOMEM, "alloc failed");
     hipMemsetAsync(dctr, 0, 8, s->st);
-    uint64_t* segb = nullptr; uint32_t* segc = nullptr;
-    gn_dmalloc(&segb, (size_t)s->n_reads * f->geom.wpr);
-    gn_dmalloc(&segc, (size_t)s->n_reads * f->geom.wpr);
     p.cursor = dctr; p.seg_begin = segb; p.seg_count = segc;
     p.dense = dd; p.dense_begin = read_begin; p.dense_end = read_end;
     p.max_blocks = (uint32_t)f->n_cu * 16u;
-    e = gn_launch_count(p, f->geom, f->ibf.h, s->st);
+    hipError_t e  = gn_launch_count(p, f->geom, f->ibf.h, s->st);
     hipError_t e2 = hipStreamSynchronize(s->st);
     if (e == hipSuccess && e2 == hipSuccess)
         e = hipMemcpy(counts, dd, nel * 2, hipMemcpyDeviceToHost);
-    hipFree(dd); hipFree(dctr); hipFree(segb); hipFree(segc);
     memcpy(s->h_ctr, saved, sizeof(saved));
     if (e != hipSuccess || e2 != hipSuccess)
         return gn_fail(GN_ENODEV, "dense count tap failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));

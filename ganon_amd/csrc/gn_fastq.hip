@@ -226,57 +226,42 @@ __global__ void gn_fq_finish_kernel(const uint32_t* __restrict__ nl, const uint6
     fq[5] = n_bytes;
 }
 
-void gn_fastq_release(gn_stream* s)
-{
-    if (s->fq_probe[3] > 0)
-        fprintf(stderr, "[hip call timing] gn_stream_upload_text x%.0f: initial sync %.3f ms, copy call %.3f ms, other calls %.3f ms per batch\n", s->fq_probe[3],
-                s->fq_probe[0] / s->fq_probe[3] * 1e3, s->fq_probe[1] / s->fq_probe[3] * 1e3, s->fq_probe[2] / s->fq_probe[3] * 1e3);
-    for (void* p : { (void*)s->d_text, (void*)s->d_fq_tile, (void*)s->d_fq_nl, (void*)s->d_fq_rec, (void*)s->d_fq_seq, (void*)s->d_fq_len, (void*)s->d_fq,
-                     (void*)s->d_fq_scan, (void*)s->d_fq_hoff, (void*)s->d_fq_hdr, s->d_fq_hscan, (void*)s->d_fq2_tile, (void*)s->d_fq2_nl, (void*)s->d_fq2_rec, (void*)s->d_fq2_seq, (void*)s->d_fq2_len })
-        if (p)
-            hipFree(p);
-    if (s->h_fq)
-        hipHostFree(s->h_fq);
-    s->d_text = nullptr;
-    s->d_fq_tile = s->d_fq_nl = s->d_fq_rec = s->d_fq_seq = s->d_fq_len = nullptr;
-    s->d_fq2_tile = s->d_fq2_nl = s->d_fq2_rec = s->d_fq2_seq = s->d_fq2_len = nullptr;
-    s->d_fq = nullptr;
-    s->d_fq_scan = nullptr;
-    s->d_fq_hoff = nullptr;
-    s->d_fq_hdr = nullptr;
-    s->d_fq_hscan = nullptr;
-    s->h_fq = nullptr;
-}
-
+// Each group of buffers is built aside and moved into the stream when it is whole: a failed allocation leaves the stream without it
 static int gn_fastq_prepare(gn_stream* s, bool pair)
 {
-    if (!s->d_text)
+    if (!s->fq.ready)
     {
+        GnFastqBufs b;
         // the text never holds more bytes than the stream holds bases (every base is a byte of it)
-        s->fq_text_cap  = s->max_bases;
-        s->fq_tiles_cap = (uint32_t)((s->fq_text_cap + GN_FQ_TILE - 1) / GN_FQ_TILE) + 1u;
-        s->fq_nl_cap    = 4u * s->max_reads + 4u;
-        GN_HIP(hipMalloc(&s->d_text, s->fq_text_cap + 64));
-        GN_HIP(hipMalloc(&s->d_fq_tile, ((size_t)s->fq_tiles_cap + 1) * 2 * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq_nl, (size_t)s->fq_nl_cap * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq_rec, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq_seq, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq_len, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq, 16 * sizeof(unsigned long long))); // [0..7] the text, [8..15] the mates' text
-        GN_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_fq), 16 * sizeof(unsigned long long), hipHostMallocDefault));
+        b.text_cap  = s->max_bases;
+        b.tiles_cap = (uint32_t)((b.text_cap + GN_FQ_TILE - 1) / GN_FQ_TILE) + 1u;
+        b.nl_cap    = 4u * s->max_reads + 4u;
+        GN_HIP(b.d_text.alloc(b.text_cap + 64));
+        GN_HIP(b.d_tile.alloc(((size_t)b.tiles_cap + 1) * 2));
+        GN_HIP(b.d_nl.alloc(b.nl_cap));
+        GN_HIP(b.d_rec.alloc((size_t)s->max_reads + 1));
+        GN_HIP(b.d_seq.alloc((size_t)s->max_reads + 1));
+        GN_HIP(b.d_len.alloc((size_t)s->max_reads + 1));
+        GN_HIP(b.d_fq.alloc(16)); // [0..7] the text, [8..15] the mates' text
+        GN_HIP(b.h_fq.alloc(16));
         size_t t1 = 0, t2 = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, t1, s->d_fq_tile, s->d_fq_tile, (int)(s->fq_tiles_cap + 1), s->st);
-        gn_scan_counts_from(nullptr, t2, s->d_fq_len, s->d_off1, (uint64_t)0, (int)(s->max_reads + 1), s->st);
-        s->fq_scan_bytes = std::max(t1, t2) + 256;
-        GN_HIP(hipMalloc(&s->d_fq_scan, s->fq_scan_bytes));
+        hipcub::DeviceScan::ExclusiveSum(nullptr, t1, b.d_tile.get(), b.d_tile.get(), (int)(b.tiles_cap + 1), s->st);
+        gn_scan_counts_from(nullptr, t2, b.d_len, s->d_off1, (uint64_t)0, (int)(s->max_reads + 1), s->st);
+        b.scan_bytes = std::max(t1, t2) + 256;
+        GN_HIP(b.d_scan.alloc(b.scan_bytes));
+        b.ready = true;
+        s->fq   = std::move(b);
     }
-    if (pair && !s->d_fq2_nl) // the mates' text has line and record tables of its own
+    if (pair && !s->fq2.ready) // the mates' text has line and record tables of its own
     {
-        GN_HIP(hipMalloc(&s->d_fq2_tile, ((size_t)s->fq_tiles_cap + 1) * 2 * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq2_nl, (size_t)s->fq_nl_cap * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq2_rec, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq2_seq, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq2_len, ((size_t)s->max_reads + 1) * sizeof(uint32_t)));
+        GnFastqMateBufs b;
+        GN_HIP(b.d_tile.alloc(((size_t)s->fq.tiles_cap + 1) * 2));
+        GN_HIP(b.d_nl.alloc(s->fq.nl_cap));
+        GN_HIP(b.d_rec.alloc((size_t)s->max_reads + 1));
+        GN_HIP(b.d_seq.alloc((size_t)s->max_reads + 1));
+        GN_HIP(b.d_len.alloc((size_t)s->max_reads + 1));
+        b.ready = true;
+        s->fq2  = std::move(b);
     }
     return GN_OK;
 }
@@ -289,16 +274,16 @@ static int gn_fq_enqueue(gn_stream* s, const uint8_t* d_text, uint64_t n_bytes, 
     const uint32_t lpr   = fasta ? 2u : 4u;
     const uint32_t tiles = (uint32_t)((n_bytes + GN_FQ_TILE - 1) / GN_FQ_TILE);
     uint32_t*      cnt   = d_tile;
-    uint32_t*      toff  = d_tile + s->fq_tiles_cap + 1;
+    uint32_t*      toff  = d_tile + s->fq.tiles_cap + 1;
     GN_HIP(hipMemsetAsync(cnt + tiles, 0, sizeof(uint32_t), st));
     GN_HIP(hipMemsetAsync(d_fq, 0, 8 * sizeof(unsigned long long), st));
     GN_HIP(hipMemsetAsync(d_fq + 1, 0xFF, sizeof(unsigned long long), st));
     if (tiles)
         hipLaunchKernelGGL(gn_fq_count_kernel, dim3(tiles), dim3(256), 0, st, d_text, n_bytes, cnt);
-    size_t tmp = s->fq_scan_bytes;
-    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->d_fq_scan, tmp, cnt, toff, (int)(tiles + 1), st));
+    size_t tmp = s->fq.scan_bytes;
+    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->fq.d_scan, tmp, cnt, toff, (int)(tiles + 1), st));
     if (tiles)
-        hipLaunchKernelGGL(gn_fq_lines_kernel, dim3(tiles), dim3(256), 0, st, d_text, n_bytes, toff, d_nl, s->fq_nl_cap);
+        hipLaunchKernelGGL(gn_fq_lines_kernel, dim3(tiles), dim3(256), 0, st, d_text, n_bytes, toff, d_nl, s->fq.nl_cap);
     // a four-line record is at least 6 bytes ("@\n\n+\n\n" is not even legal), a two-line one 3 (">\n\n"): bound of the per-record launches
     const uint32_t bound = (uint32_t)std::min<uint64_t>(s->max_reads, n_bytes / (fasta ? 3 : 6)) + 1u;
     if (format == GN_TEXT_FASTA)
@@ -307,8 +292,8 @@ static int gn_fq_enqueue(gn_stream* s, const uint8_t* d_text, uint64_t n_bytes, 
     else
         hipLaunchKernelGGL(gn_fq_records_kernel<0>, dim3((bound + 255) / 256), dim3(256), 0, st, d_text, d_nl, toff + tiles, s->max_reads, bound,
                            n_bytes, d_rec, d_seq, d_len, d_fq);
-    tmp = s->fq_scan_bytes;
-    GN_HIP(gn_scan_counts_from(s->d_fq_scan, tmp, d_len, d_off, off_init, (int)bound, st));
+    tmp = s->fq.scan_bytes;
+    GN_HIP(gn_scan_counts_from(s->fq.d_scan, tmp, d_len, d_off, off_init, (int)bound, st));
     const uint32_t blocks = std::min<uint32_t>((bound + 3) / 4, (uint32_t)s->f->n_cu * 8u);
     hipLaunchKernelGGL(gn_fq_copy_kernel, dim3(blocks), dim3(256), 0, st, d_text, d_seq, d_len, d_off, d_fq, s->max_reads, bound, lpr, s->d_bases, d_fq);
     return GN_OK;
@@ -341,32 +326,32 @@ static int gn_upload_texts(gn_stream* s, const uint8_t* text, uint64_t n_bytes, 
     if (n_bytes && src_device >= 0 && src_device != s->f->device)
     {
         gn_peer_enable(s->f->device, src_device);
-        GN_HIP(hipMemcpyPeerAsync(s->d_text, s->f->device, text, src_device, n_bytes, st));
+        GN_HIP(hipMemcpyPeerAsync(s->fq.d_text, s->f->device, text, src_device, n_bytes, st));
     }
     else if (n_bytes)
-        GN_HIP(hipMemcpyAsync(s->d_text, text, n_bytes, src_device >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(s->fq.d_text, text, n_bytes, src_device >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     const int dev2 = src_device2 == -2 ? src_device : src_device2;
     if (pair && n_bytes2 && dev2 >= 0 && dev2 != s->f->device)
     {
         gn_peer_enable(s->f->device, dev2);
-        GN_HIP(hipMemcpyPeerAsync(s->d_text + at2, s->f->device, text2, dev2, n_bytes2, st));
+        GN_HIP(hipMemcpyPeerAsync(s->fq.d_text + at2, s->f->device, text2, dev2, n_bytes2, st));
     }
     else if (pair && n_bytes2)
-        GN_HIP(hipMemcpyAsync(s->d_text + at2, text2, n_bytes2, dev2 >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(s->fq.d_text + at2, text2, n_bytes2, dev2 >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     const double p2 = probe ? now() : 0;
-    rc = gn_fq_enqueue(s, s->d_text, n_bytes, format, s->d_fq_tile, s->d_fq_nl, s->d_fq_rec, s->d_fq_seq, s->d_fq_len, s->d_fq, s->d_off1, 0, st);
+    rc = gn_fq_enqueue(s, s->fq.d_text, n_bytes, format, s->fq.d_tile, s->fq.d_nl, s->fq.d_rec, s->fq.d_seq, s->fq.d_len, s->fq.d_fq, s->d_off1, 0, st);
     if (rc)
         return rc;
     if (pair) // mate i's letters: behind every letter the first text can hold (off2 starts at the second text's place in the buffer)
     {
-        rc = gn_fq_enqueue(s, s->d_text + at2, n_bytes2, format, s->d_fq2_tile, s->d_fq2_nl, s->d_fq2_rec, s->d_fq2_seq, s->d_fq2_len, s->d_fq + 8,
+        rc = gn_fq_enqueue(s, s->fq.d_text + at2, n_bytes2, format, s->fq2.d_tile, s->fq2.d_nl, s->fq2.d_rec, s->fq2.d_seq, s->fq2.d_len, s->fq.d_fq + 8,
                            s->d_off2, at2, st);
         if (rc)
             return rc;
     }
-    hipLaunchKernelGGL(gn_fq_finish_kernel, dim3(1), dim3(1), 0, st, s->d_fq_nl, s->d_off1, s->max_reads, n_bytes, fasta ? 2u : 4u, s->d_fq,
-                       pair ? s->d_fq2_nl : nullptr, pair ? s->d_fq + 8 : nullptr, total);
-    GN_HIP(hipMemcpyAsync(s->h_fq, s->d_fq, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(gn_fq_finish_kernel, dim3(1), dim3(1), 0, st, s->fq.d_nl, s->d_off1, s->max_reads, n_bytes, fasta ? 2u : 4u, s->fq.d_fq,
+                       pair ? s->fq2.d_nl : nullptr, pair ? s->fq.d_fq + 8 : nullptr, total);
+    GN_HIP(hipMemcpyAsync(s->fq.h_fq, s->fq.d_fq, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     GN_HIP(hipGetLastError());
     if (probe)
     {
@@ -439,8 +424,8 @@ static int gn_text_index(gn_stream* s, bool pair, uint32_t* n_reads, uint64_t* n
     s->v_nh       = s->d_nh;
     s->v_status   = s->d_status;
     s->src        = nullptr;
-    s->n_reads    = (uint32_t)s->h_fq[2];
-    s->n_bases    = s->h_fq[3];
+    s->n_reads    = (uint32_t)s->fq.h_fq[2];
+    s->n_bases    = s->fq.h_fq[3];
     s->fq_reads   = s->n_reads;
     s->paired     = pair;
     s->have_reads = true;
@@ -452,9 +437,9 @@ static int gn_text_index(gn_stream* s, bool pair, uint32_t* n_reads, uint64_t* n
     if (n_bases)
         *n_bases = s->n_bases;
     if (parsed_bytes)
-        *parsed_bytes = s->h_fq[4];
+        *parsed_bytes = s->fq.h_fq[4];
     if (parsed_bytes2)
-        *parsed_bytes2 = s->h_fq[8 + 4];
+        *parsed_bytes2 = s->fq.h_fq[8 + 4];
     return GN_OK;
 }
 
@@ -498,16 +483,16 @@ static int gn_text_records(gn_stream* s, const uint32_t* d_rec, const uint32_t* 
 
 extern "C" int gn_stream_fastq_records(gn_stream* s, uint32_t* rec_at, uint32_t* seq_at, uint32_t* seq_len)
 {
-    if (!s || !s->have_reads || !s->d_text)
+    if (!s || !s->have_reads || !s->fq.ready)
         return gn_fail(GN_EINVAL, "gn_stream_fastq_records: not a tokenised batch");
-    return gn_text_records(s, s->d_fq_rec, s->d_fq_seq, s->d_fq_len, rec_at, seq_at, seq_len);
+    return gn_text_records(s, s->fq.d_rec, s->fq.d_seq, s->fq.d_len, rec_at, seq_at, seq_len);
 }
 
 extern "C" int gn_stream_text_pair_records2(gn_stream* s, uint32_t* rec_at, uint32_t* seq_at, uint32_t* seq_len)
 {
-    if (!s || !s->have_reads || !s->d_fq2_rec || !s->fq_pair)
+    if (!s || !s->have_reads || !s->fq2.ready || !s->fq_pair)
         return gn_fail(GN_EINVAL, "gn_stream_text_pair_records2: not a tokenised pair of texts");
-    return gn_text_records(s, s->d_fq2_rec, s->d_fq2_seq, s->d_fq2_len, rec_at, seq_at, seq_len);
+    return gn_text_records(s, s->fq2.d_rec, s->fq2.d_seq, s->fq2.d_len, rec_at, seq_at, seq_len);
 }
 
 // ---- header lines of the batch's records, for a caller that does not hold the text (gn_stream_upload_text_device) ----------------------
@@ -534,7 +519,7 @@ __global__ void gn_fq_hcopy_kernel(const uint8_t* __restrict__ text, const uint3
 
 extern "C" int gn_stream_fastq_headers(gn_stream* s, uint8_t* dst, uint64_t cap, uint32_t* hdr_off, uint64_t* n_bytes)
 {
-    if (!s || !s->have_reads || !s->d_text || !hdr_off || !n_bytes || (!dst && cap))
+    if (!s || !s->have_reads || !s->fq.ready || !hdr_off || !n_bytes || (!dst && cap))
         return gn_fail(GN_EINVAL, "gn_stream_fastq_headers: not a tokenised batch, or null argument");
     GN_HIP(hipSetDevice(s->f->device));
     const uint32_t n = s->n_reads;
@@ -542,21 +527,24 @@ extern "C" int gn_stream_fastq_headers(gn_stream* s, uint8_t* dst, uint64_t cap,
     hdr_off[0]       = 0;
     if (n == 0)
         return GN_OK;
-    if (!s->d_fq_hoff)
+    if (!s->fqh.ready)
     {
-        GN_HIP(hipMalloc(&s->d_fq_hoff, ((size_t)s->max_reads + 2) * 2 * sizeof(uint32_t)));
-        GN_HIP(hipMalloc(&s->d_fq_hdr, s->fq_text_cap + 64));
+        GnFastqHdrBufs b;
+        GN_HIP(b.d_hoff.alloc(((size_t)s->max_reads + 2) * 2));
+        GN_HIP(b.d_hdr.alloc(s->fq.text_cap + 64));
         size_t tmp = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, s->d_fq_hoff, s->d_fq_hoff, (int)(s->max_reads + 1), s->st);
-        s->fq_hscan_bytes = tmp + 256;
-        GN_HIP(hipMalloc(&s->d_fq_hscan, s->fq_hscan_bytes));
+        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, b.d_hoff.get(), b.d_hoff.get(), (int)(s->max_reads + 1), s->st);
+        b.scan_bytes = tmp + 256;
+        GN_HIP(b.d_scan.alloc(b.scan_bytes));
+        b.ready = true;
+        s->fqh  = std::move(b);
     }
-    uint32_t* hlen = s->d_fq_hoff;
-    uint32_t* hoff = s->d_fq_hoff + s->max_reads + 2;
-    hipLaunchKernelGGL(gn_fq_hlen_kernel, dim3((n + 256) / 256), dim3(256), 0, s->st, s->d_fq_rec, s->d_fq_seq, n, hlen);
-    size_t tmp = s->fq_hscan_bytes;
-    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->d_fq_hscan, tmp, hlen, hoff, (int)(n + 1), s->st));
-    hipLaunchKernelGGL(gn_fq_hcopy_kernel, dim3((n + 255) / 256), dim3(256), 0, s->st, s->d_text, s->d_fq_rec, hoff, n, s->d_fq_hdr);
+    uint32_t* hlen = s->fqh.d_hoff;
+    uint32_t* hoff = s->fqh.d_hoff + s->max_reads + 2;
+    hipLaunchKernelGGL(gn_fq_hlen_kernel, dim3((n + 256) / 256), dim3(256), 0, s->st, s->fq.d_rec, s->fq.d_seq, n, hlen);
+    size_t tmp = s->fqh.scan_bytes;
+    GN_HIP(hipcub::DeviceScan::ExclusiveSum(s->fqh.d_scan, tmp, hlen, hoff, (int)(n + 1), s->st));
+    hipLaunchKernelGGL(gn_fq_hcopy_kernel, dim3((n + 255) / 256), dim3(256), 0, s->st, s->fq.d_text, s->fq.d_rec, hoff, n, s->fqh.d_hdr);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpyAsync(hdr_off, hoff, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st));
     GN_HIP(hipStreamSynchronize(s->st));
@@ -564,7 +552,7 @@ extern "C" int gn_stream_fastq_headers(gn_stream* s, uint8_t* dst, uint64_t cap,
     *n_bytes             = total;
     if (total > cap)
         return gn_fail(GN_EOVERFLOW, "gn_stream_fastq_headers: %llu bytes of header lines, room for %llu", (unsigned long long)total, (unsigned long long)cap);
-    GN_HIP(hipMemcpyAsync(dst, s->d_fq_hdr, total, hipMemcpyDeviceToHost, s->st));
+    GN_HIP(hipMemcpyAsync(dst, s->fqh.d_hdr, total, hipMemcpyDeviceToHost, s->st));
     GN_HIP(hipStreamSynchronize(s->st));
     return GN_OK;
 }

@@ -33,18 +33,14 @@ struct gn_gather
     int         device = 0;
     hipStream_t st     = nullptr;
     uint32_t    n_parts = 0;
-    std::vector<uint32_t*> d_map; // per part: part-local target id -> caller's id (nullptr = the same)
+    std::vector<GnDev<uint32_t>> d_map; // per part: part-local target id -> caller's id (nullptr = the same)
     std::vector<uint32_t>  n_map;
     // landing buffers on `device` for parts that live elsewhere
-    std::vector<uint64_t*> d_off;
-    std::vector<uint64_t>  off_cap;
-    std::vector<gn_match*> d_in;
-    std::vector<uint64_t>  in_cap;
+    std::vector<GnDev<uint64_t>> d_off;
+    std::vector<GnDev<gn_match>> d_in;
     // result
-    uint64_t* d_moff   = nullptr;
-    uint64_t  moff_cap = 0;
-    gn_match* d_out    = nullptr;
-    uint64_t  out_cap  = 0;
+    GnDev<uint64_t> d_moff;
+    GnDev<gn_match> d_out;
     uint32_t  n_reads  = 0;
     uint64_t  n_matches = 0;
     uint64_t  peer_bytes = 0; // bytes that crossed devices in the last run
@@ -222,22 +218,10 @@ extern "C" int gn_gather_destroy(gn_gather* g)
         return GN_OK;
     hipSetDevice(g->device);
     if (g->st)
+    {
         hipStreamSynchronize(g->st);
-    for (auto* q : g->d_map)
-        if (q)
-            hipFree(q);
-    for (auto* q : g->d_off)
-        if (q)
-            hipFree(q);
-    for (auto* q : g->d_in)
-        if (q)
-            hipFree(q);
-    if (g->d_moff)
-        hipFree(g->d_moff);
-    if (g->d_out)
-        hipFree(g->d_out);
-    if (g->st)
         hipStreamDestroy(g->st);
+    }
     delete g;
     return GN_OK;
 }
@@ -258,21 +242,17 @@ extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* co
         return gn_fail(GN_ENOMEM, "out of host memory");
     g->device  = device;
     g->n_parts = n_parts;
-    g->d_map.assign(n_parts, nullptr);
+    g->d_map.resize(n_parts);
     g->n_map.assign(n_parts, 0);
-    g->d_off.assign(n_parts, nullptr);
-    g->off_cap.assign(n_parts, 0);
-    g->d_in.assign(n_parts, nullptr);
-    g->in_cap.assign(n_parts, 0);
+    g->d_off.resize(n_parts);
+    g->d_in.resize(n_parts);
     hipError_t e = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
     for (uint32_t i = 0; i < n_parts && e == hipSuccess; ++i)
     {
         if (!target_map || !target_map[i] || !n_map || n_map[i] == 0)
             continue;
         g->n_map[i] = n_map[i];
-        e = hipMalloc(reinterpret_cast<void**>(&g->d_map[i]), (size_t)n_map[i] * 4);
-        if (e == hipSuccess)
-            e = hipMemcpy(g->d_map[i], target_map[i], (size_t)n_map[i] * 4, hipMemcpyHostToDevice);
+        e = g->d_map[i].upload(target_map[i], n_map[i]);
     }
     if (e != hipSuccess)
     {
@@ -284,18 +264,9 @@ extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* co
 }
 
 template <typename T>
-static int gn_gather_reserve(T** p, uint64_t* cap, uint64_t need)
+static hipError_t gn_gather_reserve(GnDev<T>& b, uint64_t need)
 {
-    if (*cap >= need && *p)
-        return GN_OK;
-    if (*p)
-        GN_HIP(hipFree(*p));
-    *p   = nullptr;
-    *cap = 0;
-    const uint64_t n = need + need / 4 + 1024;
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-    *cap = n;
-    return GN_OK;
+    return b.reserve(need, need + need / 4 + 1024);
 }
 
 extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n_streams)
@@ -358,12 +329,8 @@ extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n
         else
         {
             GN_HIP(hipSetDevice(g->device));
-            int rc = gn_gather_reserve(&g->d_off[i], &g->off_cap[i], (uint64_t)n + 1);
-            if (rc)
-                return rc;
-            rc = gn_gather_reserve(&g->d_in[i], &g->in_cap[i], s->n_matches);
-            if (rc)
-                return rc;
+            GN_HIP(gn_gather_reserve(g->d_off[i], (uint64_t)n + 1));
+            GN_HIP(gn_gather_reserve(g->d_in[i], s->n_matches));
             gn_peer_enable(g->device, s->device);
             GN_HIP(hipMemcpyPeerAsync(g->d_off[i], g->device, src_off, s->device, ((size_t)n + 1) * 8, g->st));
             if (s->n_matches)
@@ -376,12 +343,8 @@ extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n
         p.map[i] = g->d_map[i];
     }
     GN_HIP(hipSetDevice(g->device));
-    int rc = gn_gather_reserve(&g->d_moff, &g->moff_cap, (uint64_t)n + 1);
-    if (rc)
-        return rc;
-    rc = gn_gather_reserve(&g->d_out, &g->out_cap, total);
-    if (rc)
-        return rc;
+    GN_HIP(gn_gather_reserve(g->d_moff, (uint64_t)n + 1));
+    GN_HIP(gn_gather_reserve(g->d_out, total));
     p.moff = g->d_moff;
     p.out  = g->d_out;
     hipLaunchKernelGGL(gn_gather_parts_kernel, dim3((unsigned)(((uint64_t)n + 1 + 255) / 256)), dim3(256), 0, g->st, p);
@@ -416,12 +379,8 @@ extern "C" int gn_gather_run_buffers(gn_gather* g, const uint64_t* const* d_off,
         p.map[i] = g->d_map[i];
         total += n_matches[i];
     }
-    int rc = gn_gather_reserve(&g->d_moff, &g->moff_cap, (uint64_t)n_reads + 1);
-    if (rc)
-        return rc;
-    rc = gn_gather_reserve(&g->d_out, &g->out_cap, total);
-    if (rc)
-        return rc;
+    GN_HIP(gn_gather_reserve(g->d_moff, (uint64_t)n_reads + 1));
+    GN_HIP(gn_gather_reserve(g->d_out, total));
     p.moff = g->d_moff;
     p.out  = g->d_out;
     hipLaunchKernelGGL(gn_gather_parts_kernel, dim3((unsigned)(((uint64_t)n_reads + 1 + 255) / 256)), dim3(256), 0, g->st, p);

@@ -1447,20 +1447,11 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
                 b = e;
             }
         }
-        uint4*    d_runs  = nullptr;
-        uint4*    d_mruns = nullptr;
-        uint32_t* d_tab   = nullptr;
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&d_runs), std::max<size_t>(1, runs.size()) * sizeof(uint4)));
-        f->hibf_allocs.push_back(d_runs);
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&d_mruns), std::max<size_t>(1, mruns.size()) * sizeof(uint4)));
-        f->hibf_allocs.push_back(d_mruns);
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&d_tab), tab.size() * sizeof(uint32_t)));
-        f->hibf_allocs.push_back(d_tab);
-        if (!runs.empty())
-            GN_HIP(hipMemcpy(d_runs, runs.data(), runs.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        if (!mruns.empty())
-            GN_HIP(hipMemcpy(d_mruns, mruns.data(), mruns.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        GN_HIP(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        GnDev<uint4>    d_runs, d_mruns;
+        GnDev<uint32_t> d_tab;
+        GN_HIP(d_runs.upload(runs.data(), runs.size()));
+        GN_HIP(d_mruns.upload(mruns.data(), mruns.size()));
+        GN_HIP(d_tab.upload(tab.data(), tab.size()));
         dev[i].rows    = f->ibfs[i].d_rows;
         dev[i].S       = f->ibfs[i].S;
         dev[i].W       = (uint32_t)f->ibfs[i].Ws; // width = stride on the device: the words a row is padded with are zero
@@ -1474,6 +1465,9 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
         dev[i].mruns   = d_mruns;
         dev[i].n_mruns = (uint32_t)mruns.size();
         max_tb         = std::max(max_tb, dev[i].W * 64u);
+        f->hibf_runs.push_back(std::move(d_runs));
+        f->hibf_runs.push_back(std::move(d_mruns));
+        f->hibf_tabs.push_back(std::move(d_tab));
         if (dev[i].h != dev[0].h)
             return gn_fail(GN_ERANGE, "IBFs of one HIBF with different numbers of hash functions (%u vs %u)", dev[i].h, dev[0].h);
     }
@@ -1534,8 +1528,7 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
         for (uint32_t l = 0; l < deepest; ++l)
             f->level_row_bytes[l] = 8u << f->level_gp[l];
     }
-    GN_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_hibf), n_ibf * sizeof(GnHibfIbfDev)));
-    GN_HIP(hipMemcpy(f->d_hibf, dev.data(), n_ibf * sizeof(GnHibfIbfDev), hipMemcpyHostToDevice));
+    GN_HIP(f->d_hibf.upload(dev.data(), n_ibf));
     f->n_user_bins = n_user_bins;
     f->max_bins    = max_tb;
     return GN_OK;
@@ -1543,28 +1536,24 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
 
 static int gn_hibf_ensure_sort_buffers(gn_stream* s)
 {
-    if (s->hibf_cap >= s->match_cap && s->d_keys[0])
+    if (s->sort.ready && s->sort.cap >= s->match_cap)
         return GN_OK;
+    // built aside and moved into the stream when it is whole: a failed allocation leaves the stream without the group
+    s->sort = GnHibfSortBufs{}; // free before malloc
+    GnHibfSortBufs b;
     for (int i = 0; i < 2; ++i)
     {
-        if (s->d_keys[i])
-            hipFree(s->d_keys[i]);
-        if (s->d_vals[i])
-            hipFree(s->d_vals[i]);
-        s->d_keys[i] = nullptr;
-        s->d_vals[i] = nullptr;
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_keys[i]), std::max<uint64_t>(1, s->match_cap) * 8));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_vals[i]), std::max<uint64_t>(1, s->match_cap) * 4));
+        GN_HIP(b.d_keys[i].alloc(s->match_cap));
+        GN_HIP(b.d_vals[i].alloc(s->match_cap));
     }
-    if (s->d_sort_tmp)
-        hipFree(s->d_sort_tmp);
-    s->d_sort_tmp = nullptr;
-    size_t tmp    = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, s->d_keys[0], s->d_keys[1], s->d_vals[0], s->d_vals[1],
+    size_t tmp = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, b.d_keys[0].get(), b.d_keys[1].get(), b.d_vals[0].get(), b.d_vals[1].get(),
                                        (int)std::min<uint64_t>(s->match_cap, 0x7FFFFFFFull), 0, 64, s->st);
-    s->sort_tmp_bytes = tmp + 256;
-    GN_HIP(hipMalloc(&s->d_sort_tmp, s->sort_tmp_bytes));
-    s->hibf_cap = s->match_cap;
+    b.tmp_bytes = tmp + 256;
+    GN_HIP(b.d_tmp.alloc(b.tmp_bytes));
+    b.cap   = s->match_cap;
+    b.ready = true;
+    s->sort = std::move(b);
     return GN_OK;
 }
 
@@ -1968,14 +1957,14 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
     const bool     no_pack = no_reg || gn_sw().hibf_pack;
     const uint32_t reg_bpc = gn_sw().hibf_bpc; // workgroups per CU of the register kernels: 0 = what the occupancy query says
     // with a filter_matches pre-pass on the stream, what it is bound to drop does not reach the sort
-    const bool may_predrop = s->pf_on && !s->pf_merge && s->d_pf_segmin && s->d_pf_rmax && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
-                             (uint64_t)n + 1 <= s->pf_segmin_cap && !gn_sw().predrop;
+    const bool may_predrop = s->pf_on && !s->pf_merge && s->pf.d_segmin && s->pf.d_rmax && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
+                             (uint64_t)n + 1 <= s->pf.segmin_cap && !gn_sw().predrop;
     s->pf_predrop = false;
     if (may_predrop)
     {
-        GN_HIP(hipMemsetAsync(s->d_pf_rmax, 0, ((size_t)n + 1) * 4, st));
-        GN_HIP(hipMemsetAsync(s->d_pf_segmin, 0xFF, ((size_t)n + 1) * 4, st));
-        GN_HIP(hipMemsetAsync(s->d_pf_pre, 0, 2 * sizeof(unsigned long long), st)); // [0] pairs left out [1] output cursor
+        GN_HIP(hipMemsetAsync(s->pf.d_rmax, 0, ((size_t)n + 1) * 4, st));
+        GN_HIP(hipMemsetAsync(s->pf.d_segmin, 0xFF, ((size_t)n + 1) * 4, st));
+        GN_HIP(hipMemsetAsync(s->pf.d_pre, 0, 2 * sizeof(unsigned long long), st)); // [0] pairs left out [1] output cursor
     }
     // pairs one range may have: the sort's int, and what the device could hold if the buffers were grown for it (two pair
     // buffers, two match buffers, the sort's scratch: ~64 bytes a pair) -- switch hibf_pair_limit=N for tests
@@ -2023,8 +2012,8 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
             p.count_out   = s->d_hctr + lvl + 1;
             p.work_cap    = s->work_cap;
             p.ctr         = s->d_ctr;
-            p.keys        = s->d_keys[0];
-            p.vals        = s->d_vals[0];
+            p.keys        = s->sort.d_keys[0];
+            p.vals        = s->sort.d_vals[0];
             p.match_cap   = s->match_cap;
             p.ub_bits     = ub_bits;
             p.lds_bins    = f->max_bins;
@@ -2195,16 +2184,20 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         if (worst > s->work_cap)
         {
             // a queue overflowed (entries past the capacity were dropped): grow the queues and run the range again
-            for (uint2** q : { &s->d_work[0], &s->d_work[1], &s->d_hdefer, &s->d_hdefer2 })
-            {
-                hipFree(*q);
-                *q = nullptr;
-            }
-            s->work_cap = (uint32_t)std::min<uint64_t>(worst + worst / 4 + 1024, 0xFFFFFFF0ull);
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_work[0]), (size_t)s->work_cap * sizeof(uint2)));
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_work[1]), (size_t)s->work_cap * sizeof(uint2)));
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_hdefer), (size_t)s->work_cap * sizeof(uint2)));
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_hdefer2), (size_t)s->work_cap * sizeof(uint2)));
+            // (all four are freed before the first is allocated; work_cap says what is there: 0 until all four are)
+            GnDev<uint2>* const queues[] = { &s->d_work[0], &s->d_work[1], &s->d_hdefer, &s->d_hdefer2 };
+            for (GnDev<uint2>* q : queues)
+                q->reset();
+            s->work_cap        = 0;
+            const uint32_t cap = (uint32_t)std::min<uint64_t>(worst + worst / 4 + 1024, 0xFFFFFFF0ull);
+            hipError_t     e   = hipSuccess;
+            for (GnDev<uint2>* q : queues)
+                e = e == hipSuccess ? q->alloc(cap) : e;
+            if (e != hipSuccess)
+                for (GnDev<uint2>* q : queues)
+                    q->reset();
+            GN_HIP(e);
+            s->work_cap = cap;
             if ((rc = restore()))
                 return rc;
             continue;
@@ -2229,16 +2222,16 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         int      src = 0;
         if (may_predrop && nm > 8ull * cnt)
         {
-            GN_HIP(hipMemsetAsync(s->d_pf_pre + 1, 0, sizeof(unsigned long long), st));
+            GN_HIP(hipMemsetAsync(s->pf.d_pre + 1, 0, sizeof(unsigned long long), st));
             const unsigned blocks = (unsigned)std::min<uint64_t>((nm + 255) / 256, (uint64_t)f->n_cu * 8);
-            hipLaunchKernelGGL(gn_hibf_premax_kernel, dim3(blocks), dim3(256), 0, st, s->d_keys[0], s->d_vals[0], nm, ub_bits, s->v_nh,
-                               s->d_pf_rmax);
-            hipLaunchKernelGGL(gn_hibf_predrop_kernel, dim3(blocks), dim3(256), 0, st, s->d_keys[0], s->d_vals[0], nm, ub_bits, s->v_nh,
-                               s->d_pf_rmax, s->rel_cutoff, s->pf_joint ? 2u : 1u, s->pf_rel_filter, s->d_keys[1], s->d_vals[1], s->match_cap,
-                               s->d_pf_pre + 1, s->d_pf_segmin, s->d_pf_pre);
+            hipLaunchKernelGGL(gn_hibf_premax_kernel, dim3(blocks), dim3(256), 0, st, s->sort.d_keys[0], s->sort.d_vals[0], nm, ub_bits, s->v_nh,
+                               s->pf.d_rmax);
+            hipLaunchKernelGGL(gn_hibf_predrop_kernel, dim3(blocks), dim3(256), 0, st, s->sort.d_keys[0], s->sort.d_vals[0], nm, ub_bits, s->v_nh,
+                               s->pf.d_rmax, s->rel_cutoff, s->pf_joint ? 2u : 1u, s->pf_rel_filter, s->sort.d_keys[1], s->sort.d_vals[1], s->match_cap,
+                               s->pf.d_pre + 1, s->pf.d_segmin, s->pf.d_pre);
             GN_HIP(hipGetLastError());
             unsigned long long out_n = 0;
-            GN_HIP(hipMemcpyAsync(&out_n, s->d_pf_pre + 1, sizeof(out_n), hipMemcpyDeviceToHost, st));
+            GN_HIP(hipMemcpyAsync(&out_n, s->pf.d_pre + 1, sizeof(out_n), hipMemcpyDeviceToHost, st));
             GN_HIP(hipStreamSynchronize(st));
             if (out_n <= s->match_cap) // (else: chunk holes pushed it past the buffer -- the raw pairs are sorted as they are)
             {
@@ -2261,17 +2254,17 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         }
         if (ns)
         {
-            size_t tmp = s->sort_tmp_bytes;
-            GN_HIP(hipcub::DeviceRadixSort::SortPairs(s->d_sort_tmp, tmp, s->d_keys[src], s->d_keys[1 - src], s->d_vals[src], s->d_vals[1 - src],
+            size_t tmp = s->sort.tmp_bytes;
+            GN_HIP(hipcub::DeviceRadixSort::SortPairs(s->sort.d_tmp, tmp, s->sort.d_keys[src].get(), s->sort.d_keys[1 - src].get(), s->sort.d_vals[src].get(), s->sort.d_vals[1 - src].get(),
                                                       (int)ns, 0, (int)(ub_bits + rd_bits), st));
             if (src == 1) // (the sorted pairs are expected in buffer 1)
             {
-                std::swap(s->d_keys[0], s->d_keys[1]);
-                std::swap(s->d_vals[0], s->d_vals[1]);
+                std::swap(s->sort.d_keys[0], s->sort.d_keys[1]);
+                std::swap(s->sort.d_vals[0], s->sort.d_vals[1]);
             }
-            hipLaunchKernelGGL(gn_hibf_finish_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, s->d_keys[1], s->d_vals[1], ns,
+            hipLaunchKernelGGL(gn_hibf_finish_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, s->sort.d_keys[1], s->sort.d_vals[1], ns,
                                ub_bits, s->v_nh, s->d_sorted, s->d_seg_count, d_out_base, s->match_cap);
-            hipLaunchKernelGGL(gn_hibf_advance_kernel, dim3(1), dim3(1), 0, st, s->d_keys[1], ns, d_out_base);
+            hipLaunchKernelGGL(gn_hibf_advance_kernel, dim3(1), dim3(1), 0, st, s->sort.d_keys[1], ns, d_out_base);
             GN_HIP(hipGetLastError());
             out_upper += ns;
         }
@@ -2319,8 +2312,8 @@ int gn_hibf_dense(gn_stream* s, uint32_t rb, uint32_t re, uint16_t* counts)
     std::vector<uint32_t> vals(nm ? nm : 1);
     if (nm)
     {
-        GN_HIP(hipMemcpy(keys.data(), s->d_keys[1], nm * 8, hipMemcpyDeviceToHost));
-        GN_HIP(hipMemcpy(vals.data(), s->d_vals[1], nm * 4, hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(keys.data(), s->sort.d_keys[1], nm * 8, hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(vals.data(), s->sort.d_vals[1], nm * 4, hipMemcpyDeviceToHost));
     }
     std::fill(counts, counts + (size_t)(re - rb) * f->n_user_bins, (uint16_t)0);
     for (uint64_t i = 0; i < nm; ++i)

@@ -2155,14 +2155,14 @@ struct gn_inflate
     uint64_t    step_bytes  = 256ull << 20;
     uint32_t    n_chunks_file = 0;
     uint32_t    next_chunk = 0; // first chunk of the file the next step decodes
-    uint8_t*    d_comp = nullptr;
+    GnDev<uint8_t> d_comp;
     // per step
     uint32_t  slots_cap = 0, fix_cap = 64;
     // Two sets of what a step's decode writes (chunk records, symbol pool, counters): the NEXT step's decode is launched on a stream
     // of its own as soon as its range is known, and runs beside this step's tail, order, window and resolve passes.
-    GiChunk*  d_chunks_set[GI_SETS] = {};
-    uint16_t* d_pool_set[GI_SETS]   = {};
-    uint32_t* d_ctr_set[GI_SETS]    = {};
+    GnDev<GiChunk>  d_chunks_set[GI_SETS];
+    GnDev<uint16_t> d_pool_set[GI_SETS];
+    GnDev<uint32_t> d_ctr_set[GI_SETS];
     hipStream_t st_dec[GI_SETS] = {}; // (one per set: the decodes run side by side, a later one fills what the tail of an earlier one leaves idle)
     hipEvent_t  ev_dec[GI_SETS][2] = {};
     int       n_sets = 0;
@@ -2177,42 +2177,41 @@ struct gn_inflate
     int nq = 0;
     int  set_in_use = -1;        // the set the running step reads
     bool ahead_from_next = false; // the step's true end is known: decodes ahead begin there
-    GiChunk*  d_chunks = nullptr; // (the set of the step being finished)
+    GiChunk*  d_chunks = nullptr; // (the set of the step being finished: d_chunks, d_pool and d_ctr point into d_*_set[k] and own nothing)
     uint16_t* d_pool   = nullptr;
     uint32_t  pool_cap = 0;
     uint32_t* d_ctr    = nullptr; // [0] pool_next [1] work_next
-    GiState*  d_state  = nullptr;
-    GiState*  h_state  = nullptr; // page-locked
-    uint8_t*  d_window = nullptr;
-    uint16_t* d_p_store = nullptr; // per chain chunk: its P (64 KiB)
-    uint16_t* d_g_store = nullptr; // per group: its function
-    uint8_t*  d_w_store = nullptr; // per group: the window before it
-    GiReal*   d_real = nullptr;
-    uint2*    d_work = nullptr;
+    GnDev<GiState>    d_state;
+    GnPinned<GiState> h_state;
+    GnDev<uint8_t>    d_window;
+    GnDev<uint16_t>   d_p_store; // per chain chunk: its P (64 KiB)
+    GnDev<uint16_t>   d_g_store; // per group: its function
+    GnDev<uint8_t>    d_w_store; // per group: the window before it
+    GnDev<GiReal>     d_real;
+    GnDev<uint2>      d_work;
     uint32_t  work_cap = 0;
-    uint8_t*  d_text[2] = { nullptr, nullptr };
+    GnDev<uint8_t>    d_text[2];
     uint64_t  text_cap = 0;
     int       cur = 1; // buffer of the last step
     uint64_t  n_text_last = 0;
     uint64_t  carry = 0; // bytes at the end of the last step's text that the next step's text begins with (gn_inflate_set_carry)
-    unsigned long long* d_mlist_pos = nullptr;
-    uint32_t* d_mlist_crc = nullptr; // [mlist_cap] wanted, then [mlist_cap + 1] accumulated, then [2] result
+    GnDev<unsigned long long> d_mlist_pos;
+    GnDev<uint32_t> d_mlist_crc; // [mlist_cap] wanted, then [mlist_cap + 1] accumulated, then [2] result
     uint32_t  mlist_cap = 65536;
     uint32_t  crc_carry = 0; // CRC-32 of the open member's bytes so far
-    uint32_t* h_crc = nullptr;
-    uint32_t* d_cut_cnt = nullptr; // newline counts per tile, then their exclusive sums
-    void*     d_cut_tmp = nullptr;
+    GnPinned<uint32_t> h_crc;
+    GnDev<uint32_t> d_cut_cnt; // newline counts per tile, then their exclusive sums
+    GnDev<uint8_t>  d_cut_tmp;
     size_t    cut_tmp_bytes = 0;
-    unsigned long long* d_cuts = nullptr;
-    uint32_t  cut_tiles_cap = 0, cuts_cap = 0;
+    GnDev<unsigned long long> d_cuts;
+    uint32_t  cut_tiles_cap = 0; // tiles d_cut_cnt and d_cut_tmp are sized for (0: not both there)
     uint64_t  lines_of_step = ~0ull; // the step whose text the line index in d_cut_cnt describes
     bool      ended = false;
     // Several inflaters of the SAME file on different devices take its steps in turn (gn_inflate_set_turns / gn_inflate_handoff): the
     // decode of a step -- nine tenths of the work -- depends on nothing before it; what the next step needs of this one is the stream
     // position, the member's length and CRC so far, the 32 KiB window and the text the step's end cut off (the carried record).
     uint32_t  turns = 1, turn = 0;
-    uint8_t*  d_carry_in = nullptr; // the carried text, when it came from another inflater
-    uint64_t  carry_in_cap = 0;
+    GnDev<uint8_t> d_carry_in; // the carried text, when it came from another inflater
     bool      carry_in = false;
     // totals
     gn_inflate_stats stats{};
@@ -2225,16 +2224,6 @@ static void gi_free(gn_inflate* z)
         return;
     hipSetDevice(z->device);
     hipDeviceSynchronize();
-    for (void* p : { (void*)z->d_comp, (void*)z->d_chunks_set[0], (void*)z->d_pool_set[0], (void*)z->d_ctr_set[0], (void*)z->d_chunks_set[1], (void*)z->d_pool_set[1], (void*)z->d_ctr_set[1],
-                     (void*)z->d_chunks_set[2], (void*)z->d_pool_set[2], (void*)z->d_ctr_set[2], (void*)z->d_state, (void*)z->d_window, (void*)z->d_p_store, (void*)z->d_g_store, (void*)z->d_w_store,
-                     (void*)z->d_real, (void*)z->d_work, (void*)z->d_mlist_pos, (void*)z->d_mlist_crc, (void*)z->d_cut_cnt, z->d_cut_tmp, (void*)z->d_cuts, (void*)z->d_text[0], (void*)z->d_text[1],
-                     (void*)z->d_carry_in })
-        if (p)
-            hipFree(p);
-    if (z->h_state)
-        hipHostFree(z->h_state);
-    if (z->h_crc)
-        hipHostFree(z->h_crc);
     for (hipStream_t s : { z->st, z->st_copy, z->st_out, z->st_dec[0], z->st_dec[1], z->st_dec[2] })
         if (s)
             hipStreamDestroy(s);
@@ -2293,7 +2282,7 @@ extern "C" int gn_inflate_create(int device, uint64_t compressed_bytes, uint32_t
     for (auto& ev : z->ev)
         GI_TRY(hipEventCreate(&ev), "event");
     const uint64_t comp_alloc = ((compressed_bytes + 3) & ~3ull) + 1024;
-    GI_TRY(hipMalloc((void**)&z->d_comp, comp_alloc), "compressed bytes");
+    GI_TRY(z->d_comp.alloc(comp_alloc), "compressed bytes");
     GI_TRY(hipMemsetAsync(z->d_comp + (compressed_bytes & ~3ull), 0, comp_alloc - (compressed_bytes & ~3ull), z->st), "memset");
     for (int k = 0; k < GI_SETS; ++k)
     {
@@ -2301,9 +2290,9 @@ extern "C" int gn_inflate_create(int device, uint64_t compressed_bytes, uint32_t
         if (k >= 1 && (uint64_t)z->n_chunks_file * z->chunk_bytes <= (uint64_t)k * step)
             break;
         z->n_sets = k + 1;
-        GI_TRY(hipMalloc((void**)&z->d_chunks_set[k], (size_t)(z->slots_cap + z->fix_cap) * sizeof(GiChunk)), "chunk records");
-        GI_TRY(hipMalloc((void**)&z->d_pool_set[k], (size_t)z->pool_cap * GI_PIECE * 2u), "symbol pool");
-        GI_TRY(hipMalloc((void**)&z->d_ctr_set[k], 64), "counters");
+        GI_TRY(z->d_chunks_set[k].alloc((size_t)z->slots_cap + z->fix_cap), "chunk records");
+        GI_TRY(z->d_pool_set[k].alloc((size_t)z->pool_cap * GI_PIECE), "symbol pool");
+        GI_TRY(z->d_ctr_set[k].alloc(16), "counters");
         {
             // the decodes run at the lowest stream priority: whatever else the device has to do (the step's own small passes, the
             // classification, a filter being loaded) goes first when a slot frees up
@@ -2315,23 +2304,23 @@ extern "C" int gn_inflate_create(int device, uint64_t compressed_bytes, uint32_t
         for (auto& e2 : z->ev_dec[k])
             GI_TRY(hipEventCreate(&e2), "event");
     }
-    GI_TRY(hipMalloc((void**)&z->d_state, sizeof(GiState)), "state");
-    GI_TRY(hipHostMalloc((void**)&z->h_state, sizeof(GiState), hipHostMallocDefault), "state (host)");
-    GI_TRY(hipMalloc((void**)&z->d_window, GI_WINDOW), "window");
+    GI_TRY(z->d_state.alloc(1), "state");
+    GI_TRY(z->h_state.alloc(1), "state (host)");
+    GI_TRY(z->d_window.alloc(GI_WINDOW), "window");
     GI_TRY(hipMemsetAsync(z->d_window, 0, GI_WINDOW, z->st), "memset");
     {
         const size_t real_cap = z->slots_cap + z->fix_cap, groups = (real_cap + GI_GROUP - 1) / GI_GROUP;
-        GI_TRY(hipMalloc((void**)&z->d_p_store, real_cap * GI_WINDOW * 2u), "windows");
-        GI_TRY(hipMalloc((void**)&z->d_g_store, groups * GI_WINDOW * 2u), "windows");
-        GI_TRY(hipMalloc((void**)&z->d_w_store, groups * GI_WINDOW), "windows");
+        GI_TRY(z->d_p_store.alloc(real_cap * GI_WINDOW), "windows");
+        GI_TRY(z->d_g_store.alloc(groups * GI_WINDOW), "windows");
+        GI_TRY(z->d_w_store.alloc(groups * GI_WINDOW), "windows");
     }
-    GI_TRY(hipMalloc((void**)&z->d_real, (size_t)(z->slots_cap + z->fix_cap) * sizeof(GiReal)), "chain");
-    GI_TRY(hipMalloc((void**)&z->d_work, (size_t)z->work_cap * sizeof(uint2)), "work list");
-    GI_TRY(hipMalloc((void**)&z->d_mlist_pos, (size_t)z->mlist_cap * sizeof(unsigned long long)), "member list");
-    GI_TRY(hipMalloc((void**)&z->d_mlist_crc, ((size_t)z->mlist_cap * 2u + 8u) * sizeof(uint32_t)), "member list");
-    GI_TRY(hipHostMalloc((void**)&z->h_crc, 2 * sizeof(uint32_t), hipHostMallocDefault), "crc result");
+    GI_TRY(z->d_real.alloc((size_t)z->slots_cap + z->fix_cap), "chain");
+    GI_TRY(z->d_work.alloc(z->work_cap), "work list");
+    GI_TRY(z->d_mlist_pos.alloc(z->mlist_cap), "member list");
+    GI_TRY(z->d_mlist_crc.alloc((size_t)z->mlist_cap * 2u + 8u), "member list");
+    GI_TRY(z->h_crc.alloc(2), "crc result");
     for (int b = 0; b < 2; ++b)
-        GI_TRY(hipMalloc((void**)&z->d_text[b], z->text_cap + 64), "text");
+        GI_TRY(z->d_text[b].alloc(z->text_cap + 64), "text");
     std::memset(z->h_state, 0, sizeof(GiState));
     GI_TRY(hipMemcpyAsync(z->d_state, z->h_state, sizeof(GiState), hipMemcpyHostToDevice, z->st), "state");
     GI_TRY(hipStreamSynchronize(z->st), "sync");
@@ -2364,7 +2353,7 @@ extern "C" int gn_inflate_feed(gn_inflate* z, const uint8_t* data, uint64_t n)
 static int gi_launch_chunks(gn_inflate* z, int set, hipStream_t st, uint64_t fed, uint32_t j0, uint32_t n, uint64_t fix_start, uint64_t fix_stop, uint32_t fix_slot)
 {
     GiParams p;
-    p.comp        = reinterpret_cast<const uint32_t*>(z->d_comp);
+    p.comp        = reinterpret_cast<const uint32_t*>(z->d_comp.get());
     p.avail_bits  = fed * 8u;
     p.total_bits  = z->total * 8u;
     p.chunk_bytes = z->chunk_bytes;
@@ -2650,17 +2639,8 @@ extern "C" int gn_inflate_handoff(gn_inflate* from, gn_inflate* to)
     {
         if (c > to->text_cap / 4u)
             return gn_fail(GN_EINVAL, "gn_inflate_handoff: %llu carried bytes are more than a quarter of a step's capacity", (unsigned long long)c);
-        if (to->carry_in_cap < c)
-        {
-            if (to->d_carry_in)
-                hipFree(to->d_carry_in);
-            to->d_carry_in   = nullptr;
-            to->carry_in_cap = 0;
-            const uint64_t cap = std::max<uint64_t>(c + c / 2u, 1u << 20);
-            if (hipMalloc((void**)&to->d_carry_in, cap) != hipSuccess)
-                return gn_fail(GN_ENOMEM, "gn_inflate_handoff: no room for %llu carried bytes", (unsigned long long)c);
-            to->carry_in_cap = cap;
-        }
+        if (to->d_carry_in.reserve(c, std::max<uint64_t>(c + c / 2u, 1u << 20)) != hipSuccess)
+            return gn_fail(GN_ENOMEM, "gn_inflate_handoff: no room for %llu carried bytes", (unsigned long long)c);
         GN_HIP(hipMemcpyPeerAsync(to->d_carry_in, to->device, from->d_text[from->cur] + (from->n_text_last - c), from->device, c, to->st));
     }
     to->carry    = c;
@@ -2719,28 +2699,18 @@ static int gi_line_index(gn_inflate* z, uint32_t m_cuts)
     const uint32_t tiles = (uint32_t)((n + GI_CUT_TILE - 1) / GI_CUT_TILE);
     if (tiles + 1u > z->cut_tiles_cap)
     {
-        if (z->d_cut_cnt)
-            hipFree(z->d_cut_cnt);
-        if (z->d_cut_tmp)
-            hipFree(z->d_cut_tmp);
-        z->d_cut_cnt = nullptr;
-        z->d_cut_tmp = nullptr;
+        z->cut_tiles_cap = 0;
+        z->d_cut_cnt.reset();
+        z->d_cut_tmp.reset();
         const uint32_t want = (uint32_t)((z->text_cap + GI_CUT_TILE - 1) / GI_CUT_TILE) + 2u;
-        GN_HIP(hipMalloc((void**)&z->d_cut_cnt, (size_t)want * 2u * sizeof(uint32_t)));
+        GN_HIP(z->d_cut_cnt.alloc((size_t)want * 2u));
         size_t tmp = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, z->d_cut_cnt, z->d_cut_cnt, (int)want, z->st);
+        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, z->d_cut_cnt.get(), z->d_cut_cnt.get(), (int)want, z->st);
         z->cut_tmp_bytes = tmp + 256;
-        GN_HIP(hipMalloc(&z->d_cut_tmp, z->cut_tmp_bytes));
+        GN_HIP(z->d_cut_tmp.alloc(z->cut_tmp_bytes));
         z->cut_tiles_cap = want;
     }
-    if (3u * m_cuts + 8u > z->cuts_cap)
-    {
-        if (z->d_cuts)
-            hipFree(z->d_cuts);
-        z->d_cuts = nullptr;
-        GN_HIP(hipMalloc((void**)&z->d_cuts, (size_t)(3u * m_cuts + 256u) * sizeof(unsigned long long)));
-        z->cuts_cap = 3u * m_cuts + 256u;
-    }
+    GN_HIP(z->d_cuts.reserve(3u * m_cuts + 8u, 3u * m_cuts + 256u));
     if (z->lines_of_step == z->stats.steps)
         return GN_OK;
     uint32_t* cnt = z->d_cut_cnt;

@@ -9,6 +9,7 @@
 
 #include "../../include/ganon_hip.h"
 #include "../../include/ganon_ibf_hash.h"
+#include "gn_devmem.h"
 
 #define GN_MAX_CHUNKS 64 // pipeline chunks per batch (minimiser on the side stream || count on the main stream)
 // candidate-driven select of the generic count kernel: targets with more bins than this are scanned from a list
@@ -222,9 +223,6 @@ struct GnHibfIbfDev
 
 // ---- misc kernels ---------------------------------------------------------------------------
 int  gn_run_postfilter(gn_stream* s);     // gn_postfilter.hip
-void gn_postfilter_release(gn_stream* s);
-void gn_build_release(gn_stream* s);       // gn_build.hip
-void gn_fastq_release(gn_stream* s);       // gn_fastq.hip
 void gn_peer_enable(int dst, int src);     // gn_gather.hip: direct device-to-device copies between the two (best effort)
 hipError_t gn_launch_emplace(uint64_t* rows, uint64_t S, uint32_t W, uint32_t shift, uint32_t h, const uint64_t* hashes,
                              const uint32_t* bins, uint64_t n, hipStream_t st);
@@ -243,7 +241,7 @@ int gn_fail(int code, const char* fmt, ...);
 
 struct GnIbfHost
 {
-    uint64_t* d_rows = nullptr;
+    GnDev<uint64_t> d_rows;
     uint64_t  S = 0, W = 0, B = 0;
     uint64_t  Ws = 0; // words from one row to the next on the device: W, or -- the IBFs of an HIBF -- W padded so that no row straddles a 128-byte
                       // line (gn_pad_row_words); the words beyond W are zero.  Everything the C ABI takes or returns is W words a row.
@@ -273,19 +271,18 @@ struct gn_filter
     bool     storage_only = false; // flat, created without a bin map: no streams (gn_filter_upload_ibf)
     uint64_t device_bytes = 0;
     hipStream_t load_st = nullptr; // streaming upload (gn_filter_write_rows), created on first use
-    uint64_t*   d_emplace_stage = nullptr; // gn_filter_emplace_split's staging buffer
-    uint64_t    emplace_stage_cap = 0;     // ... and its capacity in hashes
+    GnDev<uint64_t> d_emplace_stage; // gn_filter_emplace_split's staging buffer (cap(): its capacity in hashes)
     // flat
     GnIbfHost       ibf;
-    uint32_t*       d_tgt_off  = nullptr;
-    uint32_t*       d_tgt_bins = nullptr;
-    uint32_t*       d_tgt_lds  = nullptr;
-    uint4*          d_tgt_rec  = nullptr;
-    uint32_t*       d_bin_tgt  = nullptr; // bin -> CSR target (0xFFFFFFFF = none)
-    uint32_t*       d_bin_nb2  = nullptr; // see GnCountParams::bin_nb2
-    uint32_t*       d_big_list = nullptr; // targets with more than GN_CAND_NBIG bins
+    GnDev<uint32_t> d_tgt_off;
+    GnDev<uint32_t> d_tgt_bins;
+    GnDev<uint32_t> d_tgt_lds;
+    GnDev<uint4>    d_tgt_rec;
+    GnDev<uint32_t> d_bin_tgt;  // bin -> CSR target (0xFFFFFFFF = none)
+    GnDev<uint32_t> d_bin_nb2;  // see GnCountParams::bin_nb2
+    GnDev<uint32_t> d_big_list; // targets with more than GN_CAND_NBIG bins
     uint32_t        n_big      = 0;
-    uint32_t*       d_sl_nbr   = nullptr; // split kernel (GnCountParams::sl_nbr); nullptr = not applicable
+    GnDev<uint32_t> d_sl_nbr;   // split kernel (GnCountParams::sl_nbr); nullptr = not applicable
     uint32_t        split_bpc  = 0;       // split kernel: resident blocks per CU
     uint32_t        n_targets  = 0;
     bool            identity   = false;
@@ -296,8 +293,9 @@ struct gn_filter
     GnCountGeometry geom{};
     // hibf
     std::vector<GnIbfHost> ibfs;
-    std::vector<void*>     hibf_allocs;
-    GnHibfIbfDev*          d_hibf   = nullptr;
+    std::vector<GnDev<uint4>>    hibf_runs; // per IBF: what GnHibfIbfDev::runs and ::mruns point to
+    std::vector<GnDev<uint32_t>> hibf_tabs; // ... and ::bin_tab
+    GnDev<GnHibfIbfDev>    d_hibf;
     uint64_t               n_user_bins = 0;
     uint32_t               max_bins = 0;
     uint32_t               max_depth = 0;
@@ -305,6 +303,84 @@ struct gn_filter
     std::vector<std::vector<uint32_t>> level_gps; // ... and every width that occurs there, most common first
     std::vector<uint64_t>  level_bytes; // per tree level: bytes of the IBFs at that depth (is the level's table cache resident?)
     std::vector<uint32_t>  level_row_bytes; // per tree level: row bytes most of its IBFs have
+};
+
+// ---- buffer groups of a stream that are created on first use ------------------------------------------------------------
+// Each is built aside and moved into the stream only when every allocation succeeded (`ready`): a stream holds a group
+// completely or not at all, and no call finds half of one after an allocation failed.
+
+// device-side pre-pass of filter_matches (gn_postfilter.hip): created by the first gn_stream_set_postfilter
+struct GnPostfilterBufs
+{
+    bool                      ready = false;
+    GnDev<uint32_t>           d_keep; // survivors per read
+    GnDev<uint32_t>           d_max;  // max count per read before filtering
+    GnDev<uint32_t>           d_min;  // joint pass: min count per read (this stream's filter)
+    GnDev<uint32_t>           d_gmax; // joint pass: the level's max / min per read (filled on the first stream)
+    GnDev<uint32_t>           d_gmin;
+    GnDev<uint32_t>           d_peer; // joint pass over several devices: [this device's max | min] then one such pair per other device (grown on demand)
+    GnDev<uint32_t>           d_gid;  // merging form: device target -> level-wide target id (allocated when first asked for)
+    GnDev<double>             d_fpr;  // per target
+    GnDev<uint32_t>           d_segmin; // per (read, column slice): see GnCountParams::seg_min
+    uint64_t                  segmin_cap = 0;
+    GnDev<unsigned long long> d_pre;  // [0] matches the count kernel did not write (they count as dropped by rel_filter) [1] HIBF: cursor
+    GnDev<uint32_t>           d_rmax; // HIBF: largest count per read over the raw pairs (gn_hibf_premax_kernel)
+    GnDev<unsigned long long> d_ctr;  // [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+    GnPinned<unsigned long long> h_ctr; // pinned copy
+    GnDev<uint8_t>            d_scan;
+    size_t                    scan_bytes = 0;
+};
+
+// build side (gn_build.hip): pack / sort / unique buffers, allocated by the first gn_stream_distinct_hashes
+struct GnBuildBufs
+{
+    GnDev<uint64_t>           d_build[2];
+    GnDev<uint8_t>            d_tmp;
+    size_t                    tmp_bytes = 0;
+    GnDev<unsigned long long> d_ctr; // [0] packed hashes [1] distinct hashes
+    uint64_t                  cap = 0; // hashes d_build[] hold (0: no buffers)
+};
+
+// HIBF sort buffers (gn_hibf.hip), sized to the stream's match_cap
+struct GnHibfSortBufs
+{
+    bool            ready = false;
+    GnDev<uint64_t> d_keys[2];
+    GnDev<uint32_t> d_vals[2];
+    GnDev<uint8_t>  d_tmp;
+    size_t          tmp_bytes = 0;
+    uint64_t        cap = 0; // the match_cap they were sized to
+};
+
+// FASTQ text tokenised on the device (gn_fastq.hip); allocated by the first gn_stream_upload_fastq
+struct GnFastqBufs
+{
+    bool                      ready = false;
+    GnDev<uint8_t>            d_text;
+    GnDev<uint32_t>           d_tile; // newline count per 4 KiB tile, then its exclusive scan
+    GnDev<uint32_t>           d_nl;   // position of every newline (up to four per read the stream holds)
+    GnDev<uint32_t>           d_rec;  // per record: first byte / first letter / number of letters
+    GnDev<uint32_t>           d_seq;
+    GnDev<uint32_t>           d_len;
+    GnDev<unsigned long long> d_fq;   // see gn_fq_records_kernel
+    GnPinned<unsigned long long> h_fq; // pinned copy
+    GnDev<uint8_t>            d_scan;
+    size_t                    scan_bytes = 0;
+    uint64_t                  text_cap = 0;
+    uint32_t                  tiles_cap = 0, nl_cap = 0;
+};
+struct GnFastqMateBufs // the mates' text: line and record tables of its own
+{
+    bool            ready = false;
+    GnDev<uint32_t> d_tile, d_nl, d_rec, d_seq, d_len;
+};
+struct GnFastqHdrBufs // gn_stream_fastq_headers
+{
+    bool            ready = false;
+    GnDev<uint32_t> d_hoff; // header length per record, then the exclusive sums
+    GnDev<uint8_t>  d_hdr;  // ... the header lines back to back
+    GnDev<uint8_t>  d_scan;
+    size_t          scan_bytes = 0;
 };
 
 struct gn_stream
@@ -321,23 +397,24 @@ struct gn_stream
     uint64_t    max_bases = 0;
     uint64_t    match_cap = 0;
     // device buffers
-    uint8_t*            d_bases    = nullptr;
-    uint64_t*           d_off1     = nullptr;
-    uint64_t*           d_off2     = nullptr;
-    uint64_t*           d_slot_cnt = nullptr; // n+1 window counts (scan input)
-    uint64_t*           d_slot_off = nullptr; // n+1
-    uint64_t*           d_hashes   = nullptr;
-    uint32_t*           d_nh       = nullptr;
-    uint8_t*            d_status   = nullptr;
+    GnDev<uint8_t>      d_bases;
+    GnDev<uint64_t>     d_off1;
+    GnDev<uint64_t>     d_off2;
+    GnDev<uint64_t>     d_slot_cnt; // n+1 window counts (scan input)
+    GnDev<uint64_t>     d_slot_off; // n+1
+    GnDev<uint64_t>     d_hashes;
+    GnDev<uint32_t>     d_nh;
+    GnDev<uint8_t>      d_status;
     // what the count / select / fetch side READS: this stream's own buffers above, or -- after gn_stream_classify_shared -- those of
-    // the stream whose resident batch it shares (same device, same reads, hashed once)
+    // the stream whose resident batch it shares (same device, same reads, hashed once).  These, pf_out and every pointer inside a
+    // kernel parameter block (Gn*Params, GnHibfIbfDev) are aliases into buffers owned elsewhere: raw pointers, never freed.
     const uint64_t*     v_hashes   = nullptr;
     const uint64_t*     v_slot_off = nullptr;
     const uint32_t*     v_nh       = nullptr;
     const uint8_t*      v_status   = nullptr;
     gn_stream*          src        = nullptr; // the stream shared from (nullptr: own batch)
-    gn_match*           d_matches  = nullptr; // unordered (reservation order)
-    gn_match*           d_sorted   = nullptr; // grouped by read
+    GnDev<gn_match>     d_matches; // unordered (reservation order)
+    GnDev<gn_match>     d_sorted;  // grouped by read
     // A flat IBF whose reads are one unit each (wpr == 1) leaves every read's matches as ONE contiguous segment of d_matches
     // (seg_begin[r], seg_count[r]): that IS the grouped result, written once.  The pre-pass of filter_matches reads the segments
     // where they lie; the contiguous copy (d_sorted, CSR) is made only when a consumer asks for it (gn_result_compact), not per batch.
@@ -346,96 +423,59 @@ struct gn_stream
     gn_match*           pf_out     = nullptr; // where the pre-pass put its survivors (d_matches, or d_sorted when it read segments)
     hipEvent_t          ev_cmp[2]{};          // around the last contiguous copy (gn_timings.ms_compact)
     bool                cmp_timed  = false;
-    unsigned long long* d_ctr      = nullptr; // [0] cursor [1] total_hashes [2] algo_bytes [3] work count
-    uint64_t*           d_seg_begin = nullptr;
-    uint32_t*           d_seg_count = nullptr;
-    uint64_t*           d_seg_off   = nullptr; // n*wpr+1 exclusive scan of seg_count
-    uint32_t*           d_deferred  = nullptr; // reads the fast count kernel left to the generic one
-    uint32_t*           d_mdeferred = nullptr; // reads the lane-per-read minimiser kernel left to the wave-per-read one
-    void*               d_scan_tmp  = nullptr;
+    GnDev<unsigned long long> d_ctr; // [0] cursor [1] total_hashes [2] algo_bytes [3] work count
+    GnDev<uint64_t>     d_seg_begin;
+    GnDev<uint32_t>     d_seg_count;
+    GnDev<uint64_t>     d_seg_off;   // n*wpr+1 exclusive scan of seg_count
+    GnDev<uint32_t>     d_deferred;  // reads the fast count kernel left to the generic one
+    GnDev<uint32_t>     d_mdeferred; // reads the lane-per-read minimiser kernel left to the wave-per-read one
+    GnDev<uint8_t>      d_scan_tmp;
     size_t              scan_tmp_bytes = 0;
     // hibf work queues + sort buffers
-    uint2*        d_work[2]{ nullptr, nullptr };
-    uint2*        d_hdefer = nullptr;  // (read, ibf) items the packed kernel leaves to the per-item register-counter kernel
-    uint2*        d_hdefer2 = nullptr; // ... and those that one leaves to the LDS-counter kernel
-    unsigned long long* d_hsub = nullptr; // per level 3 x 128: counts, bases, cursors of the (width class, n-bin) keys of the level's sorted queue
-    unsigned long long* d_hctr = nullptr; // NL = GN_HIBF_MAXDEPTH+1 per row: [l] queue length of level l, [NL+l] / [2NL+l] deferred items
-    unsigned long long* h_hctr = nullptr; // pinned copy
-    uint32_t      work_cap = 0;
-    uint64_t*     d_keys[2]{ nullptr, nullptr };
-    uint32_t*     d_vals[2]{ nullptr, nullptr };
-    void*         d_sort_tmp = nullptr;
-    size_t        sort_tmp_bytes = 0;
-    uint64_t      hibf_cap = 0;
+    GnDev<uint2>  d_work[2];
+    GnDev<uint2>  d_hdefer;  // (read, ibf) items the packed kernel leaves to the per-item register-counter kernel
+    GnDev<uint2>  d_hdefer2; // ... and those that one leaves to the LDS-counter kernel
+    GnDev<unsigned long long> d_hsub; // per level 3 x 128: counts, bases, cursors of the (width class, n-bin) keys of the level's sorted queue
+    GnDev<unsigned long long> d_hctr; // NL = GN_HIBF_MAXDEPTH+1 per row: [l] queue length of level l, [NL+l] / [2NL+l] deferred items
+    GnPinned<unsigned long long> h_hctr; // pinned copy
+    uint32_t      work_cap = 0; // entries each of the four queues holds (0: not all four are there)
+    GnHibfSortBufs sort;
     hipEvent_t    ev_lvl[GN_HIBF_TIMED_LEVELS + 1]{}; // HIBF: start of every tree level's kernels (and the end of the last)
     uint32_t      hibf_levels_run = 0;
     uint32_t      hibf_ranges = 0;       // read ranges the last HIBF batch was run in (1 = the usual case)
     uint32_t      hibf_range_reads = 0;  // reads per range that went through last time (0: whole batches)
     // reads with more than 65 535 minimisers (gn_stream_set_long_reads): list, counter, uint32 count slabs of the long kernel
     bool                long_reads = false;
-    uint32_t*           d_long_list = nullptr;
-    unsigned long long* d_long_count = nullptr;
-    uint32_t*           d_long_scratch = nullptr;
-    // build side (gn_build.hip): pack / sort / unique buffers, allocated by the first gn_stream_distinct_hashes
-    uint64_t*           d_build[2]{ nullptr, nullptr };
-    void*               d_build_tmp = nullptr;
-    size_t              build_tmp_bytes = 0;
-    unsigned long long* d_build_ctr = nullptr; // [0] packed hashes [1] distinct hashes
-    uint64_t            build_cap = 0;
+    GnDev<uint32_t>           d_long_list;
+    GnDev<unsigned long long> d_long_count;
+    GnDev<uint32_t>           d_long_scratch;
+    GnBuildBufs         build;
     uint64_t            build_distinct = ~0ull; // result of the last gn_stream_distinct_hashes on the resident hashes (~0: none)
     // device-side pre-pass of filter_matches (gn_postfilter.hip); off unless gn_stream_set_postfilter enabled it
     bool                pf_on = false;
     double              pf_rel_filter = 0, pf_fpr_query = 1;
-    uint32_t*           d_pf_keep = nullptr; // survivors per read
-    uint32_t*           d_pf_max  = nullptr; // max count per read before filtering
-    uint32_t*           d_pf_min  = nullptr; // joint pass: min count per read (this stream's filter)
-    uint32_t*           d_pf_gmax = nullptr; // joint pass: the level's max / min per read (filled on the first stream)
-    uint32_t*           d_pf_gmin = nullptr;
+    GnPostfilterBufs    pf;
     bool                pf_joint  = false;   // the pass is run by gn_streams_postfilter_joint, not with the batch
     bool                pf_joint_done = false; // ... and has run for the batch this stream holds
-    uint32_t*           d_pf_peer = nullptr; // joint pass over several devices: [this device's max | min] then one such pair per other device
-    uint64_t            pf_peer_cap = 0;     // ... in uint32 entries
-    bool                pf_predrop = false;  // this batch's count kernel left surely-dropped matches unwritten (seg_min, d_pf_pre valid)
+    bool                pf_predrop = false;  // this batch's count kernel left surely-dropped matches unwritten (seg_min, pf.d_pre valid)
     bool                pf_merge  = false;   // ... in its merging form (filters of the level share targets)
-    uint32_t*           d_pf_gid  = nullptr; // merging form: device target -> level-wide target id
-    double*             d_pf_fpr  = nullptr; // per target
-    uint32_t*           d_pf_segmin = nullptr; // per (read, column slice): see GnCountParams::seg_min
-    uint64_t            pf_segmin_cap = 0;
-    unsigned long long* d_pf_pre  = nullptr; // [0] matches the count kernel did not write (they count as dropped by rel_filter) [1] HIBF: cursor
-    uint32_t*           d_pf_rmax = nullptr; // HIBF: largest count per read over the raw pairs (gn_hibf_premax_kernel)
-    unsigned long long* d_pf_ctr  = nullptr; // [0] dropped rel_filter [1] dropped fpr_query [2] survivors
-    unsigned long long* h_pf_ctr  = nullptr; // pinned copy
-    void*               d_pf_scan = nullptr;
-    size_t              pf_scan_bytes = 0;
-    // FASTQ text tokenised on the device (gn_fastq.hip); allocated by the first gn_stream_upload_fastq
-    uint8_t*            d_text    = nullptr;
-    uint32_t*           d_fq_tile = nullptr; // newline count per 4 KiB tile, then its exclusive scan
-    uint32_t*           d_fq_nl   = nullptr; // position of every newline (up to four per read the stream holds)
-    uint32_t*           d_fq_rec  = nullptr; // per record: first byte / first letter / number of letters
-    uint32_t*           d_fq_seq  = nullptr;
-    uint32_t*           d_fq_len  = nullptr;
-    unsigned long long* d_fq      = nullptr; // see gn_fq_records_kernel
-    uint32_t*           d_fq_hoff = nullptr; // gn_stream_fastq_headers: header length per record, then the exclusive sums
-    uint8_t*            d_fq_hdr  = nullptr; // ... the header lines back to back
-    void*               d_fq_hscan = nullptr;
-    size_t              fq_hscan_bytes = 0;
-    unsigned long long* h_fq      = nullptr; // pinned copy
-    void*               d_fq_scan = nullptr;
-    size_t              fq_scan_bytes = 0;
-    uint64_t            fq_text_cap = 0, fq_bytes = 0;
-    uint32_t            fq_tiles_cap = 0, fq_nl_cap = 0, fq_reads = 0;
-    uint32_t *          d_fq2_tile = nullptr, *d_fq2_nl = nullptr, *d_fq2_rec = nullptr, *d_fq2_seq = nullptr, *d_fq2_len = nullptr; // the mates' text
+    // FASTQ text tokenised on the device (gn_fastq.hip)
+    GnFastqBufs         fq;
+    GnFastqMateBufs     fq2;
+    GnFastqHdrBufs      fqh;
+    uint64_t            fq_bytes = 0;
+    uint32_t            fq_reads = 0;
     bool                fq_pair = false; // the resident text batch is a pair of texts (gn_stream_upload_text_pair)
     double              fq_probe[4]{}; // $GANON_HIP_CALL_TIMING: seconds in the calls of gn_stream_upload_fastq, batches
     bool                fq_pending = false;  // text uploaded, gn_stream_fastq_index not yet called
     // pinned host
-    unsigned long long* h_ctr = nullptr;
+    GnPinned<unsigned long long> h_ctr;
     // state
     uint32_t n_reads = 0;
     uint64_t n_bases = 0;
     bool     paired  = false;
     bool     have_reads = false, classified = false, hashed = false;
-    bool     ctr_copied = false; // the batch's counters are on their way to h_ctr / h_pf_ctr (queued behind its last kernel)
+    bool     ctr_copied = false; // the batch's counters are on their way to h_ctr / pf.h_ctr (queued behind its last kernel)
     // reads the previous batch left to the deferred launches (count stage, minimiser stage): their lists are usually empty and a
     // chip-filling persistent grid that finds nothing costs 0.1-0.2 ms per launch; ~0: unknown
     uint64_t prev_count_deferred = ~0ull, prev_min_deferred = ~0ull;

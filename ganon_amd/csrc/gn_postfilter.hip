@@ -382,7 +382,7 @@ __global__ void gn_postfilter_compact_kernel(const gn_match* __restrict__ in, gn
 }
 
 // queued on the stream right after the grouping pass; results: s->d_matches (compacted survivors), s->d_slot_cnt (n+1
-// offsets), s->d_pf_max, s->d_pf_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+// offsets), s->pf.d_max, s->pf.d_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
 static GnPostfilterParams gn_pf_params(gn_stream* s)
 {
     GnPostfilterParams p{};
@@ -396,16 +396,16 @@ static GnPostfilterParams gn_pf_params(gn_stream* s)
     p.nh         = s->v_nh;
     p.rel_filter = s->pf_rel_filter;
     p.fpr_query  = s->pf_fpr_query;
-    p.tfpr       = s->d_pf_fpr;
-    p.keep       = s->d_pf_keep;
-    p.maxc       = s->d_pf_max;
-    p.minc       = s->d_pf_min;
-    p.ctr        = s->d_pf_ctr;
+    p.tfpr       = s->pf.d_fpr;
+    p.keep       = s->pf.d_keep;
+    p.maxc       = s->pf.d_max;
+    p.minc       = s->pf.d_min;
+    p.ctr        = s->pf.d_ctr;
     p.cursor     = s->d_ctr;
     p.cap        = s->match_cap;
     p.n_targets  = s->f->is_hibf ? s->f->n_user_bins : s->f->n_targets;
-    p.seg_min    = s->pf_predrop ? s->d_pf_segmin : nullptr;
-    p.pre_ctr    = s->pf_predrop ? s->d_pf_pre : nullptr;
+    p.seg_min    = s->pf_predrop ? s->pf.d_segmin : nullptr;
+    p.pre_ctr    = s->pf_predrop ? s->pf.d_pre : nullptr;
     return p;
 }
 
@@ -414,26 +414,26 @@ static int gn_pf_finish(gn_stream* s, const GnPostfilterParams& p)
 {
     const uint32_t n      = s->n_reads;
     const unsigned blocks = (unsigned)(((uint64_t)n + 1 + 255) / 256);
-    size_t         tmp    = s->pf_scan_bytes;
-    GN_HIP(gn_scan_counts(s->d_pf_scan, tmp, s->d_pf_keep, s->d_slot_cnt, (int)(n + 1), s->st));
+    size_t         tmp    = s->pf.scan_bytes;
+    GN_HIP(gn_scan_counts(s->pf.d_scan, tmp, s->pf.d_keep, s->d_slot_cnt, (int)(n + 1), s->st));
     // survivors go to the buffer the pre-pass did not read: d_matches after a contiguous copy, d_sorted after segments
     gn_match* out = p.m == s->d_sorted ? s->d_matches : s->d_sorted;
     hipLaunchKernelGGL(gn_postfilter_compact_kernel, dim3(blocks), dim3(256), 0, s->st, p.m, out, s->d_seg_off, p.begin, p.stride,
-                       s->d_pf_keep, s->d_slot_cnt, n, s->d_ctr, s->match_cap);
+                       s->pf.d_keep, s->d_slot_cnt, n, s->d_ctr, s->match_cap);
     s->pf_out = out;
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(s->d_pf_ctr + 2, s->d_slot_cnt + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
-    GN_HIP(hipMemcpyAsync(s->h_pf_ctr, s->d_pf_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st));
+    GN_HIP(hipMemcpyAsync(s->pf.d_ctr + 2, s->d_slot_cnt + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
+    GN_HIP(hipMemcpyAsync(s->pf.h_ctr, s->pf.d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st));
     return GN_OK;
 }
 
 // queued on the stream right after the grouping pass; results: s->d_matches (compacted survivors), s->d_slot_cnt (n+1
-// offsets), s->d_pf_max, s->d_pf_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+// offsets), s->pf.d_max, s->pf.d_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
 int gn_run_postfilter(gn_stream* s)
 {
     if (!s->pf_on || s->pf_joint) // (a joint pass is run by gn_streams_postfilter_joint, after every stream of the level)
         return GN_OK;
-    GN_HIP(hipMemsetAsync(s->d_pf_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+    GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
     const GnPostfilterParams p = gn_pf_params(s);
     const unsigned blocks = (unsigned)(((uint64_t)s->n_reads + 1 + 255) / 256);
     hipLaunchKernelGGL(gn_postfilter_kernel<0>, dim3(blocks), dim3(256), 0, s->st, p);
@@ -699,28 +699,28 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
         for (uint32_t i = 0; i < n_streams; ++i)
         {
             gn_stream* s = streams[i];
-            if (!s->pf_merge || !s->d_pf_gid)
+            if (!s->pf_merge || !s->pf.d_gid)
                 return gn_fail(GN_EINVAL, "stream %u of a merging joint pass has no target_gid table", i);
             int rc = gn_finish_batch(s);
             if (rc)
                 return rc;
-            GN_HIP(hipMemsetAsync(s->d_pf_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+            GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
             if ((rc = gn_result_compact(s)) != GN_OK) // (the merge kernel walks contiguous per-read ranges)
                 return rc;
             mp.m[i]         = s->d_sorted;
             mp.off[i]       = s->d_seg_off;
             mp.stride[i]    = s->f->is_hibf ? 1u : (uint32_t)s->f->geom.wpr;
-            mp.gid[i]       = s->d_pf_gid;
-            mp.fpr[i]       = s->d_pf_fpr;
+            mp.gid[i]       = s->pf.d_gid;
+            mp.fpr[i]       = s->pf.d_fpr;
             mp.n_targets[i] = s->f->is_hibf ? s->f->n_user_bins : s->f->n_targets;
-            mp.maxc[i]      = s->d_pf_max;
+            mp.maxc[i]      = s->pf.d_max;
         }
         mp.n_reads    = n;
         mp.nh         = s0->v_nh;
         mp.rel_filter = s0->pf_rel_filter;
         mp.fpr_query  = s0->pf_fpr_query;
-        mp.ctr        = s0->d_pf_ctr;
-        mp.big        = s0->d_pf_min; // (a merging pass has no use for the per-stream minima: the buffer holds the list)
+        mp.ctr        = s0->pf.d_ctr;
+        mp.big        = s0->pf.d_min; // (a merging pass has no use for the per-stream minima: the buffer holds the list)
         for (uint32_t i = 0; i < n_streams; ++i)
             GN_HIP(hipStreamSynchronize(streams[i]->st));
         if (n)
@@ -778,7 +778,7 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
         if (rc)
             return rc;
         GN_HIP(hipSetDevice(s->device));
-        GN_HIP(hipMemsetAsync(s->d_pf_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+        GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
         hipLaunchKernelGGL(gn_postfilter_kernel<1>, dim3(blocks), dim3(256), 0, s->st, gn_pf_params(s));
         GN_HIP(hipGetLastError());
     }
@@ -793,28 +793,20 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
     {
         gn_stream* L = g.leader;
         GN_HIP(hipSetDevice(L->device));
-        uint32_t *lmax = L->d_pf_gmax, *lmin = L->d_pf_gmin;
+        uint32_t *lmax = L->pf.d_gmax, *lmin = L->pf.d_gmin;
         if (ng > 1)
         {
             const uint64_t need = 2ull * ((uint64_t)L->max_reads + 1) * ng;
-            if (L->pf_peer_cap < need)
-            {
-                if (L->d_pf_peer)
-                    GN_HIP(hipFree(L->d_pf_peer));
-                L->d_pf_peer   = nullptr;
-                L->pf_peer_cap = 0;
-                GN_HIP(hipMalloc(reinterpret_cast<void**>(&L->d_pf_peer), need * 4));
-                L->pf_peer_cap = need;
-            }
-            lmax = L->d_pf_peer;
-            lmin = L->d_pf_peer + slot;
+            GN_HIP(L->pf.d_peer.reserve(need, need));
+            lmax = L->pf.d_peer;
+            lmin = L->pf.d_peer + slot;
         }
         GnPfLists lists{};
         lists.k = (uint32_t)g.idx.size();
         for (size_t j = 0; j < g.idx.size(); ++j)
         {
-            lists.mx[j] = streams[g.idx[j]]->d_pf_max;
-            lists.mn[j] = streams[g.idx[j]]->d_pf_min;
+            lists.mx[j] = streams[g.idx[j]]->pf.d_max;
+            lists.mn[j] = streams[g.idx[j]]->pf.d_min;
         }
         if (n)
             hipLaunchKernelGGL(gn_pf_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, L->st, lists, n, lmax, lmin);
@@ -833,24 +825,24 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
             GN_HIP(hipSetDevice(L->device));
             GnPfLists lists{};
             lists.k     = (uint32_t)ng;
-            lists.mx[0] = L->d_pf_peer;
-            lists.mn[0] = L->d_pf_peer + slot;
+            lists.mx[0] = L->pf.d_peer;
+            lists.mn[0] = L->pf.d_peer + slot;
             size_t k    = 1;
             for (size_t b = 0; b < ng; ++b)
             {
                 if (b == a)
                     continue;
                 gn_stream* R   = groups[b].leader;
-                uint32_t*  dst = L->d_pf_peer + 2 * slot * k;
+                uint32_t*  dst = L->pf.d_peer + 2 * slot * k;
                 gn_peer_enable(L->device, R->device);
                 if (n) // [max | min] of the other device in one copy
-                    GN_HIP(hipMemcpyPeerAsync(dst, L->device, R->d_pf_peer, R->device, 2 * slot * 4, L->st));
+                    GN_HIP(hipMemcpyPeerAsync(dst, L->device, R->pf.d_peer, R->device, 2 * slot * 4, L->st));
                 lists.mx[k] = dst;
                 lists.mn[k] = dst + slot;
                 ++k;
             }
             if (n)
-                hipLaunchKernelGGL(gn_pf_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, L->st, lists, n, L->d_pf_gmax, L->d_pf_gmin);
+                hipLaunchKernelGGL(gn_pf_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, L->st, lists, n, L->pf.d_gmax, L->pf.d_gmin);
             GN_HIP(hipGetLastError());
         }
         for (auto& g : groups)
@@ -865,8 +857,8 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
             gn_stream* s = streams[i];
             GN_HIP(hipSetDevice(s->device));
             GnPostfilterParams p = gn_pf_params(s);
-            p.gmax = g.leader->d_pf_gmax;
-            p.gmin = g.leader->d_pf_gmin;
+            p.gmax = g.leader->pf.d_gmax;
+            p.gmin = g.leader->pf.d_gmin;
             hipLaunchKernelGGL(gn_postfilter_kernel<2>, dim3(blocks), dim3(256), 0, s->st, p);
             GN_HIP(hipGetLastError());
             int rc = gn_pf_finish(s, p);
@@ -896,33 +888,38 @@ extern "C" int gn_stream_set_postfilter(gn_stream* s, const gn_postfilter* pf)
     if (pf->fpr_query < 1.0 && !pf->target_fpr)
         return gn_fail(GN_EINVAL, "target_fpr is required when fpr_query < 1");
     GN_HIP(hipSetDevice(s->f->device));
-    if (!s->d_pf_keep)
+    if (!s->pf.ready)
     {
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_keep), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_max), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_min), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_gmax), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_gmin), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_ctr), 4 * sizeof(unsigned long long)));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_pre), 2 * sizeof(unsigned long long)));
-        s->pf_segmin_cap = ((uint64_t)s->max_reads + 1) * (s->f->is_hibf ? 1u : s->f->geom.wpr);
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_segmin), s->pf_segmin_cap * 4));
+        // built aside and moved into the stream when it is whole: a failed allocation leaves the stream without the group
+        GnPostfilterBufs b;
+        const size_t     nr = (size_t)s->max_reads + 1;
+        GN_HIP(b.d_keep.alloc(nr));
+        GN_HIP(b.d_max.alloc(nr));
+        GN_HIP(b.d_min.alloc(nr));
+        GN_HIP(b.d_gmax.alloc(nr));
+        GN_HIP(b.d_gmin.alloc(nr));
+        GN_HIP(b.d_ctr.alloc(4));
+        GN_HIP(b.d_pre.alloc(2));
+        b.segmin_cap = ((uint64_t)s->max_reads + 1) * (s->f->is_hibf ? 1u : s->f->geom.wpr);
+        GN_HIP(b.d_segmin.alloc(b.segmin_cap));
         if (s->f->is_hibf)
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_rmax), ((size_t)s->max_reads + 1) * 4));
-        GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_fpr), (nt ? nt : 1) * sizeof(double)));
-        GN_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_pf_ctr), 4 * sizeof(unsigned long long), hipHostMallocDefault));
+            GN_HIP(b.d_rmax.alloc(nr));
+        GN_HIP(b.d_fpr.alloc(nt));
+        GN_HIP(b.h_ctr.alloc(4));
         size_t tmp = 0;
-        gn_scan_counts(nullptr, tmp, s->d_pf_keep, s->d_slot_cnt, (int)(s->max_reads + 1), s->st);
-        GN_HIP(hipMalloc(&s->d_pf_scan, tmp ? tmp : 1));
-        s->pf_scan_bytes = tmp;
+        gn_scan_counts(nullptr, tmp, b.d_keep.get(), s->d_slot_cnt.get(), (int)(s->max_reads + 1), s->st);
+        GN_HIP(b.d_scan.alloc(tmp));
+        b.scan_bytes = tmp;
+        b.ready      = true;
+        s->pf        = std::move(b);
     }
     GN_HIP(hipStreamSynchronize(s->st)); // (a batch in flight still reads the previous table)
     if (pf->target_fpr && nt)
-        GN_HIP(hipMemcpy(s->d_pf_fpr, pf->target_fpr, nt * sizeof(double), hipMemcpyHostToDevice));
+        GN_HIP(hipMemcpy(s->pf.d_fpr, pf->target_fpr, nt * sizeof(double), hipMemcpyHostToDevice));
     else if (nt)
     {
         // (stream-ordered: s->st is a non-blocking stream, a null-stream fill would be unordered against its kernels)
-        GN_HIP(hipMemsetAsync(s->d_pf_fpr, 0, nt * sizeof(double), s->st));
+        GN_HIP(hipMemsetAsync(s->pf.d_fpr, 0, nt * sizeof(double), s->st));
         GN_HIP(hipStreamSynchronize(s->st));
     }
     s->pf_rel_filter = pf->rel_filter;
@@ -933,37 +930,14 @@ extern "C" int gn_stream_set_postfilter(gn_stream* s, const gn_postfilter* pf)
     {
         if (!pf->target_gid)
             return gn_fail(GN_EINVAL, "joint = 2 needs target_gid");
-        if (!s->d_pf_gid)
-            GN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pf_gid), (nt ? nt : 1) * sizeof(uint32_t)));
+        if (!s->pf.d_gid)
+            GN_HIP(s->pf.d_gid.alloc(nt));
         for (uint64_t t = 0; t < nt; ++t)
             if (pf->target_gid[t] >= (1u << 28))
                 return gn_fail(GN_ERANGE, "level-wide target ids must be below 2^28");
         if (nt)
-            GN_HIP(hipMemcpy(s->d_pf_gid, pf->target_gid, nt * sizeof(uint32_t), hipMemcpyHostToDevice));
+            GN_HIP(hipMemcpy(s->pf.d_gid, pf->target_gid, nt * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     s->pf_on         = true;
     return GN_OK;
-}
-
-void gn_postfilter_release(gn_stream* s)
-{
-    void* ptrs[] = { s->d_pf_keep, s->d_pf_max, s->d_pf_min, s->d_pf_gmax, s->d_pf_gmin, s->d_pf_ctr, s->d_pf_fpr, s->d_pf_scan, s->d_pf_gid,
-                     s->d_pf_segmin, s->d_pf_pre, s->d_pf_rmax, s->d_pf_peer };
-    for (void* q : ptrs)
-        if (q)
-            hipFree(q);
-    if (s->h_pf_ctr)
-        hipHostFree(s->h_pf_ctr);
-    s->d_pf_keep = s->d_pf_max = s->d_pf_min = s->d_pf_gmax = s->d_pf_gmin = s->d_pf_gid = nullptr;
-    s->d_pf_ctr  = nullptr;
-    s->d_pf_segmin = nullptr;
-    s->pf_segmin_cap = 0;
-    s->d_pf_pre  = nullptr;
-    s->d_pf_rmax = nullptr;
-    s->d_pf_peer = nullptr;
-    s->pf_peer_cap = 0;
-    s->pf_predrop = false;
-    s->d_pf_fpr  = nullptr;
-    s->d_pf_scan = nullptr;
-    s->h_pf_ctr  = nullptr;
 }

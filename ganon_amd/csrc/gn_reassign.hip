@@ -30,19 +30,19 @@ struct gn_reassign
     hipStream_t st     = nullptr;
     uint64_t    n_reads = 0, n_entries = 0;
     uint32_t    n_targets = 0;
-    uint64_t*   d_off    = nullptr; // n_reads + 1
-    uint32_t*   d_target = nullptr; // n_entries
-    uint32_t*   d_heavy  = nullptr; // reads with more than GN_RA_LIGHT entries
-    unsigned long long* d_n_heavy = nullptr;
+    GnDev<uint64_t>           d_off;    // n_reads + 1
+    GnDev<uint32_t>           d_target; // n_entries
+    GnDev<uint32_t>           d_heavy;  // reads with more than GN_RA_LIGHT entries
+    GnDev<unsigned long long> d_n_heavy;
     uint64_t    n_heavy = 0;
-    unsigned long long* d_uniq   = nullptr; // per target: reads that list it and nothing else (:96-103)
-    unsigned long long* d_counts = nullptr; // reassigned_matches of the last iteration (:113-121), widened for the fetch call
-    uint32_t*   d_w[2]   = { nullptr, nullptr }; // counts of the pass before (what a pass compares) / of the running pass
-    uint32_t*   d_chosen = nullptr; // per read: the target it chose in the pass before
-    double*     d_prob   = nullptr;
-    double*     d_absd   = nullptr; // |old - new| per target
-    double*     d_diff   = nullptr; // [0] the iteration's diff
-    uint64_t*   d_choice = nullptr; // entry index per read
+    GnDev<unsigned long long> d_uniq;   // per target: reads that list it and nothing else (:96-103)
+    GnDev<unsigned long long> d_counts; // reassigned_matches of the last iteration (:113-121), widened for the fetch call
+    GnDev<uint32_t>           d_w[2];   // counts of the pass before (what a pass compares) / of the running pass
+    GnDev<uint32_t>           d_chosen; // per read: the target it chose in the pass before
+    GnDev<double>             d_prob;
+    GnDev<double>             d_absd;   // |old - new| per target
+    GnDev<double>             d_diff;   // [0] the iteration's diff
+    GnDev<uint64_t>           d_choice; // entry index per read
     uint64_t    n_unique = 0;       // reads with exactly one entry
     uint64_t    n_multi  = 0;       // reads with more than one
     uint32_t    iterations = 0;
@@ -51,12 +51,6 @@ struct gn_reassign
     float       ms_em = 0.f;
     hipEvent_t  ev0 = nullptr, ev1 = nullptr;
 };
-
-template <typename T>
-static hipError_t ra_malloc(T** p, size_t n)
-{
-    return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
-}
 
 // ---- once per table ---------------------------------------------------------------------------------------------------
 // unique counts, the heavy-read list, and the number of unique / multi reads
@@ -329,19 +323,6 @@ static int ra_free(gn_reassign* g)
     hipSetDevice(g->device);
     if (g->st)
         hipStreamSynchronize(g->st);
-    hipFree(g->d_off);
-    hipFree(g->d_target);
-    hipFree(g->d_heavy);
-    hipFree(g->d_n_heavy);
-    hipFree(g->d_uniq);
-    hipFree(g->d_counts);
-    hipFree(g->d_w[0]);
-    hipFree(g->d_w[1]);
-    hipFree(g->d_chosen);
-    hipFree(g->d_prob);
-    hipFree(g->d_absd);
-    hipFree(g->d_diff);
-    hipFree(g->d_choice);
     if (g->ev0)
         hipEventDestroy(g->ev0);
     if (g->ev1)
@@ -396,19 +377,19 @@ extern "C" int gn_reassign_create(int device, uint64_t n_reads, uint64_t n_entri
     };
     ok(hipEventCreate(&g->ev0));
     ok(hipEventCreate(&g->ev1));
-    ok(ra_malloc(&g->d_off, n_reads + 1));
-    ok(ra_malloc(&g->d_target, n_entries));
-    ok(ra_malloc(&g->d_heavy, n_reads));
-    ok(ra_malloc(&g->d_n_heavy, 4));
-    ok(ra_malloc(&g->d_uniq, n_targets));
-    ok(ra_malloc(&g->d_counts, n_targets));
-    ok(ra_malloc(&g->d_w[0], n_targets));
-    ok(ra_malloc(&g->d_w[1], n_targets));
-    ok(ra_malloc(&g->d_chosen, n_reads));
-    ok(ra_malloc(&g->d_prob, n_targets));
-    ok(ra_malloc(&g->d_absd, n_targets));
-    ok(ra_malloc(&g->d_diff, 1));
-    ok(ra_malloc(&g->d_choice, n_reads));
+    ok(g->d_off.alloc(n_reads + 1));
+    ok(g->d_target.alloc(n_entries));
+    ok(g->d_heavy.alloc(n_reads));
+    ok(g->d_n_heavy.alloc(4));
+    ok(g->d_uniq.alloc(n_targets));
+    ok(g->d_counts.alloc(n_targets));
+    ok(g->d_w[0].alloc(n_targets));
+    ok(g->d_w[1].alloc(n_targets));
+    ok(g->d_chosen.alloc(n_reads));
+    ok(g->d_prob.alloc(n_targets));
+    ok(g->d_absd.alloc(n_targets));
+    ok(g->d_diff.alloc(1));
+    ok(g->d_choice.alloc(n_reads));
     if (e != hipSuccess)
     {
         ra_free(g);
