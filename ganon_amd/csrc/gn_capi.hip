@@ -52,8 +52,7 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
                               {"const_nb", &GnSwitches::const_nb},           {"split_kernel", &GnSwitches::split_kernel},
                               {"predrop", &GnSwitches::predrop},             {"deferred_grids", &GnSwitches::deferred_grids}, {"on_demand", &GnSwitches::on_demand}, {"hibf_dense_rows", &GnSwitches::hibf_dense_rows},
                               {"hibf_reg", &GnSwitches::hibf_reg},           {"hibf_pack", &GnSwitches::hibf_pack},
-                              {"hibf_one_pack", &GnSwitches::hibf_one_pack}, {"hibf_persistent", &GnSwitches::hibf_persistent}, {"hibf_stage", &GnSwitches::hibf_stage}, {"hibf_nsort", &GnSwitches::hibf_nsort}, {"hibf_reread", &GnSwitches::hibf_reread},
-                              {"hibf_fake_hashes", &GnSwitches::hibf_fake_hashes}, {"gather_copy", &GnSwitches::gather_copy},     {"joint_apart", &GnSwitches::joint_apart},
+                              {"hibf_one_pack", &GnSwitches::hibf_one_pack}, {"gather_copy", &GnSwitches::gather_copy},     {"joint_apart", &GnSwitches::joint_apart},
                               {"pinned_malloc", &GnSwitches::pinned_malloc}, {"inflate_ahead", &GnSwitches::inflate_ahead}, {"debug", &GnSwitches::debug},
                               {"fake_count", &GnSwitches::fake_count}, {"seg_result", &GnSwitches::seg_result}};
     for (const char* p = list ? list : ""; *p;)
@@ -72,8 +71,6 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
             sw.chunk = (uint32_t)strtoul(p + 6, nullptr, 10), known = true;
         if (!known && n > 11 && !strncmp(p, "emit_probe=", 11))
             sw.emit_probe = (uint32_t)strtoul(p + 11, nullptr, 10) & (64u | 128u), known = true;
-        if (!known && n > 9 && !strncmp(p, "hibf_bpc=", 9))
-            sw.hibf_bpc = (uint32_t)strtoul(p + 9, nullptr, 10), known = true;
         if (!known && n > 16 && !strncmp(p, "hibf_pair_limit=", 16))
             sw.hibf_pair_limit = std::max<uint64_t>(64, strtoull(p + 16, nullptr, 10)), known = true;
         if (!known && n > 5 && !strncmp(p, "sync=", 5))
@@ -1251,7 +1248,7 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     p.max_blocks = (uint32_t)f->n_cu * 16u;
     // persistent grid = a whole number of resident rounds: 8-byte-lane variant holds 4 blocks per CU, 16-byte one 3
     p.max_blocks_fast = (uint32_t)f->n_cu * (f->geom.lw == 1 ? 8u : 6u);
-    p.nt_loads = gn_sw().emit_probe; // (0 in the product; bits 6 / 7: the emission probe of the fast kernel's low-cutoff epilogue)
+    p.emit_probe = gn_sw().emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
     p.early_exit = gn_sw().early_exit ? 0u : 1u; // (bench.py's every-row measurement and the parity tests of the exit)
     p.skip_ctr   = s->d_ctr + 7;
     if (lo == 0) // (a re-run after a match-buffer regrow starts the tally again)

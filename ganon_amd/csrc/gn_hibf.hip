@@ -96,18 +96,15 @@ struct GnHibfLevelParams
     uint32_t                  n_reads;   // level 0 of the register-counter kernels: the reads are the items ...
     uint32_t                  read_base; // ... reads [read_base, read_base + n_reads) of the batch (a batch may be run in read ranges)
     const uint8_t*            status;
-    const unsigned long long* work_base; // packed kernel: its items begin at work_in[*work_base] (a class of the level's sorted list); nullptr = 0
     uint32_t                  pack_gp;   // packed kernel: log2 of the lanes per row every item of the launch must have
     // packed kernel, ONE launch for a level whose queue was sorted by row width: class c (c < n_cls) holds cls_count[c] items from
     // work_in[cls_base[c]] on, all of cls_gp[c] lanes per row; the persistent waves walk the classes one after the other (n_cls = 0:
-    // the single class described by pack_gp / count_in / work_base)
+    // the single class described by pack_gp / count_in, from work_in[0] on)
     uint32_t                  n_cls;
     uint8_t                   cls_gp[8];
     const unsigned long long* cls_count;
     const unsigned long long* cls_base;
     unsigned long long*       grab;      // packed kernel: per class the cursor its waves take their later batches from (zero at launch)
-    uint32_t                  fake_hashes;
-    uint32_t                  reread;
     uint32_t                  lds_region;   // packed kernel: 8-byte words of dynamic LDS per wave
     uint32_t                  stage_hashes; // packed kernel: the first GN_HIBF_NQ minimisers of every item are staged in LDS (classes of at
                                             // most 4 lanes per row; lds_region holds (64 >> narrowest class) items' worth)
@@ -320,9 +317,9 @@ __global__ __launch_bounds__(256) GN_PACK_ATTR void gn_hibf_pack_kernel(GnHibfLe
     {
         const unsigned long long nw64 = p.n_cls ? p.cls_count[cls] : *p.count_in;
         n_work                        = (uint32_t)(nw64 < p.work_cap ? nw64 : p.work_cap);
-        if (p.n_cls || p.work_base)
+        if (p.n_cls)
         {
-            work_first = p.n_cls ? p.cls_base[cls] : *p.work_base;
+            work_first = p.cls_base[cls];
             if (work_first + n_work > p.work_cap)
                 n_work = work_first < p.work_cap ? (uint32_t)(p.work_cap - work_first) : 0u;
         }
@@ -470,7 +467,6 @@ __global__ __launch_bounds__(256) GN_PACK_ATTR void gn_hibf_pack_kernel(GnHibfLe
             uint64_t m[HF];
         };
         const uint64_t hs_at = cur.slot; // (index into p.hashes)
-        const uint64_t fake0 = p.fake_hashes ? p.hashes[n ? hs_at : 0ull] : 0ull;
         const bool     staged = p.stage_hashes && gpl >= 1 && gpl <= 2; // (wave-uniform; see gn_hibf_pack_region)
 #ifdef GN_PACK_PROF
         const unsigned long long pp_t1 = GN_PP_NOW();
@@ -515,23 +511,19 @@ __global__ __launch_bounds__(256) GN_PACK_ATTR void gn_hibf_pack_kernel(GnHibfLe
         // memory latency (the rows), not two (hash, then rows) -- taken out of the chain in an experiment a level of narrow IBFs ran 21 %
         // faster (profiles/r05_hibf_probe_fake2.jsonl)
         auto fetch = [&](uint32_t it) -> uint64_t {
-            if (!(it < n || (p.reread && n)))
+            if (it >= n)
                 return 0ull;
-            const uint32_t q = it < n ? it : n - 1;
-            if (p.fake_hashes) // timing experiment: one load per item, the other "hashes" derived from it
-                return fake0 * (2ull * q + 1ull);
-            if (staged && q < GN_HIBF_NQ)
-                return hst[grp * GN_HIBF_NQ_STRIDE + q];
-            return p.hashes[hs_at + q];
+            if (staged && it < GN_HIBF_NQ)
+                return hst[grp * GN_HIBF_NQ_STRIDE + it];
+            return p.hashes[hs_at + it];
         };
         auto issue = [&](uint32_t it, Rows& R, uint64_t v) {
             // Lanes whose item is through (or is not counted here) issue nothing.  They used to re-read their last row "for free": with 64
             // items a wave the longest item has 1.29 x the mean number of minimisers, and a re-read row was long gone from the L1 and L2 --
             // a quarter of the level's row requests went to the fabric for nothing.  (A group's lanes share n: the branch is group-uniform,
             // the permutes below stay inside the group.)
-            if (it < n || (p.reread && n))
+            if (it < n)
             {
-                // (A/B switch hibf_reread: finished lanes read their last row again, as up to round 4 -- fetch() repeats the last hash)
                 uint32_t row[HF];
                 if (share)
                 {
@@ -1511,8 +1503,8 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
         for (uint32_t l = 0; l < deepest; ++l)
         {
             f->level_gp[l] = (uint32_t)(std::max_element(votes[l].begin(), votes[l].end()) - votes[l].begin());
-            // every lane width the level's IBFs have, most common first: the packed kernel runs once per width, each pass on what
-            // the pass before left (raptor's lower levels mix IBFs of 64 ... 1024 bins)
+            // every lane width the level's IBFs have, most common first: the packed kernel's one persistent launch walks them as its
+            // classes (raptor's lower levels mix IBFs of 64 ... 1024 bins)
             std::vector<uint32_t> order;
             for (uint32_t g = 0; g < 7; ++g)
                 if (votes[l][g])
@@ -1559,24 +1551,21 @@ static int gn_hibf_ensure_sort_buffers(gn_stream* s)
 
 // persistent grid = what is resident at once (the register budget decides)
 template <int HF, bool LEVEL0>
-static void gn_hibf_launch_reg2(const GnHibfLevelParams& p, uint32_t n_cu, uint32_t bpc, hipStream_t st)
+static void gn_hibf_launch_reg2(const GnHibfLevelParams& p, uint32_t n_cu, hipStream_t st)
 {
-    if (bpc == 0)
-    {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gn_hibf_reg_kernel<HF, LEVEL0>, 256, 0) != hipSuccess || per_cu < 1)
-            per_cu = 4;
-        bpc = (uint32_t)per_cu;
-    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gn_hibf_reg_kernel<HF, LEVEL0>, 256, 0) != hipSuccess || per_cu < 1)
+        per_cu = 4;
+    const uint32_t bpc = (uint32_t)per_cu;
     hipLaunchKernelGGL((gn_hibf_reg_kernel<HF, LEVEL0>), dim3(n_cu * bpc), dim3(256), 0, st, p);
 }
 template <int HF>
-static void gn_hibf_launch_reg(const GnHibfLevelParams& p, bool level0, uint32_t n_cu, uint32_t bpc, hipStream_t st)
+static void gn_hibf_launch_reg(const GnHibfLevelParams& p, bool level0, uint32_t n_cu, hipStream_t st)
 {
     if (level0)
-        gn_hibf_launch_reg2<HF, true>(p, n_cu, bpc, st);
+        gn_hibf_launch_reg2<HF, true>(p, n_cu, st);
     else
-        gn_hibf_launch_reg2<HF, false>(p, n_cu, bpc, st);
+        gn_hibf_launch_reg2<HF, false>(p, n_cu, st);
 }
 
 // dynamic LDS of a packed launch: per wave the 4 KB counter image, or the staged hashes of the items a wave of the narrowest class holds
@@ -1595,22 +1584,19 @@ static uint32_t gn_hibf_pack_region(GnHibfLevelParams& p, bool level0)
     else
         for (uint32_t c = 0; c < p.n_cls; ++c)
             take(p.cls_gp[c]);
-    p.stage_hashes = min_gp <= 2 && !gn_sw().hibf_stage ? 1u : 0u;
+    p.stage_hashes = min_gp <= 2 ? 1u : 0u;
     p.lds_region   = std::max<uint32_t>(GN_WAVE * 8u, p.stage_hashes ? (GN_WAVE >> min_gp) * GN_HIBF_NQ_STRIDE : 0u);
     return p.lds_region * 8u * 4u; // bytes per workgroup of four waves
 }
 
 template <int HF, bool LEVEL0>
-static void gn_hibf_launch_pack2(GnHibfLevelParams p, uint32_t n_cu, uint32_t bpc, hipStream_t st)
+static void gn_hibf_launch_pack2(GnHibfLevelParams p, uint32_t n_cu, hipStream_t st)
 {
     const uint32_t lds = gn_hibf_pack_region(p, LEVEL0);
-    if (bpc == 0)
-    {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gn_hibf_pack_kernel<HF, LEVEL0>, 256, lds) != hipSuccess || per_cu < 1)
-            per_cu = 2;
-        bpc = (uint32_t)per_cu;
-    }
+    int            per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gn_hibf_pack_kernel<HF, LEVEL0>, 256, lds) != hipSuccess || per_cu < 1)
+        per_cu = 2;
+    const uint32_t bpc = (uint32_t)per_cu;
     hipLaunchKernelGGL((gn_hibf_pack_kernel<HF, LEVEL0>), dim3(n_cu * bpc), dim3(256), lds, st, p);
 #ifdef GN_PACK_PROF
     {
@@ -1664,17 +1650,17 @@ static void gn_hibf_launch_pack2(GnHibfLevelParams p, uint32_t n_cu, uint32_t bp
 #endif
 }
 template <int HF>
-static void gn_hibf_launch_pack(const GnHibfLevelParams& p, bool level0, uint32_t n_cu, uint32_t bpc, hipStream_t st)
+static void gn_hibf_launch_pack(const GnHibfLevelParams& p, bool level0, uint32_t n_cu, hipStream_t st)
 {
     if (level0)
-        gn_hibf_launch_pack2<HF, true>(p, n_cu, bpc, st);
+        gn_hibf_launch_pack2<HF, true>(p, n_cu, st);
     else
-        gn_hibf_launch_pack2<HF, false>(p, n_cu, bpc, st);
+        gn_hibf_launch_pack2<HF, false>(p, n_cu, st);
 }
 
 // ---- a level's items sorted by the lane width of their IBF ------------------------------------------------------------------
 // raptor's lower levels mix IBFs of 64 ... 1024 technical bins; the packed kernel wants every item of a launch to have the same
-// lanes per row.  Two passes over the level's queue (8 bytes per item): count per class, then scatter -- class c = the c-th most
+// lanes per row.  Two passes over the level's queue (8 bytes per item): count per key, then scatter -- class c = the c-th most
 // common width of the level (cls_of_gp), class 7 = what the packed kernel does not take (wider than 64 words, more than 127
 // minimisers), which goes straight to the per-item kernels' list.  Holes of the chunked queue are dropped on the way.
 struct GnHibfBucketParams
@@ -1687,119 +1673,20 @@ struct GnHibfBucketParams
     uint8_t                   cls_of_gp[8];
     unsigned long long*       cls_count; // [8]
     unsigned long long*       cls_base;  // [8] exclusive prefix of cls_count[0..6]
-    unsigned long long*       cls_cursor; // [8]
     uint2*                    sorted_out;
     uint2*                    rest_out;  // class 7
     unsigned long long*       rest_count;
 };
 
-__device__ __forceinline__ uint32_t gn_hibf_item_class(const GnHibfBucketParams& p, uint2 e)
-{
-    if (e.x == 0xFFFFFFFFu)
-        return 8u; // a hole
-    const uint32_t W = p.ibfs[e.y].W, n = p.n_hashes[e.x];
-    if (n == 0)
-        return 8u;
-    if (W > GN_WAVE || n > 127u)
-        return 7u;
-    const uint32_t g = W <= 1 ? 0u : 32u - (uint32_t)__builtin_clz(W - 1);
-    return p.cls_of_gp[g];
-}
-
-// A workgroup takes the queue in chunks of 4096 items; per chunk ONE atomic per class (a counter address sustains only ~90 atomics
-// per microsecond: per-wave atomics made these two passes the most expensive kernels of the level).
-#define GN_HIBF_BUCKET_ROUNDS 16u
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void gn_hibf_bucket_kernel(GnHibfBucketParams p)
-{
-    __shared__ uint32_t           wave_cnt[4][8];
-    __shared__ unsigned long long chunk_base[8];
-    const unsigned long long      nw64 = *p.count_in;
-    const uint32_t                n    = (uint32_t)(nw64 < p.work_cap ? nw64 : p.work_cap);
-    const uint32_t                lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t                chunk = 256u * GN_HIBF_BUCKET_ROUNDS;
-    const uint32_t                n_chunks = (n + chunk - 1) / chunk;
-    for (uint32_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x)
-    {
-        const uint32_t first = ch * chunk + wave * 64u * GN_HIBF_BUCKET_ROUNDS; // this wave's 1024 items
-        uint32_t       mine[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            mine[c] = 0;
-        for (uint32_t k = 0; k < GN_HIBF_BUCKET_ROUNDS; ++k)
-        {
-            const uint32_t i = first + k * 64u + lane;
-            const uint32_t c = gn_hibf_item_class(p, i < n ? p.work_in[i] : make_uint2(0xFFFFFFFFu, 0u));
-#pragma unroll
-            for (uint32_t cc = 0; cc < 8; ++cc)
-                mine[cc] += (uint32_t)__popcll(__ballot(c == cc)); // (wave-uniform)
-        }
-        if (lane < 8)
-        {
-            uint32_t v = 0;
-#pragma unroll
-            for (uint32_t cc = 0; cc < 8; ++cc)
-                v = lane == cc ? mine[cc] : v;
-            wave_cnt[wave][lane] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < 8)
-        {
-            const uint32_t c     = threadIdx.x;
-            const uint32_t total = wave_cnt[0][c] + wave_cnt[1][c] + wave_cnt[2][c] + wave_cnt[3][c];
-            if (!SCATTER)
-            {
-                if (total)
-                    atomicAdd(&p.cls_count[c], (unsigned long long)total);
-            }
-            else
-                chunk_base[c] = total ? atomicAdd(c == 7 ? p.rest_count : &p.cls_cursor[c], (unsigned long long)total) : 0ull;
-        }
-        __syncthreads();
-        if (SCATTER)
-        {
-            unsigned long long at[8];
-#pragma unroll
-            for (uint32_t cc = 0; cc < 8; ++cc)
-            {
-                at[cc] = chunk_base[cc] + (cc == 7 ? 0ull : p.cls_base[cc]);
-                for (uint32_t w = 0; w < wave; ++w)
-                    at[cc] += wave_cnt[w][cc];
-            }
-            for (uint32_t k = 0; k < GN_HIBF_BUCKET_ROUNDS; ++k)
-            {
-                const uint32_t i = first + k * 64u + lane;
-                const uint2    e = i < n ? p.work_in[i] : make_uint2(0xFFFFFFFFu, 0u);
-                const uint32_t c = gn_hibf_item_class(p, e);
-#pragma unroll
-                for (uint32_t cc = 0; cc < 8; ++cc)
-                {
-                    const uint64_t m = __ballot(c == cc);
-                    if (c == cc)
-                    {
-                        const unsigned long long o = at[cc] + __popcll(m & ((1ULL << lane) - 1ULL));
-                        if (cc == 7)
-                        {
-                            if (o < p.work_cap)
-                                p.rest_out[o] = e;
-                        }
-                        else
-                            p.sorted_out[o] = e;
-                    }
-                    at[cc] += __popcll(m);
-                }
-            }
-        }
-        __syncthreads(); // (wave_cnt / chunk_base are reused by the next chunk)
-    }
-}
-
 // ---- ... and, inside a width class, by the number of minimisers ---------------------------------------------------------------------
 // A wave of the packed kernel holds up to 64 items and runs as many iterations as its LONGEST item has minimisers: reads of 150 bp have
 // 12 .. 25 (mean 17.6), the longest of 64 has 22.6 -- in a fifth of a wave's iterations part of its lanes have nothing in flight, on
-// levels that are bound by the requests a wave keeps outstanding.  The same two passes therefore sort by (class, n / 2): 16 bins of
-// two, everything from 30 minimisers up in the last.  Counting and scattering go through an LDS histogram per 4096-item chunk (one
-// global atomic per key and chunk); the order inside a key is whatever the LDS atomics give -- the matches are sorted at the end anyway.
+// levels that are bound by the requests a wave keeps outstanding.  The two passes therefore sort by (class, n / 2): 16 bins of
+// two, everything from 30 minimisers up in the last.  A workgroup takes the queue in chunks of 4096 items; counting and scattering go
+// through an LDS histogram per chunk and ONE global atomic per key and chunk (a counter address sustains only ~90 atomics per
+// microsecond: per-wave atomics made these two passes the most expensive kernels of the level); the order inside a key is whatever the
+// LDS atomics give -- the matches are sorted at the end anyway.
+#define GN_HIBF_BUCKET_ROUNDS 16u // 256 items of a chunk per round
 #define GN_HIBF_NBINS 16u
 #define GN_HIBF_NKEYS (7u * GN_HIBF_NBINS) // key 112 = what the packed kernel does not take (class 7), 113 = holes
 struct GnHibfSubParams
@@ -1914,17 +1801,6 @@ __global__ void gn_hibf_nsort_bases_kernel(const unsigned long long* __restrict_
     cls_count[7] = sub_count[GN_HIBF_NKEYS];
 }
 
-__global__ void gn_hibf_bucket_bases_kernel(const unsigned long long* __restrict__ cnt, unsigned long long* __restrict__ base)
-{
-    unsigned long long at = 0;
-    for (int c = 0; c < 7; ++c)
-    {
-        base[c] = at;
-        at += cnt[c];
-    }
-    base[7] = at;
-}
-
 // Runs all levels back to back (queue lengths stay on the device), synchronises ONCE, then sorts/groups the matches.
 int gn_finish_batch(gn_stream* s); // gn_capi.hip
 
@@ -1948,14 +1824,13 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         return gn_fail(GN_ERANGE, "read index and user bin do not fit one 64-bit sort key");
     GN_HIP(hipMemsetAsync(s->d_ctr + 1, 0, 3 * sizeof(unsigned long long), st)); // line bytes, algo bytes, (unused)
     GN_HIP(hipMemsetAsync(s->d_ctr + 6, 0, sizeof(unsigned long long), st));     // exact match count
-    GN_HIP(hipMemsetAsync(s->d_hctr, 0, (37 * NL + 2) * sizeof(unsigned long long), st)); // queues, per-level bytes, [4NL] output base, [4NL+2..] per-level line bytes, [5NL+2..] per level: 8 class counts, bases, cursors, [29NL+2..] batch cursors of the packed kernel
+    GN_HIP(hipMemsetAsync(s->d_hctr, 0, (37 * NL + 2) * sizeof(unsigned long long), st)); // queues, per-level bytes, [4NL] output base, [4NL+2..] per-level line bytes, [5NL+2..] per level: 8 class counts, 8 bases, (8 unused), [29NL+2..] batch cursors of the packed kernel
     GN_HIP(hipMemsetAsync(s->d_seg_count, 0, ((size_t)n + 1) * 4, st));
     unsigned long long* d_out_base = s->d_hctr + 4 * NL;
     const uint32_t h      = f->ibfs[0].h;
     // tests / A-B: skip the packed kernel (the per-item register kernel takes whole levels), or both (LDS kernel only)
     const bool     no_reg  = gn_sw().hibf_reg;
     const bool     no_pack = no_reg || gn_sw().hibf_pack;
-    const uint32_t reg_bpc = gn_sw().hibf_bpc; // workgroups per CU of the register kernels: 0 = what the occupancy query says
     // with a filter_matches pre-pass on the stream, what it is bound to drop does not reach the sort
     const bool may_predrop = s->pf_on && !s->pf_merge && s->pf.d_segmin && s->pf.d_rmax && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
                              (uint64_t)n + 1 <= s->pf.segmin_cap && !gn_sw().predrop;
@@ -1982,8 +1857,7 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         GN_HIP(hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), st));
         GN_HIP(hipMemsetAsync(s->d_hctr, 0, 3 * NL * sizeof(unsigned long long), st));
         GN_HIP(hipMemsetAsync(s->d_hctr + 5 * NL + 2, 0, 32 * NL * sizeof(unsigned long long), st));
-        if (s->d_hsub)
-            GN_HIP(hipMemsetAsync(s->d_hsub, 0, (size_t)NL * 384 * sizeof(unsigned long long), st));
+        GN_HIP(hipMemsetAsync(s->d_hsub, 0, (size_t)NL * 384 * sizeof(unsigned long long), st));
         if (cnt && no_reg) // (the register-counter kernels take level 0 straight from the batch)
             hipLaunchKernelGGL(gn_hibf_seed_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, s->d_work[0], s->v_status, lo, cnt, s->d_hctr,
                                s->long_reads ? 1u : 0u);
@@ -2004,8 +1878,6 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
             p.n_hashes    = s->v_nh;
             p.rel_cutoff  = s->rel_cutoff;
             p.wide        = s->long_reads ? 1u : 0u;
-            p.reread      = gn_sw().hibf_reread ? 1u : 0u;
-            p.fake_hashes = gn_sw().hibf_fake_hashes && lvl > 0 ? 1u : 0u; // (level 0 keeps its real hashes: the lower levels get their real items)
             p.work_in     = s->d_work[lvl & 1];
             p.count_in    = s->d_hctr + lvl;
             p.work_out    = s->d_work[(lvl + 1) & 1];
@@ -2027,19 +1899,19 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
             auto   launch_pack = [&]() {
                 switch (h)
                 {
-                    case 1: gn_hibf_launch_pack<1>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 2: gn_hibf_launch_pack<2>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 3: gn_hibf_launch_pack<3>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 4: gn_hibf_launch_pack<4>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    default: gn_hibf_launch_pack<5>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
+                    case 1: gn_hibf_launch_pack<1>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 2: gn_hibf_launch_pack<2>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 3: gn_hibf_launch_pack<3>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 4: gn_hibf_launch_pack<4>(p, level0, (uint32_t)f->n_cu, st); break;
+                    default: gn_hibf_launch_pack<5>(p, level0, (uint32_t)f->n_cu, st); break;
                 }
             };
             const bool one_pass = gn_sw().hibf_one_pack; // tests: the level's most common width only
             const std::vector<uint32_t>& gps = lvl < f->level_gps.size() ? f->level_gps[lvl] : std::vector<uint32_t>();
             if (!no_pack && !level0 && gps.size() > 1 && !one_pass)
             {
-                // IBFs of several widths on this level: the queue is sorted by width first, then one packed launch per width over its
-                // part of the sorted list; what those do not take (and the widths beyond 64 words) is the per-item kernels' list
+                // IBFs of several widths on this level: the queue is sorted by (width, number of minimisers) first, then the packed
+                // kernel takes the sorted list; what it does not take (and the widths beyond 64 words) is the per-item kernels' list
                 GnHibfBucketParams bp{};
                 bp.ibfs     = f->d_hibf;
                 bp.n_hashes = s->v_nh;
@@ -2052,52 +1924,28 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
                     bp.cls_of_gp[gps[c]] = (uint8_t)c;
                 bp.cls_count  = s->d_hctr + 5 * NL + 2 + (size_t)lvl * 8;
                 bp.cls_base   = s->d_hctr + 13 * NL + 2 + (size_t)lvl * 8;
-                bp.cls_cursor = s->d_hctr + 21 * NL + 2 + (size_t)lvl * 8;
                 bp.sorted_out = s->d_hdefer;
                 bp.rest_out   = s->d_hdefer2;
                 bp.rest_count = s->d_hctr + NL + lvl;
                 const dim3 grid((uint32_t)f->n_cu * 8u);
-                if (!gn_sw().hibf_nsort && s->d_hsub)
-                {
-                    GnHibfSubParams sp{ s->d_hsub + (size_t)lvl * 384, s->d_hsub + (size_t)lvl * 384 + 128, s->d_hsub + (size_t)lvl * 384 + 256 };
-                    hipLaunchKernelGGL(gn_hibf_nsort_kernel<false>, grid, dim3(256), 0, st, bp, sp);
-                    hipLaunchKernelGGL(gn_hibf_nsort_bases_kernel, dim3(1), dim3(1), 0, st, sp.sub_count, sp.sub_base, bp.cls_count, bp.cls_base);
-                    hipLaunchKernelGGL(gn_hibf_nsort_kernel<true>, grid, dim3(256), 0, st, bp, sp);
-                }
-                else
-                {
-                    hipLaunchKernelGGL(gn_hibf_bucket_kernel<false>, grid, dim3(256), 0, st, bp);
-                    hipLaunchKernelGGL(gn_hibf_bucket_bases_kernel, dim3(1), dim3(1), 0, st, bp.cls_count, bp.cls_base);
-                    hipLaunchKernelGGL(gn_hibf_bucket_kernel<true>, grid, dim3(256), 0, st, bp);
-                }
+                GnHibfSubParams sp{ s->d_hsub + (size_t)lvl * 384, s->d_hsub + (size_t)lvl * 384 + 128, s->d_hsub + (size_t)lvl * 384 + 256 };
+                hipLaunchKernelGGL(gn_hibf_nsort_kernel<false>, grid, dim3(256), 0, st, bp, sp);
+                hipLaunchKernelGGL(gn_hibf_nsort_bases_kernel, dim3(1), dim3(1), 0, st, sp.sub_count, sp.sub_base, bp.cls_count, bp.cls_base);
+                hipLaunchKernelGGL(gn_hibf_nsort_kernel<true>, grid, dim3(256), 0, st, bp, sp);
                 GN_HIP(hipGetLastError());
                 p.work_in     = s->d_hdefer;
                 p.defer_out   = s->d_hdefer2;
                 p.defer_count = s->d_hctr + NL + lvl;
-                if (!gn_sw().hibf_persistent)
-                {
-                    // ONE persistent launch walks the classes of the sorted list one after the other (a launch per width left the chip
-                    // draining five times a level, and the narrow classes took a launch each for a few thousand items)
-                    p.n_cls     = (uint32_t)std::min<size_t>(gps.size(), 7);
-                    for (uint32_t c = 0; c < p.n_cls; ++c)
-                        p.cls_gp[c] = (uint8_t)gps[c];
-                    p.cls_count = bp.cls_count;
-                    p.cls_base  = bp.cls_base;
-                    launch_pack();
-                    GN_HIP(hipGetLastError());
-                    p.n_cls = 0;
-                }
-                else
-                    for (size_t c = 0; c < gps.size() && c < 7; ++c)
-                    {
-                        p.pack_gp   = gps[c];
-                        p.count_in  = bp.cls_count + c;
-                        p.work_base = bp.cls_base + c;
-                        p.grab      = gn_sw().on_demand ? nullptr : s->d_hctr + 29 * NL + 2 + (size_t)lvl * 8 + c; // (a launch per width: a cursor per launch)
-                        launch_pack();
-                        GN_HIP(hipGetLastError());
-                    }
-                p.work_base = nullptr;
+                // ONE persistent launch walks the classes of the sorted list one after the other (a launch per width left the chip
+                // draining five times a level, and the narrow classes took a launch each for a few thousand items)
+                p.n_cls = (uint32_t)std::min<size_t>(gps.size(), 7);
+                for (uint32_t c = 0; c < p.n_cls; ++c)
+                    p.cls_gp[c] = (uint8_t)gps[c];
+                p.cls_count = bp.cls_count;
+                p.cls_base  = bp.cls_base;
+                launch_pack();
+                GN_HIP(hipGetLastError());
+                p.n_cls = 0;
                 p.grab      = gn_sw().on_demand ? nullptr : s->d_hctr + 29 * NL + 2 + (size_t)lvl * 8 + 7;
                 p.work_in   = s->d_hdefer2;
                 p.count_in  = s->d_hctr + NL + lvl;
@@ -2120,11 +1968,11 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
                 p.defer_count = s->d_hctr + 2 * NL + lvl;
                 switch (h)
                 {
-                    case 1: gn_hibf_launch_reg<1>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 2: gn_hibf_launch_reg<2>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 3: gn_hibf_launch_reg<3>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    case 4: gn_hibf_launch_reg<4>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
-                    default: gn_hibf_launch_reg<5>(p, level0, (uint32_t)f->n_cu, reg_bpc, st); break;
+                    case 1: gn_hibf_launch_reg<1>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 2: gn_hibf_launch_reg<2>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 3: gn_hibf_launch_reg<3>(p, level0, (uint32_t)f->n_cu, st); break;
+                    case 4: gn_hibf_launch_reg<4>(p, level0, (uint32_t)f->n_cu, st); break;
+                    default: gn_hibf_launch_reg<5>(p, level0, (uint32_t)f->n_cu, st); break;
                 }
                 GN_HIP(hipGetLastError());
                 p.work_in  = p.defer_out;

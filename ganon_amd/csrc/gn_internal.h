@@ -46,13 +46,7 @@ struct GnSwitches
     bool hibf_reg = false;        // no per-item register kernel (LDS-counter level kernel instead)
     bool hibf_pack = false;       // no packed-items kernel either
     bool hibf_one_pack = false;   // only the level's most common width takes the packed kernel (no sorting by width)
-    bool hibf_reread = false;     // A/B: lanes whose item is through read their last row again (as up to round 4)
-    bool hibf_nsort = false;      // a level's queue is sorted by row width only, not by (width, number of minimisers)
-    bool hibf_stage = false;      // the packed kernel fetches every hash from global memory (no staging in LDS)
-    bool hibf_persistent = false; // one launch per width class instead of one persistent launch per level
     bool hibf_dense_rows = false; // (read when an HIBF is created) rows of ceil(bins / 64) words on the device, as up to round 5: no padding to whole lines
-    bool hibf_fake_hashes = false; // TIMING EXPERIMENT ONLY (wrong results): the packed kernel loads one hash per item and derives the others
-    uint32_t hibf_bpc = 0;        // >0: workgroups per CU of the HIBF register kernels (0: what the occupancy query says)
     // device inflate
     bool     inflate_ahead = false; // no decode launched ahead of the step that needs it
     uint64_t hibf_pair_limit = 0; // >0: (read, user bin) pairs per round of a batch (tests make a batch take several rounds)
@@ -143,7 +137,7 @@ struct GnCountParams
     unsigned long long*       work_count_out;
     uint32_t                  max_blocks; // generic kernel: persistent grid size
     uint32_t                  max_blocks_fast; // fast kernel: persistent grid size
-    uint32_t                  nt_loads;        // fast kernel: non-temporal row loads
+    uint32_t                  emit_probe;      // fast kernel: GnSwitches::emit_probe (0 in the product)
     // generic kernel, candidate-driven select (split bins): bin -> CSR target, and (bins of the bin's target, capped
     // at 255) as u16 pairs in the layout of the LDS count area; nullptr = scan every target
     const uint32_t*           bin_tgt;

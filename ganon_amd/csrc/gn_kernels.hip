@@ -709,7 +709,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
     if (cand_ok) // kernel-uniform: the barrier below is reached by every wave of the block
     {
         uint32_t mine = 0;
-        if (use_cand && col_act && hsub == 0 && !(p.nt_loads & 32u)) // one lane per LDS column
+        if (use_cand && col_act && hsub == 0) // one lane per LDS column
         {
             typedef unsigned short gn_u16x2 __attribute__((ext_vector_type(2)));
             const gn_u16x2 tm1 = __builtin_bit_cast(gn_u16x2, (T - 1) * 0x00010001u);
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
             for (uint32_t sl = 0; sl < wpr; ++sl)
                 c_read += candcnt[rslot * wpr + sl];
         }
-        use_cand = use_cand && (c_read <= GN_CAND_LIMIT * wpr || (p.nt_loads & 8u)); // (bit 3: ablation -- never fall back)
+        use_cand = use_cand && c_read <= GN_CAND_LIMIT * wpr;
     }
 
     if (read < p.n_reads)
@@ -898,10 +898,10 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
         bool     overflow = false;
         if (use_cand)
         {
-            total    = (p.nt_loads & 16u) ? 0u : cand_rounds(false, nullptr);
+            total    = cand_rounds(false, nullptr);
             overflow = total > GN_STAGE_CAP;
         }
-        else if (n && !(p.nt_loads & 4u)) // (bit 2: ablation -- skip the select scan)
+        else if (n)
             for (uint32_t t0 = t_lo; t0 < t_hi; t0 += 4 * GN_WAVE)
             {
                 // four 64-target chunks per trip: their records are fetched together so that the (L2-resident) table
@@ -1246,7 +1246,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             {
                 typedef uint32_t gn_u32x4 __attribute__((ext_vector_type(4)));
                 const gn_u32x4* p4 = reinterpret_cast<const gn_u32x4*>(ptr);
-                const gn_u32x4  v  = p.nt_loads ? __builtin_nontemporal_load(p4) : *p4; // rows are read once: optional nt hint
+                const gn_u32x4  v  = *p4;
                 R.m[i][0] = v.x;
                 R.m[i][1] = v.y;
                 R.m[i][2] = v.z;
@@ -1654,7 +1654,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             // cutoffs near zero) keep the direct stores.
             const uint8_t* tabb   = reinterpret_cast<const uint8_t*>(rowtab);
             const bool     listed = total <= GN_FAST_LIST;
-            if (p.nt_loads & 128u) // (emit_probe: what the epilogue costs without listing or storing anything)
+            if (p.emit_probe & 128u) // (emit_probe: what the epilogue costs without listing or storing anything)
                 goto emitted;
             gn_match*      out    = p.matches + base + my_off;
             uint32_t       k      = 0;
@@ -1693,7 +1693,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                 }
             }
             gn_wave_lds_sync(); // the list is complete; the next unit refills the row table
-            if (listed && fits && !(p.nt_loads & 64u))
+            if (listed && fits && !(p.emit_probe & 64u))
             {
                 gn_match* seg = p.matches + base;
                 for (uint32_t m = (uint32_t)lane; m < total; m += GN_WAVE)

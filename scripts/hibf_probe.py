@@ -17,7 +17,7 @@ else:
 st = ganon_amd.HipStream(flt, n, wl.bases.size, n * 2)
 st.upload(wl.bases, wl.off, None)
 ref = None
-variants = [x for x in os.environ.get("VARIANTS", "|hibf_persistent|hibf_bpc=2|hibf_bpc=4|hibf_bpc=6|hibf_bpc=8").split("|")]
+variants = [x for x in os.environ.get("VARIANTS", "|hibf_one_pack|hibf_pack").split("|")]
 for v in variants:
     ganon_amd.set_ablation(v)
     ms, lv = [], None
