@@ -32,7 +32,8 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_get_stats", "gn_inflate_cuts", "gn_inflate_set_carry", "gn_stream_upload_text_device", "gn_stream_fastq_headers",
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
-               "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path"]
+               "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path",
+               "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -161,6 +162,10 @@ def load_library():
     L.gn_filter_emplace_split.argtypes = [vp, vp, u64, u32, u64]
     L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
+    L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
+    L.gn_sketches_free.argtypes = [vp]
+    L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
+    L.gn_sketches_union_table.argtypes = [vp, vp, u32, u32, u32, u32, vp]
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
@@ -490,6 +495,48 @@ def hashes_union(sets: Sequence[np.ndarray], device: int = 0, size_only: bool = 
     out = np.empty(int(sizes.sum()), dtype=np.uint64)
     _check(L.gn_hashes_union(device, ptrs, _p(sizes), n, _p(out), len(out), C.byref(nu)))
     return out[: nu.value].copy()
+
+
+SKETCH_M = 4096                # GN_SKETCH_M
+SKETCH_TABLE_MAX = 1 << 24     # GN_SKETCH_TABLE_MAX
+
+
+class HipSketches:
+    """gn_sketches: one HyperLogLog sketch (SKETCH_M one-byte registers) per hash set, resident on the device"""
+
+    def __init__(self, sets: Sequence[np.ndarray], device: int = 0):
+        sets = [np.ascontiguousarray(a, dtype=np.uint64) for a in sets]
+        self.n = len(sets)
+        ptrs = (C.c_void_p * max(self.n, 1))(*[a.ctypes.data for a in sets])
+        sizes = np.array([len(a) for a in sets], dtype=np.uint64)
+        self._h = C.c_void_p()
+        _check(load_library().gn_sketches_create(device, ptrs, _p(sizes), self.n, C.byref(self._h)))
+
+    def download(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """registers of sketches first .. first + n - 1, uint8 [n, SKETCH_M]"""
+        n = self.n - first if n is None else n
+        out = np.empty((n, SKETCH_M), dtype=np.uint8)
+        _check(load_library().gn_sketches_download(self._h, first, n, _p(out)))
+        return out
+
+    def union_table(self, order, width: int, j0: int = 0, j1: Optional[int] = None) -> np.ndarray:
+        """gn_sketches_union_table -> uint64 [j1 - j0, width]"""
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        j1 = len(order) if j1 is None else j1
+        out = np.empty((max(j1 - j0, 0), width), dtype=np.uint64)
+        _check(load_library().gn_sketches_union_table(self._h, _p(order), len(order), j0, j1, width, _p(out)))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            load_library().gn_sketches_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class HipFilter:

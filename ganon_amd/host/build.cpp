@@ -30,6 +30,7 @@
 #include "build_params.hpp"
 #include "hasher.hpp"
 #include "hibf_layout.hpp"
+#include "hibf_layout_sketch.hpp"
 #include "hostmem.hpp"
 #include "seq_io.hpp"
 #include "tunables.hpp"
@@ -76,6 +77,8 @@ struct Config // Config.hpp:10-27
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
     bool        tmax_given = false, filter_size_given = false;
+    std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates)
+    bool        layout_given = false;
 };
 
 bool validate(Config& c) // Config.hpp:29-107, same messages
@@ -87,6 +90,10 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
     };
     if (c.tmax_given && !c.hibf)
         return say("--tmax needs --hibf");
+    if (c.layout_given && !c.hibf)
+        return say("--layout needs --hibf");
+    if (c.layout_given && c.layout != "rule" && c.layout != "sketch")
+        return say("--layout has to be rule or sketch");
     if (c.hibf)
     {
         if (c.filter_size_given)
@@ -150,6 +157,8 @@ void print_config(const Config& c) // Config.hpp:110-133
               << "--quiet             " << c.quiet << '\n';
     if (c.hibf)
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
+    if (c.layout_given)
+        std::cerr << "--layout            " << c.layout << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -174,6 +183,8 @@ const char* kHelp =
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
     "                               Default: ceil(sqrt(targets) / 64) * 64\n"
+    "      --layout arg             [--hibf] how the tree is chosen: rule (from the targets' hash counts alone) or sketch (by size,\n"
+    "                               from HyperLogLog estimates of the unions of neighbouring targets). Default: rule\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -223,7 +234,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -284,6 +295,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.filter_size = d("--filter-size"), c.filter_size_given = true;
         if (vals.count("--tmax"))
             c.tmax = u("--tmax", ~0ull), c.tmax_given = true;
+        if (vals.count("--layout"))
+            c.layout = vals["--layout"], c.layout_given = true;
         c.hibf = vals.count("--hibf") && vals["--hibf"] != "false";
         if (vals.count("--mode"))
             c.mode = vals["--mode"];
@@ -678,9 +691,52 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
     return ok;
 }
 
+// --layout sketch: one HyperLogLog sketch per user bin on the device, the estimated unions of up to `width` neighbours in the sorted
+// order for every start (tiled over the starts: gn_sketches_union_table bounds a call), then the search of hibf_layout_sketch.hpp.
+bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, const std::vector<uint32_t>& user_target, const std::vector<uint64_t>& counts,
+                         uint32_t tmax, uint8_t h, gnhibf::Layout& lay, std::string& err)
+{
+    constexpr uint64_t    kTableBytes = 4ull << 30; // the most host memory the union table may take
+    const uint64_t        n = counts.size(), width = gnhibf::sketch_width(n, tmax);
+    std::vector<uint64_t> table;
+    if (width >= 2) // (width 1: one IBF, no union is asked for)
+    {
+        if (n * width > kTableBytes / 8)
+        {
+            err = "--layout sketch: the union estimates of " + std::to_string(n) + " user bins, " + std::to_string(width) +
+                  " neighbours each, take " + std::to_string(n * width * 8) + " bytes of host memory, more than " + std::to_string(kTableBytes) +
+                  "; use another --tmax (which sets how many neighbours a merged bin may hold) or --layout rule";
+            return false;
+        }
+        std::vector<const uint64_t*> sets(n);
+        for (uint64_t u = 0; u < n; ++u)
+            sets[u] = targets[user_target[u]].hashes.data();
+        gn_sketches* sk = nullptr;
+        if (gn_sketches_create(c.device, sets.data(), counts.data(), (uint32_t)n, &sk) != GN_OK)
+        {
+            err = gn_last_error();
+            return false;
+        }
+        const std::vector<uint32_t> order = gnhibf::sketch_order(counts);
+        table.resize(n * width);
+        const uint64_t per = std::max<uint64_t>(1, GN_SKETCH_TABLE_MAX / width);
+        for (uint64_t j = 0; j < n; j += per)
+            if (gn_sketches_union_table(sk, order.data(), (uint32_t)n, (uint32_t)j, (uint32_t)std::min(n, j + per), (uint32_t)width,
+                                        table.data() + j * width) != GN_OK)
+            {
+                err = gn_last_error();
+                gn_sketches_free(sk);
+                return false;
+            }
+        gn_sketches_free(sk);
+    }
+    lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, [&](uint64_t j, uint64_t l) { return table[j * width + l - 1]; });
+    return true;
+}
+
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
 {
-    Lap            uniting, filling, writing;
+    Lap            uniting, laying, filling, writing;
     const uint8_t  h = c.hash_functions == 0 ? 4 : c.hash_functions; // (what `ganon build` passes to raptor, config.py:138-145)
     auto           fail = [](const std::string& m) {
         std::cerr << m << std::endl;
@@ -731,7 +787,17 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     uint64_t       tmax   = c.tmax;
     if (!c.tmax_given)
         tmax = (uint64_t)std::ceil(std::sqrt((double)n_user) / 64.0) * 64; // build_update.py:487
-    const gnhibf::Layout lay = gnhibf::lay_out(counts, (uint32_t)tmax);
+    laying.start();
+    gnhibf::Layout lay;
+    if (c.layout == "sketch")
+    {
+        std::string err;
+        if (!lay_out_by_sketches(c, targets, user_target, counts, (uint32_t)tmax, h, lay, err))
+            return fail(err);
+    }
+    else
+        lay = gnhibf::lay_out(counts, (uint32_t)tmax);
+    laying.stop();
 
     // rows per IBF: the largest need of its runs; a merged bin holds the union of the sets below it
     std::vector<HibfShape> ibfs(lay.ibfs.size());
@@ -772,6 +838,7 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
                   << "tmax           " << tmax << '\n'
                   << "ibfs           " << ibfs.size() << '\n'
                   << "levels         " << lay.levels << '\n'
+                  << "layout         " << c.layout << '\n'
                   << "hash_functions " << unsigned(h) << '\n'
                   << "max_fp         " << c.max_fp << '\n';
         std::cerr << "Filter size: " << device_bits << " Bits (" << device_bits / static_cast<double>(8388608u) << " Megabytes)" << std::endl;
@@ -877,7 +944,10 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         std::cerr << std::fixed << std::setprecision(2) << " - filter size: " << device_bits / static_cast<double>(8388608u) << "MB" << std::endl;
         // (one line a caller can parse: where the time went)
         std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
-                  << " write " << writing.seconds() << std::endl;
+                  << " write " << writing.seconds();
+        if (c.layout == "sketch") // (part of `union`: sketches, union table and search)
+            std::cerr << " layout " << laying.seconds();
+        std::cerr << std::endl;
     }
     return true;
 }

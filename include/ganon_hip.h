@@ -423,6 +423,40 @@ int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* siz
 int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
                            uint32_t depth);
 
+/* `ganon-build --hibf --layout sketch`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
+ * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
+ * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.
+ *
+ * A sketch is GN_SKETCH_M = 4096 registers of one byte.  For a hash h of the set:
+ *     x = h;  x ^= x >> 33;  x *= 0xff51afd7ed558ccd;  x ^= x >> 33;  x *= 0xc4ceb9fe1a85ec53;  x ^= x >> 33;     (64-bit, wrapping:
+ *                                                     murmur3's finaliser -- minimiser hashes are not uniform)
+ *     index = x >> 52                                 (the top 12 bits)
+ *     rest  = x & (2^52 - 1);  rank = 52 when rest == 0, else (leading zeros of rest as a 52-bit number) + 1     (1 .. 52)
+ *     register[index] = max(register[index], rank)
+ * An empty set is all zeros.  Register r of sketch i is byte i * 4096 + r of what gn_sketches_download returns.
+ *   gn_sketches_create       sets[i][0 .. sizes[i]) in host memory (order and repeats inside a set do not matter), one sketch each,
+ *                            kept on `device`
+ *   gn_sketches_download     registers of sketches first .. first + n - 1 (tests)
+ *   gn_sketches_union_table  `order` = n sketch indices (each below the handle's number of sketches; repeats allowed).  For every
+ *                            start j in [j0, j1) and every l in [1, min(width, n - j)], out[(j - j0) * width + l - 1] = the largest of
+ *                            E(j, 1) .. E(j, l), where E(j, l) estimates the union of sketches order[j .. j + l); entries with
+ *                            l > n - j are 0.  So every row is non-decreasing up to its end.  At most GN_SKETCH_TABLE_MAX entries
+ *                            ((j1 - j0) * width) in one call, GN_ERANGE beyond: rows are independent, tile over the starts.
+ * E from the union's registers U[r] = max over the sketches of register r, with m = 4096:
+ *     Z = number of r with U[r] == 0;  S = sum over r of 2^(52 - U[r]) as an integer (below 2^64 unless Z == m)
+ *     Z == m: E = 0.  Otherwise raw = num / (double)S, both the conversion and the division rounded to nearest, with
+ *     num = alpha * 2^76 (= alpha * m^2 * 2^52), alpha = 0.7213 / (1.0 + 1.079 / 4096.0) in double arithmetic;
+ *     value = raw <= 10240.0 (2.5 m) and Z > 0 ? 4096.0 * log(4096.0 / (double)Z) : raw
+ *     E = value rounded to the nearest integer, ties to even, as uint64
+ * (the logarithms come from a table of 4097 doubles the host computes with the C library's log(); the device calls none). */
+#define GN_SKETCH_M 4096u
+#define GN_SKETCH_TABLE_MAX (1ull << 24)
+typedef struct gn_sketches gn_sketches;
+int gn_sketches_create(int device, const uint64_t* const* sets, const uint64_t* sizes, uint32_t n_sets, gn_sketches** out);
+int gn_sketches_free(gn_sketches* s);
+int gn_sketches_download(gn_sketches* s, uint32_t first, uint32_t n, uint8_t* out);
+int gn_sketches_union_table(gn_sketches* s, const uint32_t* order, uint32_t n, uint32_t j0, uint32_t j1, uint32_t width, uint64_t* out);
+
 /* Parity / debugging taps (tests only): minimiser hashes of the resident batch in emission order
  * (hash_off[n_reads+1]; hashes[cap]) and dense per-bin counts of reads [read_begin, read_end)
  * (flat IBF: uint16[bins] per read == counting_agent::bulk_count; HIBF: uint16[n_user_bins] per read

@@ -3,8 +3,13 @@ written to a tmpfs, then `ganon-build` runs start to finish (parse -> device min
 insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_files=512] [len=4000000] [threads=16] [dir=/dev/shm]
   --hibf          the same FASTA built flat AND as HIBF (`ganon-build --hibf`), alternating, one run each to warm up and then the median
                   of --runs (5) each, both at --max-fp (0.05) and --hash-functions (4); the HIBF time split into hash / union / emplace /
-                  write; --tmax N is passed on.  Prints one JSON object with "flat" and "hibf"."""
+                  write; --tmax N is passed on.  Prints one JSON object with "flat" and "hibf".
+  --layout NAME   [--hibf] passed on as `--layout NAME` (rule | sketch).  A comma list (rule,sketch) builds every layout in turn in
+                  each round, alternating, and prints "hibf" as one object per layout; a sketch build also reports layout_s, the
+                  part of union_s that went into sketches, union table and search.
+  --lognormal S   file i has len * exp(S * z_i) bases, z_i standard normal (seeded): `len` is the median, not every file's length"""
 import json
+import math
 import os
 import re
 import subprocess
@@ -14,7 +19,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": ""}
 pos, hibf, argv = [], False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -32,9 +37,14 @@ os.makedirs(d, exist_ok=True)
 rng = np.random.default_rng(1)
 lut = np.frombuffer(b"ACGT", dtype=np.uint8)
 cols = 70
-rows = (L + cols - 1) // cols
+lengths = [L] * n_files
+if opts["--lognormal"]:
+    lengths = [max(1000, int(L * math.exp(float(opts["--lognormal"]) * z))) for z in np.random.default_rng(2).standard_normal(n_files)]
+total_bases = sum(lengths)
 with open(os.path.join(d, "in.tsv"), "w") as tsv:
     for i in range(n_files):
+        L = lengths[i]
+        rows = (L + cols - 1) // cols
         body = np.full((rows, cols + 1), ord("\n"), dtype=np.uint8)
         body[:, :cols] = lut[rng.integers(0, 4, size=(rows, cols), dtype=np.uint8)]
         f = os.path.join(d, f"g{i}.fna")
@@ -42,7 +52,10 @@ with open(os.path.join(d, "in.tsv"), "w") as tsv:
             o.write(f">genome{i} synthetic\n".encode())
             o.write(body.tobytes()[: L + L // cols + 1])
         tsv.write(f"{f}\tT{i}\n")
-out = {"files": n_files, "bases_per_file": L, "total_gbp": round(n_files * L / 1e9, 3), "threads": threads}
+L = int(pos[1]) if len(pos) > 1 else 4_000_000
+out = {"files": n_files, "bases_per_file": L, "total_gbp": round(total_bases / 1e9, 3), "threads": threads}
+if opts["--lognormal"]:
+    out["lognormal_sigma"], out["largest_file"], out["smallest_file"] = float(opts["--lognormal"]), max(lengths), min(lengths)
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
 
 
@@ -69,20 +82,23 @@ def flat_run(max_fp="0.05", extra=()):
     if p.returncode == 0:
         res["ibf_bytes"] = os.path.getsize(os.path.join(d, "db.ibf"))
         res["ibf_gib"] = round(res["ibf_bytes"] / 2**30, 3)
-        res["mbp_per_s"] = round(n_files * L / 1e6 / res.get("total_s", res["wall_s"]), 1)
+        res["mbp_per_s"] = round(total_bases / 1e6 / res.get("total_s", res["wall_s"]), 1)
     return res
 
 
-def hibf_run():
+def hibf_run(layout=""):
     res = {}
     t0 = time.time()
     cmd = [exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.hibf"), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
-           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else [])
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
     m = re.search(r" - seconds: hash ([0-9.eE+-]+) union ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
     if m:
         res["hash_s"], res["union_s"], res["emplace_s"], res["write_s"] = (float(x) for x in m.groups())
+    m = re.search(r" write [0-9.eE+-]+ layout ([0-9.eE+-]+)", p.stderr)
+    if m:
+        res["layout_s"] = float(m.group(1))
     m = re.search(r"ganon-build       start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)", p.stderr)
     if m:
         res["total_s"] = float(m.group(1))
@@ -90,7 +106,7 @@ def hibf_run():
     res["summary"] = m.group(0).strip() if m else p.stderr[-300:]
     if p.returncode == 0:
         res["hibf_bytes"] = os.path.getsize(os.path.join(d, "db.hibf"))
-        res["mbp_per_s"] = round(n_files * L / 1e6 / res.get("total_s", res["wall_s"]), 1)
+        res["mbp_per_s"] = round(total_bases / 1e6 / res.get("total_s", res["wall_s"]), 1)
     return res
 
 
@@ -108,13 +124,18 @@ if not hibf:
     out.update(flat_run())
 else:
     flat_extra = ["-s", opts["--hash-functions"]]
-    flat_run(opts["--max-fp"], flat_extra), hibf_run()  # one run each to warm up
-    flats, hibfs = [], []
+    layouts = opts["--layout"].split(",")
+    flat_run(opts["--max-fp"], flat_extra)  # one run each to warm up
+    for name in layouts:
+        hibf_run(name)
+    flats, hibfs = [], {name: [] for name in layouts}
     for _ in range(int(opts["--runs"])):
         flats.append(flat_run(opts["--max-fp"], flat_extra))
-        hibfs.append(hibf_run())
+        for name in layouts:
+            hibfs[name].append(hibf_run(name))
     out["max_fp"], out["hash_functions"], out["runs"] = float(opts["--max-fp"]), int(opts["--hash-functions"]), int(opts["--runs"])
-    out["flat"], out["hibf"] = median_of(flats), median_of(hibfs)
+    out["flat"] = median_of(flats)
+    out["hibf"] = median_of(hibfs[layouts[0]]) if len(layouts) == 1 else {name: median_of(hibfs[name]) for name in layouts}
 for f in os.listdir(d):
     os.remove(os.path.join(d, f))
 os.rmdir(d)
