@@ -2,6 +2,8 @@
 //   gn_sketches_create       one sketch of m = 4096 one-byte registers per ascending hash set, resident on the device
 //   gn_sketches_union_table  for every start j and every length l <= width the estimated cardinality of the union of the sketches
 //                            order[j .. j + l) -- the question a layout search asks n * width times
+//   gn_sketches_pair_table   for every two sketches of a list the estimated cardinality of their union -- what `--layout similarity`
+//                            orders the user bins of an interval by
 // The definitions (mixer, register index, rank, estimate) are stated bit for bit in include/ganon_hip.h.
 // No counterpart in the reference's own sources: `ganon build --filter-type hibf` runs `raptor layout`, which is chopper
 // (/root/reference/src/ganon/build_update.py:411-518).  Integer work but for one division per table entry.
@@ -98,6 +100,15 @@ __global__ __launch_bounds__(256) void gn_sketch_pack_kernel(const uint32_t* __r
     *out            = gn_bytemax(*out, v.x | (v.y << 8) | (v.z << 16) | (v.w << 24));
 }
 
+// E of include/ganon_hip.h from the sums over a union's registers
+__device__ __forceinline__ unsigned long long gn_sketch_estimate(unsigned long long S, uint32_t Z, double num, const double* __restrict__ small)
+{
+    if (Z == GN_SKETCH_M) // (S is 2^64, the estimate 0)
+        return 0;
+    const double raw = __ddiv_rn(num, __ull2double_rn(S));
+    return __double2ull_rn(raw <= 2.5 * GN_SKETCH_M && Z > 0 ? small[Z] : raw);
+}
+
 // One wave per start j.  The running union -- 4 KiB, 16 dwords a lane -- stays in registers; a step loads the next sketch with
 // four coalesced 16-byte loads a lane (issued a step ahead), takes the byte-wise maximum, sums S = sum 2^(52 - reg) and Z = zero
 // registers over the lane's 64 bytes as integers and reduces both across the wave; lane 0 turns (S, Z) into the estimate.
@@ -157,18 +168,84 @@ __global__ __launch_bounds__(256) void gn_sketch_union_kernel(const uint8_t* __r
         }
         if (lane == 0)
         {
-            unsigned long long est = 0;
-            if (Z != GN_SKETCH_M) // (Z == m: S is 2^64, the estimate 0)
-            {
-                const double raw = __ddiv_rn(num, __ull2double_rn(S));
-                est              = __double2ull_rn(raw <= 2.5 * GN_SKETCH_M && Z > 0 ? small[Z] : raw);
-            }
-            best       = est > best ? est : best;
+            const unsigned long long est = gn_sketch_estimate(S, Z, num, small);
+            best                         = est > best ? est : best;
             row[l - 1] = best;
         }
     }
     for (uint32_t l = steps + lane; l < width; l += 64) // past the last sketch
         row[l] = 0;
+}
+
+#define GN_PAIR_TILE 8u // sketches a side of a block's tile; two rows a wave
+
+// One block per tile of GN_PAIR_TILE x GN_PAIR_TILE pairs (a, b) of positions of idx, a <= b: the grid is the tiles on and above
+// the diagonal, block t = x * (x + 1) / 2 + y the tile of column tile x and row tile y <= x.  The tile's columns lie in LDS (32 KiB), read by all four waves; a wave holds one of its two rows in registers -- 4 KiB, 16
+// dwords a lane, laid out as in the union kernel -- and walks the columns: four conflict-free 16-byte LDS reads a lane, then per
+// register one byte maximum, one shift of 2^52 and one 64-bit add (the union kernel also keeps the running union and pays for that
+// with a byte-wise maximum in dword arithmetic).  S and Z are reduced across the wave as integers, lane 0 makes the division and
+// stores out[a * m + b] and out[b * m + a].  Positions at or beyond m (the last tile) are neither loaded nor paired.
+__global__ __launch_bounds__(256) void gn_sketch_pair_kernel(const uint8_t* __restrict__ regs, const uint32_t* __restrict__ idx, uint32_t m, double num,
+                                                             const double* __restrict__ small, unsigned long long* __restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint4 cols[GN_PAIR_TILE * (GN_SKETCH_M / 16)];
+    const uint32_t t = blockIdx.x;
+    uint32_t       x = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f); // t < 2^18: off by one at the most, set right below
+    while (x * (x + 1) / 2 > t)
+        --x;
+    while ((x + 1) * (x + 2) / 2 <= t)
+        ++x;
+    const uint32_t a0 = (t - x * (x + 1) / 2) * GN_PAIR_TILE, b0 = x * GN_PAIR_TILE; // (x < tiles, as t < tiles * (tiles + 1) / 2)
+    const uint32_t n_cols = m - b0 < GN_PAIR_TILE ? m - b0 : GN_PAIR_TILE;
+    for (uint32_t c = 0; c < n_cols; ++c)
+        cols[c * 256 + threadIdx.x] = ((const uint4*)(regs + (uint64_t)idx[b0 + c] * GN_SKETCH_M))[threadIdx.x];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (uint32_t r = 0; r < 2; ++r)
+    {
+        const uint32_t a = a0 + wave * 2 + r;
+        if (a >= m)
+            break;
+        uint4 row[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+            row[i] = ((const uint4*)(regs + (uint64_t)idx[a] * GN_SKETCH_M))[i * 64 + lane];
+        for (uint32_t c = a > b0 ? a - b0 : 0; c < n_cols; ++c) // (a > b0 on the diagonal tile only: pairs with a <= b)
+        {
+            unsigned long long S = 0;
+            uint32_t           Z = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i)
+            {
+                const uint4    v    = cols[c * 256 + i * 64 + lane];
+                const uint32_t x[4] = { row[i].x, row[i].y, row[i].z, row[i].w }, y[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                {
+                    Z += 4u - (uint32_t)__popc(((x[k] | y[k]) + 0x7F7F7F7Fu) & 0x80808080u); // the maximum is 0 where both bytes are
+#pragma unroll
+                    for (uint32_t b = 0; b < 32; b += 8)
+                    {
+                        const uint32_t p = (x[k] >> b) & 0xFFu, q = (y[k] >> b) & 0xFFu;
+                        S += (1ULL << 52) >> (p > q ? p : q);
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t off = 32; off; off >>= 1)
+            {
+                S += __shfl_xor(S, off);
+                Z += __shfl_xor(Z, off);
+            }
+            if (lane == 0)
+            {
+                const unsigned long long est = gn_sketch_estimate(S, Z, num, small);
+                const uint32_t           b   = b0 + c;
+                out[(uint64_t)a * m + b]     = est;
+                out[(uint64_t)b * m + a]     = est;
+            }
+        }
+    }
 }
 
 extern "C" int gn_sketches_free(gn_sketches* s)
@@ -337,6 +414,33 @@ extern "C" int gn_sketches_union_table(gn_sketches* s, const uint32_t* order, ui
     GN_HIP(d_out.alloc(entries));
     hipLaunchKernelGGL(gn_sketch_union_kernel, dim3((j1 - j0 + 3) / 4), dim3(256), 0, nullptr, s->d_regs, d_order, n, j0, j1, width, s->num, s->d_small,
                        d_out);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipMemcpy(out, d_out, entries * 8, hipMemcpyDeviceToHost));
+    return GN_OK;
+}
+
+extern "C" int gn_sketches_pair_table(gn_sketches* s, const uint32_t* idx, uint32_t m, uint64_t* out)
+{
+    if (!s || (m && !idx))
+        return gn_fail(GN_EINVAL, "gn_sketches_pair_table: null argument");
+    const uint64_t entries = (uint64_t)m * m;
+    if (entries > GN_SKETCH_TABLE_MAX)
+        return gn_fail(GN_ERANGE, "gn_sketches_pair_table: %llu entries in one call, at most %llu", (unsigned long long)entries,
+                       (unsigned long long)GN_SKETCH_TABLE_MAX);
+    if (m == 0)
+        return GN_OK;
+    if (!out)
+        return gn_fail(GN_EINVAL, "gn_sketches_pair_table: null argument");
+    for (uint32_t i = 0; i < m; ++i) // every sketch a block can reach is checked here
+        if (idx[i] >= s->n)
+            return gn_fail(GN_EINVAL, "gn_sketches_pair_table: idx[%u] = %u of %u sketches", i, idx[i], s->n);
+    GN_HIP(hipSetDevice(s->device));
+    GnDev<uint32_t>           d_idx;
+    GnDev<unsigned long long> d_out;
+    GN_HIP(d_idx.upload(idx, m));
+    GN_HIP(d_out.alloc(entries));
+    const uint32_t tiles = (m + GN_PAIR_TILE - 1) / GN_PAIR_TILE;
+    hipLaunchKernelGGL(gn_sketch_pair_kernel, dim3(tiles * (tiles + 1) / 2), dim3(256), 0, nullptr, s->d_regs, d_idx, m, s->num, s->d_small, d_out);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpy(out, d_out, entries * 8, hipMemcpyDeviceToHost));
     return GN_OK;

@@ -33,7 +33,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path",
-               "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table"]
+               "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -166,6 +166,7 @@ def load_library():
     L.gn_sketches_free.argtypes = [vp]
     L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
     L.gn_sketches_union_table.argtypes = [vp, vp, u32, u32, u32, u32, vp]
+    L.gn_sketches_pair_table.argtypes = [vp, vp, u32, vp]
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
@@ -525,6 +526,13 @@ class HipSketches:
         j1 = len(order) if j1 is None else j1
         out = np.empty((max(j1 - j0, 0), width), dtype=np.uint64)
         _check(load_library().gn_sketches_union_table(self._h, _p(order), len(order), j0, j1, width, _p(out)))
+        return out
+
+    def pair_table(self, idx) -> np.ndarray:
+        """gn_sketches_pair_table -> uint64 [m, m]: the estimated union of sketches idx[a] and idx[b]"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        out = np.empty((len(idx), len(idx)), dtype=np.uint64)
+        _check(load_library().gn_sketches_pair_table(self._h, _p(idx), len(idx), _p(out)))
         return out
 
     def free(self) -> None:

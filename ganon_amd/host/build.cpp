@@ -30,6 +30,7 @@
 #include "build_params.hpp"
 #include "hasher.hpp"
 #include "hibf_layout.hpp"
+#include "hibf_layout_similarity.hpp"
 #include "hibf_layout_sketch.hpp"
 #include "hostmem.hpp"
 #include "seq_io.hpp"
@@ -48,6 +49,7 @@
 #include <iomanip>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <sstream>
@@ -77,7 +79,8 @@ struct Config // Config.hpp:10-27
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
     bool        tmax_given = false, filter_size_given = false;
-    std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates)
+    std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates,
+                                 //  similarity = hibf_layout_similarity.hpp: sketch over an order that groups related targets)
     bool        layout_given = false;
 };
 
@@ -92,8 +95,8 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--tmax needs --hibf");
     if (c.layout_given && !c.hibf)
         return say("--layout needs --hibf");
-    if (c.layout_given && c.layout != "rule" && c.layout != "sketch")
-        return say("--layout has to be rule or sketch");
+    if (c.layout_given && c.layout != "rule" && c.layout != "sketch" && c.layout != "similarity")
+        return say("--layout has to be rule, sketch or similarity");
     if (c.hibf)
     {
         if (c.filter_size_given)
@@ -183,8 +186,10 @@ const char* kHelp =
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
     "                               Default: ceil(sqrt(targets) / 64) * 64\n"
-    "      --layout arg             [--hibf] how the tree is chosen: rule (from the targets' hash counts alone) or sketch (by size,\n"
-    "                               from HyperLogLog estimates of the unions of neighbouring targets). Default: rule\n"
+    "      --layout arg             [--hibf] how the tree is chosen: rule (from the targets' hash counts alone), sketch (by size,\n"
+    "                               from HyperLogLog estimates of the unions of neighbouring targets) or similarity (as sketch,\n"
+    "                               with targets of comparable size reordered so that related ones are neighbours; the\n"
+    "                               smaller of the two trees is kept). Default: rule\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -691,47 +696,94 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
     return ok;
 }
 
-// --layout sketch: one HyperLogLog sketch per user bin on the device, the estimated unions of up to `width` neighbours in the sorted
-// order for every start (tiled over the starts: gn_sketches_union_table bounds a call), then the search of hibf_layout_sketch.hpp.
-bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, const std::vector<uint32_t>& user_target, const std::vector<uint64_t>& counts,
-                         uint32_t tmax, uint8_t h, gnhibf::Layout& lay, std::string& err)
+// --layout sketch | similarity: one HyperLogLog sketch per user bin on the device, the estimated unions of up to `width` neighbours
+// in an order for every start (tiled over the starts: gn_sketches_union_table bounds a call), then the search of
+// hibf_layout_sketch.hpp.  similarity (hibf_layout_similarity.hpp) asks for that table twice, one after the other -- the size order's
+// and the similarity order's -- and in between for one gn_sketches_pair_table per interval of the size order.
+struct SketchLaps // seconds inside the `layout` lap: the rest of it is the host's ordering and searches
 {
-    constexpr uint64_t    kTableBytes = 4ull << 30; // the most host memory the union table may take
-    const uint64_t        n = counts.size(), width = gnhibf::sketch_width(n, tmax);
-    std::vector<uint64_t> table;
+    double sketches = 0, tables = 0, pairs = 0;
+};
+
+bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, const std::vector<uint32_t>& user_target, const std::vector<uint64_t>& counts,
+                         uint32_t tmax, uint8_t h, gnhibf::Layout& lay, SketchLaps& laps, std::string& err)
+{
+    constexpr uint64_t kTableBytes = 4ull << 30; // the most host memory a union table may take
+    const uint64_t     n = counts.size(), width = gnhibf::sketch_width(n, tmax);
+    const bool         similarity = c.layout == "similarity";
+    gn_sketches*       sk = nullptr;
+    auto               since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
     if (width >= 2) // (width 1: one IBF, no union is asked for)
     {
         if (n * width > kTableBytes / 8)
         {
-            err = "--layout sketch: the union estimates of " + std::to_string(n) + " user bins, " + std::to_string(width) +
+            err = "--layout " + c.layout + ": the union estimates of " + std::to_string(n) + " user bins, " + std::to_string(width) +
                   " neighbours each, take " + std::to_string(n * width * 8) + " bytes of host memory, more than " + std::to_string(kTableBytes) +
                   "; use another --tmax (which sets how many neighbours a merged bin may hold) or --layout rule";
             return false;
         }
+        const auto                   t0 = std::chrono::steady_clock::now();
         std::vector<const uint64_t*> sets(n);
         for (uint64_t u = 0; u < n; ++u)
             sets[u] = targets[user_target[u]].hashes.data();
-        gn_sketches* sk = nullptr;
         if (gn_sketches_create(c.device, sets.data(), counts.data(), (uint32_t)n, &sk) != GN_OK)
         {
             err = gn_last_error();
             return false;
         }
-        const std::vector<uint32_t> order = gnhibf::sketch_order(counts);
-        table.resize(n * width);
+        laps.sketches = since(t0);
+    }
+    struct DeviceError // a device call inside a callback failed: the search ends there
+    {
+        std::string what;
+    };
+    // the union table of an order, held by the estimate that reads it
+    const gnhibf::OrderUnions unions = [&](const std::vector<uint32_t>& order) -> gnhibf::UnionEstimate {
+        const auto t0    = std::chrono::steady_clock::now();
+        auto       table = std::make_shared<std::vector<uint64_t>>(n * width, 0);
         const uint64_t per = std::max<uint64_t>(1, GN_SKETCH_TABLE_MAX / width);
         for (uint64_t j = 0; j < n; j += per)
             if (gn_sketches_union_table(sk, order.data(), (uint32_t)n, (uint32_t)j, (uint32_t)std::min(n, j + per), (uint32_t)width,
-                                        table.data() + j * width) != GN_OK)
-            {
-                err = gn_last_error();
-                gn_sketches_free(sk);
-                return false;
-            }
-        gn_sketches_free(sk);
+                                        table->data() + j * width) != GN_OK)
+                throw DeviceError{ gn_last_error() };
+        laps.tables += since(t0);
+        return [table, width](uint64_t j, uint64_t l) { return (*table)[j * width + l - 1]; };
+    };
+    const std::vector<uint32_t> size_order = gnhibf::sketch_order(counts);
+    // the pair table of one interval of the size order, held likewise
+    const gnhibf::IntervalPairs pairs = [&](uint64_t a, uint64_t b) -> gnhibf::PairEstimate {
+        const auto     t0    = std::chrono::steady_clock::now();
+        const uint64_t m     = b - a;
+        auto           table = std::make_shared<std::vector<uint64_t>>(m * m, 0);
+        if (gn_sketches_pair_table(sk, size_order.data() + a, (uint32_t)m, table->data()) != GN_OK)
+            throw DeviceError{ gn_last_error() };
+        laps.pairs += since(t0);
+        return [table, m](uint64_t p, uint64_t q) { return (*table)[p * m + q]; };
+    };
+    bool ok = true;
+    try
+    {
+        if (similarity)
+        {
+            gnhibf::SimilarityLayout got = gnhibf::lay_out_similarity(counts, tmax, c.max_fp, h, unions, pairs);
+            lay                          = std::move(got.layout);
+            if (c.verbose)
+                std::cerr << "layout similarity: " << got.intervals << " intervals, " << got.moved << " of " << n << " user bins moved, kept " << got.kept
+                          << std::endl;
+        }
+        else if (width >= 2)
+            lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, unions(size_order));
+        else
+            lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, [](uint64_t, uint64_t) -> uint64_t { return 0; });
     }
-    lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, [&](uint64_t j, uint64_t l) { return table[j * width + l - 1]; });
-    return true;
+    catch (const DeviceError& e)
+    {
+        err = e.what;
+        ok  = false;
+    }
+    if (sk)
+        gn_sketches_free(sk);
+    return ok;
 }
 
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
@@ -789,10 +841,11 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         tmax = (uint64_t)std::ceil(std::sqrt((double)n_user) / 64.0) * 64; // build_update.py:487
     laying.start();
     gnhibf::Layout lay;
-    if (c.layout == "sketch")
+    SketchLaps     sketch_laps;
+    if (c.layout == "sketch" || c.layout == "similarity")
     {
         std::string err;
-        if (!lay_out_by_sketches(c, targets, user_target, counts, (uint32_t)tmax, h, lay, err))
+        if (!lay_out_by_sketches(c, targets, user_target, counts, (uint32_t)tmax, h, lay, sketch_laps, err))
             return fail(err);
     }
     else
@@ -945,9 +998,12 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         // (one line a caller can parse: where the time went)
         std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
                   << " write " << writing.seconds();
-        if (c.layout == "sketch") // (part of `union`: sketches, union table and search)
+        if (c.layout == "sketch" || c.layout == "similarity") // (part of `union`: sketches, union table and search)
             std::cerr << " layout " << laying.seconds();
         std::cerr << std::endl;
+        if (c.layout == "similarity") // (where the layout lap went; host = the ordering and the searches)
+            std::cerr << " - layout seconds: sketches " << sketch_laps.sketches << " tables " << sketch_laps.tables << " pairs " << sketch_laps.pairs << " host "
+                      << laying.seconds() - sketch_laps.sketches - sketch_laps.tables - sketch_laps.pairs << std::endl;
     }
     return true;
 }

@@ -2,7 +2,8 @@
 // by size.  Host only: no device, no I/O.  The caller says how large the union of neighbouring user bins is -- the builder from
 // HyperLogLog sketches (gn_sketches_union_table), a test with exact sums -- and the search balances split and merged bins on it, as
 // chopper does for `raptor layout` (/root/reference/src/ganon/build_update.py:411-518).  Not taken over from chopper: the weight of
-// the query cost, the rearrangement of user bins by similarity, its layout files.
+// the query cost, its layout files.  (Its rearrangement of user bins by similarity is `--layout similarity`, hibf_layout_similarity.hpp:
+// the same search over another order.)
 //
 // User bins are sorted once by (count descending, index ascending); every IBF's members are a contiguous slice [a, b) of that order.
 // An IBF has a level budget Lb: the root's is levels_for(n, tmax), a child's its parent's minus one; cap = tmax^(Lb - 1) is the most
@@ -230,18 +231,52 @@ inline std::vector<uint32_t> sketch_order(const std::vector<uint64_t>& counts)
     return order;
 }
 
-// counts[u] = distinct hashes of user bin u (all > 0), tmax >= 2, max_fp and hash_functions as the IBFs will be sized with.
-// No user bin: an empty layout.
-inline Layout lay_out_sketch(const std::vector<uint64_t>& counts, uint32_t tmax, double max_fp, uint8_t hash_functions, const UnionEstimate& estimate)
+// The search over a given order -- any permutation of the user bins, `estimate` speaking of its positions -- with no comparison
+// against the rule: the tree and, in *bits, what the estimates say it takes.  counts, tmax, max_fp, hash_functions as below.
+inline Layout lay_out_order(const std::vector<uint64_t>& counts, const std::vector<uint32_t>& order, uint32_t tmax, double max_fp, uint8_t hash_functions,
+                            const UnionEstimate& estimate, uint64_t* bits)
 {
     Layout out;
+    *bits = 0;
+    if (counts.empty() || tmax < 2)
+        return out;
+    const detail::SketchSearch search{ counts, order, tmax, max_fp, hash_functions, estimate };
+    search.lay(out, 0, counts.size(), levels_for(counts.size(), tmax), -1, 0, 0);
+    *bits = search.bits(out);
+    return out;
+}
+
+// lay_out_sketch below, which also says what it kept: *bits = the estimated bits of the tree returned, *kept_rule = it is the rule's
+inline Layout lay_out_sketch_costed(const std::vector<uint64_t>& counts, uint32_t tmax, double max_fp, uint8_t hash_functions, const UnionEstimate& estimate,
+                                    uint64_t* bits, bool* kept_rule)
+{
+    Layout out;
+    *bits      = 0;
+    *kept_rule = false;
     if (counts.empty() || tmax < 2)
         return out;
     const std::vector<uint32_t> order = sketch_order(counts);
     const detail::SketchSearch  search{ counts, order, tmax, max_fp, hash_functions, estimate };
     search.lay(out, 0, counts.size(), levels_for(counts.size(), tmax), -1, 0, 0);
-    Layout rule = lay_out(counts, tmax);
-    return search.bits(rule) < search.bits(out) ? rule : out;
+    *bits = search.bits(out);
+    Layout                     rule      = lay_out(counts, tmax);
+    const uint64_t             rule_bits = search.bits(rule);
+    if (rule_bits < *bits)
+    {
+        *bits      = rule_bits;
+        *kept_rule = true;
+        return rule;
+    }
+    return out;
+}
+
+// counts[u] = distinct hashes of user bin u (all > 0), tmax >= 2, max_fp and hash_functions as the IBFs will be sized with.
+// No user bin: an empty layout.
+inline Layout lay_out_sketch(const std::vector<uint64_t>& counts, uint32_t tmax, double max_fp, uint8_t hash_functions, const UnionEstimate& estimate)
+{
+    uint64_t bits      = 0;
+    bool     kept_rule = false;
+    return lay_out_sketch_costed(counts, tmax, max_fp, hash_functions, estimate, &bits, &kept_rule);
 }
 
 } // namespace gnhibf

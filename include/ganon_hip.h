@@ -423,7 +423,7 @@ int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* siz
 int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
                            uint32_t depth);
 
-/* `ganon-build --hibf --layout sketch`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
+/* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.
  *
@@ -442,6 +442,11 @@ int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t*
  *                            E(j, 1) .. E(j, l), where E(j, l) estimates the union of sketches order[j .. j + l); entries with
  *                            l > n - j are 0.  So every row is non-decreasing up to its end.  At most GN_SKETCH_TABLE_MAX entries
  *                            ((j1 - j0) * width) in one call, GN_ERANGE beyond: rows are independent, tile over the starts.
+ *   gn_sketches_pair_table   (`--layout similarity`) `idx` = m sketch indices (each below the handle's number of sketches, GN_EINVAL
+ *                            otherwise; repeats allowed).  out[a * m + b] = E of the union of the two sketches idx[a] and idx[b],
+ *                            for every a and b below m: the plain E of the pair -- no running maximum as in the union table.  The
+ *                            table is symmetric, and its diagonal is E of the single sketch.  At most GN_SKETCH_TABLE_MAX entries
+ *                            (m * m, so m <= 4096) in one call, GN_ERANGE beyond.  m == 0 writes nothing and returns GN_OK.
  * E from the union's registers U[r] = max over the sketches of register r, with m = 4096:
  *     Z = number of r with U[r] == 0;  S = sum over r of 2^(52 - U[r]) as an integer (below 2^64 unless Z == m)
  *     Z == m: E = 0.  Otherwise raw = num / (double)S, both the conversion and the division rounded to nearest, with
@@ -456,6 +461,7 @@ int gn_sketches_create(int device, const uint64_t* const* sets, const uint64_t* 
 int gn_sketches_free(gn_sketches* s);
 int gn_sketches_download(gn_sketches* s, uint32_t first, uint32_t n, uint8_t* out);
 int gn_sketches_union_table(gn_sketches* s, const uint32_t* order, uint32_t n, uint32_t j0, uint32_t j1, uint32_t width, uint64_t* out);
+int gn_sketches_pair_table(gn_sketches* s, const uint32_t* idx, uint32_t m, uint64_t* out);
 
 /* Parity / debugging taps (tests only): minimiser hashes of the resident batch in emission order
  * (hash_off[n_reads+1]; hashes[cap]) and dense per-bin counts of reads [read_begin, read_end)

@@ -4,9 +4,14 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --hibf          the same FASTA built flat AND as HIBF (`ganon-build --hibf`), alternating, one run each to warm up and then the median
                   of --runs (5) each, both at --max-fp (0.05) and --hash-functions (4); the HIBF time split into hash / union / emplace /
                   write; --tmax N is passed on.  Prints one JSON object with "flat" and "hibf".
-  --layout NAME   [--hibf] passed on as `--layout NAME` (rule | sketch).  A comma list (rule,sketch) builds every layout in turn in
-                  each round, alternating, and prints "hibf" as one object per layout; a sketch build also reports layout_s, the
-                  part of union_s that went into sketches, union table and search.
+  --layout NAME   [--hibf] passed on as `--layout NAME` (rule | sketch | similarity).  A comma list (rule,sketch,similarity) builds
+                  every layout in turn in each round, alternating, and prints "hibf" as one object per layout; a sketch or
+                  similarity build also reports layout_s, the part of union_s that went into sketches, union tables and search,
+                  a similarity build its split (layout_sketches_s, layout_tables_s, layout_pairs_s, layout_host_s) and the
+                  tree it kept.
+  --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
+                  i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
+                  from its end, so that the lengths of the families interleave
   --lognormal S   file i has len * exp(S * z_i) bases, z_i standard normal (seeded): `len` is the median, not every file's length"""
 import json
 import math
@@ -19,7 +24,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": ""}
 pos, hibf, argv = [], False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -40,13 +45,25 @@ cols = 70
 lengths = [L] * n_files
 if opts["--lognormal"]:
     lengths = [max(1000, int(L * math.exp(float(opts["--lognormal"]) * z))) for z in np.random.default_rng(2).standard_normal(n_files)]
+n_families, divergence, ancestors = 0, 0.0, []
+if opts["--families"]:
+    n_families, divergence = int(opts["--families"].split(":")[0]), float(opts["--families"].split(":")[1])
+    cut = np.random.default_rng(3)
+    lengths = [n - int(cut.random() * 0.1 * n) for n in lengths]
+    ancestors = [rng.integers(0, 4, size=max(lengths[f::n_families]), dtype=np.uint8) for f in range(n_families)]
 total_bases = sum(lengths)
 with open(os.path.join(d, "in.tsv"), "w") as tsv:
     for i in range(n_files):
         L = lengths[i]
         rows = (L + cols - 1) // cols
         body = np.full((rows, cols + 1), ord("\n"), dtype=np.uint8)
-        body[:, :cols] = lut[rng.integers(0, 4, size=(rows, cols), dtype=np.uint8)]
+        if n_families:
+            ranks = ancestors[i % n_families][:L].copy()
+            hit = np.nonzero(rng.random(L) < divergence)[0]
+            ranks[hit] = (ranks[hit] + rng.integers(1, 4, size=len(hit), dtype=np.uint8)) & 3  # another base
+            body.reshape(-1)[np.arange(L) + np.arange(L) // cols] = lut[ranks]
+        else:
+            body[:, :cols] = lut[rng.integers(0, 4, size=(rows, cols), dtype=np.uint8)]
         f = os.path.join(d, f"g{i}.fna")
         with open(f, "wb") as o:
             o.write(f">genome{i} synthetic\n".encode())
@@ -54,6 +71,8 @@ with open(os.path.join(d, "in.tsv"), "w") as tsv:
         tsv.write(f"{f}\tT{i}\n")
 L = int(pos[1]) if len(pos) > 1 else 4_000_000
 out = {"files": n_files, "bases_per_file": L, "total_gbp": round(total_bases / 1e9, 3), "threads": threads}
+if n_families:
+    out["families"], out["divergence"] = n_families, divergence
 if opts["--lognormal"]:
     out["lognormal_sigma"], out["largest_file"], out["smallest_file"] = float(opts["--lognormal"]), max(lengths), min(lengths)
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
@@ -99,6 +118,12 @@ def hibf_run(layout=""):
     m = re.search(r" write [0-9.eE+-]+ layout ([0-9.eE+-]+)", p.stderr)
     if m:
         res["layout_s"] = float(m.group(1))
+    m = re.search(r" - layout seconds: sketches ([0-9.eE+-]+) tables ([0-9.eE+-]+) pairs ([0-9.eE+-]+) host ([0-9.eE+-]+)", p.stderr)
+    if m:
+        res["layout_sketches_s"], res["layout_tables_s"], res["layout_pairs_s"], res["layout_host_s"] = (float(x) for x in m.groups())
+    m = re.search(r"layout similarity: (\d+) intervals, (\d+) of \d+ user bins moved, kept (\w+)", p.stderr)
+    if m:
+        res["intervals"], res["moved"], res["kept"] = int(m.group(1)), int(m.group(2)), m.group(3)
     m = re.search(r"ganon-build       start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)", p.stderr)
     if m:
         res["total_s"] = float(m.group(1))
