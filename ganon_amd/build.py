@@ -73,14 +73,15 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_host(force: bool = False, verbose: bool = False) -> str:
-    """ganon-classify (every host source but the builder's) and ganon-build (its own sources + the sequence reader)"""
+    """ganon-classify (every host source but the builder's) and ganon-build (its own sources + the sequence reader + the index
+    reader `--verify-index` loads a file with)"""
     if not os.path.isdir(HOST):
         return ""
     every = sorted(f for f in os.listdir(HOST) if f.endswith(".cpp"))
     hdrs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "ganon_hip.h"), os.path.join(ROOT, "include", "ganon_ibf_hash.h")]
     build_hip(force=False, verbose=verbose)
     for binary, names in ((BIN, [f for f in every if f not in BUILD_ONLY + REASSIGN_ONLY]),
-                          (BIN_BUILD, [f for f in every if f in BUILD_ONLY] + ["seq_io.cpp", "pgzip.cpp"]),
+                          (BIN_BUILD, [f for f in every if f in BUILD_ONLY] + ["seq_io.cpp", "pgzip.cpp", "filter_io.cpp"]),
                           (BIN_REASSIGN, [f for f in every if f in REASSIGN_ONLY])):
         srcs = [os.path.join(HOST, f) for f in names]
         if not srcs:

@@ -143,48 +143,56 @@ __global__ __launch_bounds__(256) void gn_emplace_path_kernel(const uint64_t* __
     }
 }
 
-extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
-                                      uint32_t depth)
+// ---- the host part the insert and the probes share ------------------------------------------------------------------------------
+// One gn_path_entry against the filter, resolved for the kernels.  An insert deals hash i of a set of n to bin first_bin + i / hashes_per_bin,
+// which is checked here too; a probe looks at every bin of the run and ignores hashes_per_bin.
+static int gn_path_resolve(const char* who, const gn_filter* f, const gn_path_entry& e, uint32_t s, uint32_t d, bool dealt, uint64_t n, GnPathDev& o)
 {
-    if (!f || !f->is_hibf)
-        return gn_fail(GN_EINVAL, "gn_filter_emplace_path needs an HIBF filter");
-    if (n_sets == 0)
-        return GN_OK;
+    if (e.ibf >= f->ibfs.size())
+        return gn_fail(GN_EINVAL, "%s: set %u level %u: ibf %u of %zu", who, s, d, e.ibf, f->ibfs.size());
+    const GnIbfHost& ib = f->ibfs[e.ibf];
+    if ((uint64_t)e.first_bin + e.n_bins > ib.B)
+        return gn_fail(GN_EINVAL, "%s: set %u level %u: bins %u..%llu of an IBF with %llu", who, s, d, e.first_bin,
+                       (unsigned long long)e.first_bin + e.n_bins - 1, (unsigned long long)ib.B);
+    if (dealt && e.n_bins > 1 && (e.hashes_per_bin == 0 || (n && (n - 1) / e.hashes_per_bin >= e.n_bins)))
+        return gn_fail(GN_EINVAL, "%s: set %u level %u: %llu hashes at %llu a bin do not fit %u bins", who, s, d, (unsigned long long)n,
+                       (unsigned long long)e.hashes_per_bin, e.n_bins);
+    o = GnPathDev{ ib.d_rows, ib.S, dealt && e.n_bins > 1 ? e.hashes_per_bin : 1, (uint32_t)ib.Ws, ib.shift, e.first_bin, e.n_bins };
+    return GN_OK;
+}
+
+// n_paths paths of `depth` entries each, resolved; an entry with n_bins == 0 ends its path (set_off == NULL: no sets, n = 0 for every path)
+static int gn_paths_resolve(const char* who, const gn_filter* f, const uint64_t* set_off, uint32_t n_paths, const gn_path_entry* paths, uint32_t depth,
+                            bool dealt, std::vector<GnPathDev>& dev)
+{
+    dev.assign((size_t)n_paths * depth, GnPathDev{ nullptr, 1, 1, 1, 0, 0, 0 });
+    for (uint32_t s = 0; s < n_paths; ++s)
+    {
+        if (set_off && set_off[s + 1] < set_off[s])
+            return gn_fail(GN_EINVAL, "%s: set offsets descend at set %u", who, s);
+        const uint64_t n = set_off ? set_off[s + 1] - set_off[s] : 0;
+        for (uint32_t d = 0; d < depth && paths[(size_t)s * depth + d].n_bins != 0; ++d)
+            if (const int rc = gn_path_resolve(who, f, paths[(size_t)s * depth + d], s, d, dealt, n, dev[(size_t)s * depth + d]))
+                return rc;
+    }
+    return GN_OK;
+}
+
+// Argument checks, GnPathDev resolution, GnPathItem cutting and the staging upload of gn_filter_emplace_path and gn_filter_probe_path:
+// every bin a hash can reach is checked before anything is launched (the row is below S by construction, gn_build_row); then
+// launch(stage, items, n_items, paths) is called on f->load_st once per round of at most 32 M hashes, and waited for.
+template <typename Launch>
+static int gn_path_rounds(const char* who, gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                          uint32_t depth, bool dealt, Launch launch)
+{
     if (!set_off || !paths || depth == 0)
-        return gn_fail(GN_EINVAL, "gn_filter_emplace_path: null argument");
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
     const uint64_t total = set_off[n_sets];
     if (total && !hashes)
-        return gn_fail(GN_EINVAL, "gn_filter_emplace_path: null argument");
-    // every bin a hash can reach is checked here; the row is below S by construction (gn_build_row)
-    std::vector<GnPathDev> dev((size_t)n_sets * depth);
-    for (uint32_t s = 0; s < n_sets; ++s)
-    {
-        if (set_off[s + 1] < set_off[s])
-            return gn_fail(GN_EINVAL, "gn_filter_emplace_path: set offsets descend at set %u", s);
-        const uint64_t n    = set_off[s + 1] - set_off[s];
-        bool           open = true;
-        for (uint32_t d = 0; d < depth; ++d)
-        {
-            const gn_path_entry& e = paths[(size_t)s * depth + d];
-            GnPathDev&           o = dev[(size_t)s * depth + d];
-            o                      = GnPathDev{ nullptr, 1, 1, 1, 0, 0, 0 };
-            if (e.n_bins == 0 || !open)
-            {
-                open = false;
-                continue;
-            }
-            if (e.ibf >= f->ibfs.size())
-                return gn_fail(GN_EINVAL, "gn_filter_emplace_path: set %u level %u: ibf %u of %zu", s, d, e.ibf, f->ibfs.size());
-            const GnIbfHost& ib = f->ibfs[e.ibf];
-            if ((uint64_t)e.first_bin + e.n_bins > ib.B)
-                return gn_fail(GN_EINVAL, "gn_filter_emplace_path: set %u level %u: bins %u..%llu of an IBF with %llu", s, d, e.first_bin,
-                               (unsigned long long)e.first_bin + e.n_bins - 1, (unsigned long long)ib.B);
-            if (e.n_bins > 1 && (e.hashes_per_bin == 0 || (n && (n - 1) / e.hashes_per_bin >= e.n_bins)))
-                return gn_fail(GN_EINVAL, "gn_filter_emplace_path: set %u level %u: %llu hashes at %llu a bin do not fit %u bins", s, d,
-                               (unsigned long long)n, (unsigned long long)e.hashes_per_bin, e.n_bins);
-            o = GnPathDev{ ib.d_rows, ib.S, e.n_bins > 1 ? e.hashes_per_bin : 1, (uint32_t)ib.Ws, ib.shift, e.first_bin, e.n_bins };
-        }
-    }
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    std::vector<GnPathDev> dev;
+    if (const int rc = gn_paths_resolve(who, f, set_off, n_sets, paths, depth, dealt, dev))
+        return rc;
     if (total == 0)
         return GN_OK;
     GN_HIP(hipSetDevice(f->device));
@@ -217,11 +225,291 @@ extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, cons
             GN_HIP(hipErrorInvalidValue);
         GN_HIP(hipMemcpyAsync(f->d_emplace_stage, hashes + done, c * 8, hipMemcpyHostToDevice, f->load_st));
         GN_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GnPathItem), hipMemcpyHostToDevice, f->load_st));
-        const uint32_t n_items = (uint32_t)items.size();
-        hipLaunchKernelGGL(gn_emplace_path_kernel, dim3((n_items + 3) / 4), dim3(256), 0, f->load_st, f->d_emplace_stage, d_items, n_items,
-                           d_paths, depth, f->ibfs[0].h);
+        GN_HIP(launch((const uint64_t*)f->d_emplace_stage, (const GnPathItem*)d_items, (uint32_t)items.size(), (const GnPathDev*)d_paths));
         GN_HIP(hipGetLastError());
         GN_HIP(hipStreamSynchronize(f->load_st)); // (the staging buffer and `items` are reused, and `hashes` may be pageable)
     }
+    return GN_OK;
+}
+
+extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                                      uint32_t depth)
+{
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_emplace_path needs an HIBF filter");
+    if (n_sets == 0)
+        return GN_OK;
+    return gn_path_rounds("gn_filter_emplace_path", f, hashes, set_off, n_sets, paths, depth, true,
+                          [&](const uint64_t* stage, const GnPathItem* items, uint32_t n_items, const GnPathDev* d_paths) {
+                              hipLaunchKernelGGL(gn_emplace_path_kernel, dim3((n_items + 3) / 4), dim3(256), 0, f->load_st, stage, items, n_items, d_paths,
+                                                 depth, f->ibfs[0].h);
+                              return hipSuccess;
+                          });
+}
+
+// ---- gn_filter_probe_path / gn_filter_probe_paths_shared: the insert read back ---------------------------------------------------
+typedef const __attribute__((address_space(1))) unsigned long long GnGlobalConstWord;
+
+// bits of word `w` of a row that belong to the run first_bin .. first_bin + n_bins - 1 (which reaches into that word)
+__device__ __forceinline__ uint64_t gn_run_mask(uint32_t first_bin, uint32_t n_bins, uint32_t w)
+{
+    const uint64_t lo = max((uint64_t)first_bin, (uint64_t)w << 6), hi = min((uint64_t)first_bin + n_bins, ((uint64_t)w + 1) << 6);
+    return (hi - lo >= 64u ? ~0ULL : (1ULL << (hi - lo)) - 1) << (lo & 63u);
+}
+
+// One wave per item, as the insert: item and path entries in SGPRs, 8 hashes a lane in registers.  Per entry and word of its run the
+// H row words of all 8 hashes are loaded before any is looked at -- 8 * H independent loads in flight per lane, nothing to store -- then
+// ANDed and masked to the run.  A lane without a hash in a slot probes hash 0 there (row 0 word w of the entry: inside the matrix)
+// and its answer is not counted, so that no load sits behind a lane-dependent branch.  Counts leave the wave as one atomic each.
+template <uint32_t H>
+__global__ __launch_bounds__(256) void gn_probe_path_kernel(const uint64_t* __restrict__ stage, const GnPathItem* __restrict__ items, uint32_t n_items,
+                                                            const GnPathDev* __restrict__ paths, uint32_t depth, unsigned long long* __restrict__ found,
+                                                            unsigned long long* __restrict__ lost_at, unsigned long long* __restrict__ first_lost)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t   lane = threadIdx.x & 63u;
+    const GnPathItem it   = items[item];
+    uint64_t         v[GN_PATH_PER_LANE];
+    uint32_t         valid = 0; // bit j: slot j holds a hash of the item
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+        valid |= (q < it.cnt ? 1u : 0u) << j;
+    }
+    uint32_t alive = valid; // bit j: contained in every entry so far
+    const GnPathDev* __restrict__ p = paths + (uint64_t)it.seg * depth;
+    for (uint32_t d = 0; d < depth; ++d)
+    {
+        const GnPathDev e = p[d];
+        if (e.n_bins == 0)
+            break;
+        if (!lost_at && __ballot(alive != 0) == 0) // (nobody asks at which level: a wave whose hashes are all lost already is done)
+            break;
+        GnGlobalConstWord* rows = (GnGlobalConstWord*)e.rows;
+        const uint32_t     w1   = (e.first_bin + e.n_bins - 1) >> 6;
+        uint32_t           hit  = 0;
+        for (uint32_t w = e.first_bin >> 6; w <= w1; ++w)
+        {
+            const uint64_t mask = gn_run_mask(e.first_bin, e.n_bins, w);
+            uint64_t       r[GN_PATH_PER_LANE][H];
+#pragma unroll
+            for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+#pragma unroll
+                for (uint32_t i = 0; i < H; ++i)
+                    r[j][i] = rows[(uint64_t)gn_build_row(v[j], i, e.shift, e.S) * e.Ws + w];
+#pragma unroll
+            for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+            {
+                uint64_t a = r[j][0];
+#pragma unroll
+                for (uint32_t i = 1; i < H; ++i)
+                    a &= r[j][i];
+                hit |= ((a & mask) != 0 ? 1u : 0u) << j;
+            }
+        }
+        alive &= hit;
+        if (lost_at)
+        {
+            const uint32_t lost = valid & ~hit;
+            uint32_t       n    = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+                n += (uint32_t)__popcll(__ballot((lost >> j) & 1u));
+            if (n && lane == 0)
+                atomicAdd(&lost_at[(uint64_t)it.seg * depth + d], (unsigned long long)n);
+        }
+    }
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+        n += (uint32_t)__popcll(__ballot((alive >> j) & 1u));
+    if (n && lane == 0)
+        atomicAdd(&found[it.seg], (unsigned long long)n);
+    const uint32_t dead = valid & ~alive;
+    if (__ballot(dead != 0) != 0)
+    {
+        // slot j of this lane is hash begin + j * 64 + lane of the set: the lowest dead slot is the lane's first
+        unsigned long long m = dead ? it.begin + (uint64_t)(__ffs((int)dead) - 1) * 64u + lane : ~0ULL;
+        for (int off = 32; off; off >>= 1)
+        {
+            const unsigned long long o = __shfl_xor(m, off);
+            m                          = o < m ? o : m;
+        }
+        if (lane == 0)
+            atomicMin(&first_lost[it.seg], m);
+    }
+}
+
+template <uint32_t H>
+static hipError_t gn_probe_path_launch(hipStream_t st, const uint64_t* stage, const GnPathItem* items, uint32_t n_items, const GnPathDev* paths, uint32_t depth,
+                                       unsigned long long* found, unsigned long long* lost_at, unsigned long long* first_lost)
+{
+    hipLaunchKernelGGL(gn_probe_path_kernel<H>, dim3((n_items + 3) / 4), dim3(256), 0, st, stage, items, n_items, paths, depth, found, lost_at, first_lost);
+    return hipSuccess;
+}
+
+extern "C" int gn_filter_probe_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                                    uint32_t depth, uint64_t* found, uint64_t* lost_at, uint64_t* first_lost)
+{
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_probe_path needs an HIBF filter");
+    if (n_sets == 0)
+        return GN_OK;
+    if (!found || !first_lost)
+        return gn_fail(GN_EINVAL, "gn_filter_probe_path: null argument");
+    const uint32_t h = f->ibfs[0].h;
+    if (h < 1 || h > GN_IBF_MAX_HASH_FUNS)
+        return gn_fail(GN_EINVAL, "gn_filter_probe_path: %u hash functions", h);
+    GnDev<unsigned long long> d_found, d_lost, d_first;
+    const size_t              n_lost = (size_t)n_sets * depth;
+    const int                 rc     = gn_path_rounds(
+        "gn_filter_probe_path", f, hashes, set_off, n_sets, paths, depth, false,
+        [&](const uint64_t* stage, const GnPathItem* items, uint32_t n_items, const GnPathDev* d_paths) -> hipError_t {
+            hipError_t e = hipSuccess;
+            if (!d_found) // the first round: the counters, zero (first_lost: all ones), ordered before the kernel on the same stream
+            {
+                if ((e = d_found.alloc(n_sets)) != hipSuccess || (e = d_first.alloc(n_sets)) != hipSuccess || (lost_at && (e = d_lost.alloc(n_lost)) != hipSuccess))
+                    return e;
+                if ((e = hipMemsetAsync(d_found, 0, (size_t)n_sets * 8, f->load_st)) != hipSuccess ||
+                    (e = hipMemsetAsync(d_first, 0xFF, (size_t)n_sets * 8, f->load_st)) != hipSuccess ||
+                    (lost_at && (e = hipMemsetAsync(d_lost, 0, n_lost * 8, f->load_st)) != hipSuccess))
+                    return e;
+            }
+            switch (h)
+            {
+            case 1: return gn_probe_path_launch<1>(f->load_st, stage, items, n_items, d_paths, depth, d_found, d_lost, d_first);
+            case 2: return gn_probe_path_launch<2>(f->load_st, stage, items, n_items, d_paths, depth, d_found, d_lost, d_first);
+            case 3: return gn_probe_path_launch<3>(f->load_st, stage, items, n_items, d_paths, depth, d_found, d_lost, d_first);
+            case 4: return gn_probe_path_launch<4>(f->load_st, stage, items, n_items, d_paths, depth, d_found, d_lost, d_first);
+            default: return gn_probe_path_launch<5>(f->load_st, stage, items, n_items, d_paths, depth, d_found, d_lost, d_first);
+            }
+        });
+    if (rc != GN_OK)
+        return rc;
+    if (!d_found) // no hash in any set
+    {
+        std::fill(found, found + n_sets, 0);
+        std::fill(first_lost, first_lost + n_sets, ~0ull);
+        if (lost_at)
+            std::fill(lost_at, lost_at + n_lost, 0);
+        return GN_OK;
+    }
+    GN_HIP(hipMemcpy(found, d_found, (size_t)n_sets * 8, hipMemcpyDeviceToHost)); // (every round was waited for)
+    GN_HIP(hipMemcpy(first_lost, d_first, (size_t)n_sets * 8, hipMemcpyDeviceToHost));
+    if (lost_at)
+        GN_HIP(hipMemcpy(lost_at, d_lost, n_lost * 8, hipMemcpyDeviceToHost));
+    return GN_OK;
+}
+
+// A lane owns a path, a wave 64 paths and `chunks` chunks of 64 probes.  Per chunk the lane keeps a 64-bit mask of the probes still
+// contained; the entries are walked from the root down (the root is the last used entry), so that most probes die where the lanes of
+// a wave -- neighbours in (leaf ibf, first bin) order when the caller sorts -- read the same words of the same IBF.  The probe is read
+// at a wave-uniform address.  found[] takes one atomic add per lane and wave: integers, so neither the order of the paths nor the
+// cut of the probes into waves shows in the result.
+template <uint32_t H>
+__global__ __launch_bounds__(256) void gn_probe_shared_kernel(const uint64_t* __restrict__ probes, uint64_t n, const GnPathDev* __restrict__ paths,
+                                                              uint32_t n_paths, uint32_t depth, uint32_t path_waves, uint32_t chunks,
+                                                              unsigned long long* __restrict__ found)
+{
+    const uint32_t wave  = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const uint32_t group = wave % path_waves;
+    const uint64_t c0    = (uint64_t)(wave / path_waves) * chunks;
+    const uint32_t path  = group * 64u + (threadIdx.x & 63u);
+    const bool     mine  = path < n_paths;
+    const GnPathDev* __restrict__ p = paths + (uint64_t)(mine ? path : 0) * depth;
+    uint32_t       total = 0;
+    for (uint64_t c = c0; c < c0 + chunks && c * 64u < n; ++c)
+    {
+        const uint64_t* __restrict__ pr  = probes + c * 64u;
+        const uint32_t               cnt = (uint32_t)min((uint64_t)64, n - c * 64u);
+        uint64_t                     alive = !mine ? 0 : cnt == 64u ? ~0ULL : (1ULL << cnt) - 1;
+        for (uint32_t d = depth; d-- > 0;)
+        {
+            const GnPathDev e    = p[d];
+            const bool      used = e.n_bins != 0 && alive != 0;
+            if (__ballot(used) == 0)
+                continue;
+            GnGlobalConstWord* rows = (GnGlobalConstWord*)e.rows;
+            const uint32_t     w0 = e.first_bin >> 6, w1 = used ? (e.first_bin + e.n_bins - 1) >> 6 : w0;
+            for (uint32_t q = 0; q < cnt; ++q)
+            {
+                const uint64_t v = pr[q];
+                if (!used || !((alive >> q) & 1))
+                    continue;
+                bool hit = false;
+                for (uint32_t w = w0; w <= w1 && !hit; ++w)
+                {
+                    uint64_t r[H];
+#pragma unroll
+                    for (uint32_t i = 0; i < H; ++i)
+                        r[i] = rows[(uint64_t)gn_build_row(v, i, e.shift, e.S) * e.Ws + w];
+                    uint64_t a = r[0];
+#pragma unroll
+                    for (uint32_t i = 1; i < H; ++i)
+                        a &= r[i];
+                    hit = (a & gn_run_mask(e.first_bin, e.n_bins, w)) != 0;
+                }
+                if (!hit)
+                    alive &= ~(1ULL << q);
+            }
+        }
+        total += (uint32_t)__popcll(alive);
+    }
+    if (mine && total)
+        atomicAdd(&found[path], (unsigned long long)total);
+}
+
+extern "C" int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths, uint32_t depth,
+                                            uint64_t* found)
+{
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_probe_paths_shared needs an HIBF filter");
+    if (n_paths == 0)
+        return GN_OK;
+    if (!paths || !found || depth == 0 || (n && !probes))
+        return gn_fail(GN_EINVAL, "gn_filter_probe_paths_shared: null argument");
+    const uint32_t h = f->ibfs[0].h;
+    if (h < 1 || h > GN_IBF_MAX_HASH_FUNS)
+        return gn_fail(GN_EINVAL, "gn_filter_probe_paths_shared: %u hash functions", h);
+    std::vector<GnPathDev> dev;
+    if (const int rc = gn_paths_resolve("gn_filter_probe_paths_shared", f, nullptr, n_paths, paths, depth, false, dev))
+        return rc;
+    std::fill(found, found + n_paths, 0);
+    if (n == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    if (!f->load_st)
+        GN_HIP(hipStreamCreateWithFlags(&f->load_st, hipStreamNonBlocking));
+    GnDev<uint64_t>           d_probes;
+    GnDev<GnPathDev>          d_paths;
+    GnDev<unsigned long long> d_found;
+    GN_HIP(d_probes.alloc(n));
+    GN_HIP(d_paths.alloc(dev.size()));
+    GN_HIP(d_found.alloc(n_paths));
+    GN_HIP(hipMemcpyAsync(d_probes, probes, n * 8, hipMemcpyHostToDevice, f->load_st));
+    GN_HIP(hipMemcpyAsync(d_paths, dev.data(), dev.size() * sizeof(GnPathDev), hipMemcpyHostToDevice, f->load_st));
+    GN_HIP(hipMemsetAsync(d_found, 0, (size_t)n_paths * 8, f->load_st));
+    // enough waves to fill the device whatever the number of paths: the probes are cut so that about 8192 waves come out
+    const uint64_t n_chunks = (n + 63) / 64, path_waves = ((uint64_t)n_paths + 63) / 64;
+    const uint64_t chunks   = std::max<uint64_t>(1, (n_chunks * path_waves + 8191) / 8192);
+    const uint64_t waves    = path_waves * ((n_chunks + chunks - 1) / chunks);
+    if (chunks > 0xFFFFFFFFull || (waves + 3) / 4 > 0x7FFFFFFFull)
+        return gn_fail(GN_ERANGE, "gn_filter_probe_paths_shared: %llu probes against %u paths in one call", (unsigned long long)n, n_paths);
+    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
+    switch (h)
+    {
+    case 1: hipLaunchKernelGGL(gn_probe_shared_kernel<1>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_found); break;
+    case 2: hipLaunchKernelGGL(gn_probe_shared_kernel<2>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_found); break;
+    case 3: hipLaunchKernelGGL(gn_probe_shared_kernel<3>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_found); break;
+    case 4: hipLaunchKernelGGL(gn_probe_shared_kernel<4>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_found); break;
+    default: hipLaunchKernelGGL(gn_probe_shared_kernel<5>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_found); break;
+    }
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipStreamSynchronize(f->load_st));
+    GN_HIP(hipMemcpy(found, d_found, (size_t)n_paths * 8, hipMemcpyDeviceToHost));
     return GN_OK;
 }

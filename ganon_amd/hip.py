@@ -32,7 +32,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_get_stats", "gn_inflate_cuts", "gn_inflate_set_carry", "gn_stream_upload_text_device", "gn_stream_fastq_headers",
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
-               "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path",
+               "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
 
 
@@ -162,6 +162,8 @@ def load_library():
     L.gn_filter_emplace_split.argtypes = [vp, vp, u64, u32, u64]
     L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
+    L.gn_filter_probe_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
+    L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
     L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
     L.gn_sketches_free.argtypes = [vp]
     L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
@@ -597,6 +599,32 @@ class HipFilter:
         hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
         hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
         _check(load_library().gn_filter_emplace_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1]))
+
+    def probe_path(self, sets: Sequence[np.ndarray], paths: np.ndarray, with_lost_at: bool = True):
+        """gn_filter_probe_path: sets[s] along paths[s] (PATH_DTYPE, [len(sets), depth]) -> (found uint64 [n], lost_at uint64 [n, depth] or
+        None, first_lost uint64 [n], all ones = none)"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(sets)
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(a) for a in sets])
+        hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        found = np.zeros(len(sets), dtype=np.uint64)
+        first = np.full(len(sets), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        lost = np.zeros((len(sets), paths.shape[1]), dtype=np.uint64) if with_lost_at else None
+        _check(load_library().gn_filter_probe_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1],
+                                                   _p(found), _p(lost) if with_lost_at else None, _p(first)))
+        return found, lost, first
+
+    def probe_paths_shared(self, probes: np.ndarray, paths: np.ndarray) -> np.ndarray:
+        """gn_filter_probe_paths_shared: the same probes against every path (PATH_DTYPE, [n_paths, depth]) -> found uint64 [n_paths]"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2
+        probes = np.ascontiguousarray(probes, dtype=np.uint64)
+        found = np.zeros(paths.shape[0], dtype=np.uint64)
+        _check(load_library().gn_filter_probe_paths_shared(self._h, _p(probes), len(probes), paths.ctypes.data_as(C.c_void_p), paths.shape[0],
+                                                           paths.shape[1], _p(found)))
+        return found
 
     def probe(self, hashes: np.ndarray, bins: np.ndarray) -> Tuple[int, int, int]:
         """gn_filter_probe -> (hits summed over the bins, hashes in none of the bins, index of the first such hash or -1)"""

@@ -21,6 +21,12 @@
 //   -> rows per IBF (gnbuild::hibf_run_bits) -> zero-filled HIBF in HBM -> every user bin ORed in along its whole path
 //   (gn_filter_emplace_path) -> IBF after IBF streamed into the file (save_hibf: the twin of ganon_amd/ibf_file.py:save_hibf).
 //
+// --hibf --verify-index F (this project's extension): nothing is built.  The inputs are hashed as for a build, the file's bits are
+// streamed into HBM, and per user bin the device answers two questions: is every distinct minimiser of the target found in every
+// IBF on the user bin's root-to-leaf path (gn_filter_probe_path along hibf_paths.hpp:derive_paths -- the paths come from the
+// FILE's tables, whoever wrote it), and how often does the user bin answer to values that are no target's minimiser
+// (gn_filter_probe_paths_shared).
+//
 // Differences from the reference that cannot be avoided here: targets are laid out in the order of
 // their first appearance in the input file and a target's hashes in ascending order -- the reference uses the iteration
 // order of robin_hood maps/sets, which is not reproducible without that library; which bin of a split target holds
@@ -28,8 +34,10 @@
 // Sequences shorter than the window (but at least one k-mer long) yield the minimum over all their k-mers, which is what
 // seqan3::views::minimiser does when the range is shorter than its window (recollection of SeqAn3 3.3.0, unpinned).
 #include "build_params.hpp"
+#include "filter_io.hpp"
 #include "hasher.hpp"
 #include "hibf_layout.hpp"
+#include "hibf_paths.hpp"
 #include "hibf_layout_similarity.hpp"
 #include "hibf_layout_sketch.hpp"
 #include "hostmem.hpp"
@@ -82,6 +90,8 @@ struct Config // Config.hpp:10-27
     std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates,
                                  //  similarity = hibf_layout_similarity.hpp: sketch over an order that groups related targets)
     bool        layout_given = false;
+    std::string verify_index;    // (--hibf only: check this index against the inputs instead of building one)
+    bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
 };
 
 bool validate(Config& c) // Config.hpp:29-107, same messages
@@ -97,6 +107,44 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--layout needs --hibf");
     if (c.layout_given && c.layout != "rule" && c.layout != "sketch" && c.layout != "similarity")
         return say("--layout has to be rule, sketch or similarity");
+    if (c.verify_given)
+    {
+        if (!c.hibf)
+            return say("--verify-index needs --hibf (it checks a hierarchical index; a flat .ibf is checked by ganon-classify --verify-filter)");
+        if (c.output_given)
+            return say("--verify-index cannot be used with --output-file (nothing is built and nothing is written)");
+        if (c.verify_index.empty() || !fs::exists(c.verify_index))
+        {
+            if (!c.quiet)
+                std::cerr << "--verify-index not found: " << c.verify_index << std::endl;
+            return false;
+        }
+        // k, w and the number of hash functions are the file's; a value given on the command line has to agree
+        try
+        {
+            gnhost::FilterMeta meta;
+            gnhost::read_hibf_meta(c.verify_index, meta);
+            const unsigned k = meta.ibf_config.kmer_size, w = meta.ibf_config.window_size, h = (unsigned)meta.shapes.at(0).hash_funs;
+            auto differs = [&](const char* opt, unsigned given, unsigned file) {
+                if (!c.quiet)
+                    std::cerr << "--verify-index: " << opt << " " << given << " differs from the index, which was built with " << file << std::endl;
+                return false;
+            };
+            if (c.kmer_given && c.kmer_size != k)
+                return differs("--kmer-size", c.kmer_size, k);
+            if (c.window_given && c.window_size != w)
+                return differs("--window-size", c.window_size, w);
+            if (c.hashes_given && c.hash_functions != h)
+                return differs("--hash-functions", c.hash_functions, h);
+            c.kmer_size = (uint8_t)k, c.window_size = (uint16_t)w, c.hash_functions = (uint8_t)h;
+        }
+        catch (const std::exception& e)
+        {
+            if (!c.quiet)
+                std::cerr << "--verify-index: " << e.what() << std::endl;
+            return false;
+        }
+    }
     if (c.hibf)
     {
         if (c.filter_size_given)
@@ -122,7 +170,7 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
             std::cerr << "--input-file is empty: " << c.input_file << std::endl;
         return false;
     }
-    if (c.output_file.empty())
+    if (c.output_file.empty() && !c.verify_given)
         return say("--output-file is mandatory");
     if (c.tmp_output_folder != "" && !fs::exists(c.tmp_output_folder))
         return say("--tmp-output-folder not found");
@@ -162,6 +210,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
     if (c.layout_given)
         std::cerr << "--layout            " << c.layout << '\n';
+    if (c.verify_given)
+        std::cerr << "--verify-index      " << c.verify_index << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -190,6 +240,12 @@ const char* kHelp =
     "                               from HyperLogLog estimates of the unions of neighbouring targets) or similarity (as sketch,\n"
     "                               with targets of comparable size reordered so that related ones are neighbours; the\n"
     "                               smaller of the two trees is kept). Default: rule\n"
+    "      --verify-index arg       [--hibf] build nothing: check the index `arg` against the --input-file it was built from.\n"
+    "                               Per target: is every distinct minimiser found in every IBF on its user bin's path (FAIL\n"
+    "                               otherwise, with the first false negative), and how many of 65536 values that are no\n"
+    "                               target's minimiser the user bin answers to (WARN fp when clearly above the index's fpr;\n"
+    "                               a warning does not fail).  k, w and the hash functions come from the index; give the\n"
+    "                               --min-length of the build.  Not with --output-file\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -239,7 +295,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -287,13 +343,15 @@ int parse_args(int argc, char** argv, Config& c)
         if (vals.count("--input-file"))
             c.input_file = vals["--input-file"];
         if (vals.count("--output-file"))
-            c.output_file = vals["--output-file"];
+            c.output_file = vals["--output-file"], c.output_given = true;
         if (vals.count("--kmer-size"))
-            c.kmer_size = (uint8_t)u("--kmer-size", 255);
+            c.kmer_size = (uint8_t)u("--kmer-size", 255), c.kmer_given = true;
         if (vals.count("--window-size"))
-            c.window_size = (uint16_t)u("--window-size", 65535);
+            c.window_size = (uint16_t)u("--window-size", 65535), c.window_given = true;
         if (vals.count("--hash-functions"))
-            c.hash_functions = (uint8_t)u("--hash-functions", 255);
+            c.hash_functions = (uint8_t)u("--hash-functions", 255), c.hashes_given = true;
+        if (vals.count("--verify-index"))
+            c.verify_index = vals["--verify-index"], c.verify_given = true;
         if (vals.count("--max-fp"))
             c.max_fp = d("--max-fp");
         if (vals.count("--filter-size"))
@@ -786,6 +844,40 @@ bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, co
     return ok;
 }
 
+// a target's set = the union of its files' sets, ascending
+bool unite_files(const Config& c, Target& tg)
+{
+    if (tg.file_ends.size() <= 1)
+        return true;
+    std::vector<const uint64_t*> sets;
+    std::vector<uint64_t>        sizes;
+    uint64_t                     a = 0;
+    for (uint64_t e : tg.file_ends)
+    {
+        sets.push_back(tg.hashes.data() + a);
+        sizes.push_back(e - a);
+        a = e;
+    }
+    std::vector<uint64_t> all(tg.hashes.size());
+    uint64_t              n = 0;
+    if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), all.data(), all.size(), &n) != GN_OK)
+        return false;
+    all.resize(n);
+    tg.hashes.swap(all);
+    tg.file_ends.assign(1, n);
+    return true;
+}
+
+// the name of a target's user bin as an index file gives it back: written as <folder>/<name, "---" for a space>.minimiser by this
+// builder (and by `ganon build`, build_update.py:411-518), read as filter_io.cpp:parse_hibf reads it (GanonClassify.cpp:908-935)
+std::string user_bin_file_name(const std::string& target)
+{
+    std::string name = target;
+    for (size_t p = 0; (p = name.find(' ', p)) != std::string::npos; p += 3)
+        name.replace(p, 1, "---");
+    return name;
+}
+
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
 {
     Lap            uniting, laying, filling, writing;
@@ -808,30 +900,11 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         Target& tg = targets[t];
         if (tg.hashes.empty())
             continue;
-        if (tg.file_ends.size() > 1)
-        {
-            std::vector<const uint64_t*> sets;
-            std::vector<uint64_t>        sizes;
-            uint64_t                     a = 0;
-            for (uint64_t e : tg.file_ends)
-            {
-                sets.push_back(tg.hashes.data() + a);
-                sizes.push_back(e - a);
-                a = e;
-            }
-            std::vector<uint64_t> all(tg.hashes.size());
-            uint64_t              n = 0;
-            if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), all.data(), all.size(), &n) != GN_OK)
-                return fail(gn_last_error());
-            all.resize(n);
-            tg.hashes.swap(all);
-        }
+        if (!unite_files(c, tg))
+            return fail(gn_last_error());
         user_target.push_back(t);
         counts.push_back(tg.hashes.size());
-        std::string name = tg.name;
-        for (size_t p = 0; (p = name.find(' ', p)) != std::string::npos; p += 3)
-            name.replace(p, 1, "---");
-        files.push_back(dir + "/" + name + ".minimiser");
+        files.push_back(dir + "/" + user_bin_file_name(tg.name) + ".minimiser");
     }
     if (counts.empty())
         return fail("No valid sequences to build");
@@ -914,18 +987,9 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     }
     {
         // every user bin's path: its run in its leaf IBF, then the merged bin that leads there in each IBF above
-        const uint32_t             depth = lay.levels;
-        std::vector<gn_path_entry> path_of(n_user * depth, gn_path_entry{ 0, 0, 0, 0, 0 });
-        for (uint32_t i = 0; i < lay.ibfs.size(); ++i)
-            for (const gnhibf::Run& r : lay.ibfs[i].runs)
-            {
-                if (r.user < 0)
-                    continue;
-                gn_path_entry* p = &path_of[(size_t)r.user * depth];
-                *p++             = gn_path_entry{ i, r.first, r.n_bins, 0, (counts[r.user] + r.n_bins - 1) / r.n_bins };
-                for (uint32_t at = i; lay.ibfs[at].parent >= 0; at = (uint32_t)lay.ibfs[at].parent)
-                    *p++ = gn_path_entry{ (uint32_t)lay.ibfs[at].parent, lay.ibfs[at].parent_bin, 1, 0, 1 };
-            }
+        const gnhibf::Paths               all_paths = gnhibf::paths_of(lay, counts);
+        const uint32_t                    depth     = all_paths.depth;
+        const std::vector<gn_path_entry>& path_of   = all_paths.entries;
         // large sets go as they lie; small ones are gathered so that a launch has enough of them
         constexpr uint64_t         kBatch = 16ull << 20, kAlone = 4ull << 20;
         std::vector<uint64_t>      pool, off{ 0 };
@@ -1008,6 +1072,313 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     return true;
 }
 
+// ---- --hibf --verify-index -------------------------------------------------------------------------------------------------------
+
+// the index's bits into HBM of one device through the streaming loader (as verify.cpp's OneDeviceSink does for a flat filter)
+class HibfDeviceSink final : public gnhost::FilterSink
+{
+public:
+    explicit HibfDeviceSink(int device) : device_(device) {}
+    ~HibfDeviceSink() override
+    {
+        if (f_)
+            gn_filter_free(f_);
+        for (auto& s : stage_)
+            if (s.ptr)
+                gn_pinned_free(s.ptr);
+    }
+    bool begin(const gnhost::FilterMeta& f, std::string& err) override
+    {
+        std::vector<gn_ibf_desc>    descs(f.shapes.size());
+        std::vector<const int64_t*> nx(f.shapes.size()), bu(f.shapes.size());
+        words_.resize(f.shapes.size());
+        for (size_t i = 0; i < f.shapes.size(); ++i)
+        {
+            const gnhost::IbfShape& m = f.shapes[i];
+            descs[i] = gn_ibf_desc{ nullptr, m.bin_size, m.bin_words, m.bins, (uint32_t)m.hash_funs, (uint32_t)m.hash_shift };
+            nx[i] = f.next_ibf_id[i].data(), bu[i] = f.bin_to_user[i].data();
+            words_[i] = m.bin_words;
+        }
+        if (gn_filter_upload_hibf(device_, (uint32_t)descs.size(), descs.data(), nx.data(), bu.data(), f.n_user_bins, &f_) != GN_OK)
+        {
+            err = gn_last_error();
+            return false;
+        }
+        return true;
+    }
+    uint64_t* staging(int which, size_t bytes) override
+    {
+        Stage& s = stage_[which & 1];
+        if (s.bytes < bytes)
+        {
+            if (s.ptr)
+                gn_pinned_free(s.ptr);
+            s = Stage{};
+            void* p = nullptr;
+            if (gn_pinned_alloc(bytes, &p) != GN_OK)
+                return nullptr;
+            s.ptr = p, s.bytes = bytes;
+        }
+        return static_cast<uint64_t*>(s.ptr);
+    }
+    bool rows(uint32_t ibf, uint64_t row_begin, uint64_t n_rows, const uint64_t* src, std::string& err) override
+    {
+        if (gn_filter_write_rows(f_, ibf, row_begin, n_rows, src, words_.at(ibf), 0) == GN_OK)
+            return true;
+        err = gn_last_error();
+        return false;
+    }
+    bool drain(std::string& err) override
+    {
+        if (gn_filter_write_sync(f_) == GN_OK)
+            return true;
+        err = gn_last_error();
+        return false;
+    }
+    bool end(std::string& err) override
+    {
+        if (gn_filter_finalize(f_) == GN_OK)
+            return true;
+        err = gn_last_error();
+        return false;
+    }
+    gn_filter* filter() const { return f_; }
+
+private:
+    struct Stage
+    {
+        void*  ptr   = nullptr;
+        size_t bytes = 0;
+    };
+    int                   device_;
+    std::vector<uint64_t> words_;
+    gn_filter*            f_ = nullptr;
+    Stage                 stage_[2];
+};
+
+constexpr uint64_t kVerifyProbes = 65536; // P of the false-positive pass
+
+// probe i of the false-positive pass (include/ganon_hip.h states the generator): splitmix64 of i + 1 with bit 63 set -- a
+// (k,w)-minimiser hash is below 4^k, so for k <= 31 no target holds such a value
+uint64_t verify_probe(uint64_t i)
+{
+    uint64_t z = (i + 1) * 0x9E3779B97F4A7C15ull;
+    z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z | (1ull << 63);
+}
+
+bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counting)
+{
+    auto fail = [](const std::string& m) {
+        std::cerr << m << std::endl;
+        return false;
+    };
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
+    auto t0 = std::chrono::steady_clock::now();
+    for (Target& tg : targets)
+        if (!unite_files(c, tg))
+            return fail(gn_last_error());
+    const double hash_s = counting.seconds() + since(t0);
+    try
+    {
+        t0 = std::chrono::steady_clock::now();
+        gnhost::FilterMeta meta;
+        HibfDeviceSink     sink(c.device);
+        gnhost::load_filter_file(c.verify_index, true, meta, sink);
+        gn_filter* const flt    = sink.filter();
+        const double     load_s = since(t0);
+        std::vector<uint64_t> bins;
+        for (const gnhost::IbfShape& m : meta.shapes)
+            bins.push_back(m.bins);
+        const gnhibf::Paths paths  = gnhibf::derive_paths(bins, meta.next_ibf_id, meta.bin_to_user, meta.n_user_bins);
+        const uint32_t      depth  = paths.depth;
+        const uint64_t      n_user = meta.n_user_bins;
+        const unsigned      k = meta.ibf_config.kmer_size, h = (unsigned)meta.shapes.at(0).hash_funs;
+        const double        fpr = meta.ibf_config.max_fp;
+        std::map<std::string, uint64_t> user_of; // names as the loader recovers them -> user bin
+        for (size_t t = 0; t < meta.targets.size(); ++t)
+            user_of[meta.targets[t]] = meta.target_bins[t].at(0);
+        // the loader's own reading of the name this builder would write for a target
+        auto as_read = [](const std::string& target) {
+            std::string f     = fs::path(user_bin_file_name(target) + ".minimiser").filename().string();
+            size_t      found = f.find(".minimiser");
+            if (found != std::string::npos)
+                f = f.substr(0, found);
+            for (const auto& [from, to] : { std::pair<std::string, std::string>{ "|||", "." }, { "---", " " } })
+                for (size_t p = 0; (p = f.find(from, p)) != std::string::npos; p += to.size())
+                    f.replace(p, from.size(), to);
+            return f;
+        };
+
+        // membership: every target's set along its user bin's path, pooled as run_hibf pools its inserts
+        t0 = std::chrono::steady_clock::now();
+        constexpr uint64_t    none = ~0ull;
+        std::vector<uint64_t> user(targets.size(), none), found(targets.size(), 0), first_lost(targets.size(), none);
+        std::vector<uint64_t> lost_at(targets.size() * (size_t)depth, 0);
+        uint64_t              looked_up = 0;
+        {
+            constexpr uint64_t         kBatch = 16ull << 20, kAlone = 4ull << 20;
+            std::vector<uint64_t>      pool, off{ 0 }, r_found, r_lost, r_first;
+            std::vector<gn_path_entry> pp;
+            std::vector<size_t>        who;
+            auto probe = [&](const uint64_t* hashes, const uint64_t* set_off, const gn_path_entry* p, const std::vector<size_t>& ts) {
+                r_found.assign(ts.size(), 0), r_first.assign(ts.size(), none), r_lost.assign(ts.size() * (size_t)depth, 0);
+                if (gn_filter_probe_path(flt, hashes, set_off, (uint32_t)ts.size(), p, depth, r_found.data(), r_lost.data(), r_first.data()) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+                for (size_t j = 0; j < ts.size(); ++j)
+                {
+                    found[ts[j]] = r_found[j], first_lost[ts[j]] = r_first[j];
+                    std::copy(r_lost.begin() + j * depth, r_lost.begin() + (j + 1) * depth, lost_at.begin() + ts[j] * depth);
+                }
+            };
+            auto flush = [&] {
+                if (!who.empty())
+                    probe(pool.data(), off.data(), pp.data(), who);
+                pool.clear(), pp.clear(), who.clear(), off.assign(1, 0);
+            };
+            for (size_t t = 0; t < targets.size(); ++t)
+            {
+                const std::vector<uint64_t>& hs = targets[t].hashes;
+                auto                         it = user_of.find(as_read(targets[t].name));
+                if (it == user_of.end() || hs.empty())
+                {
+                    user[t] = it == user_of.end() ? none : it->second;
+                    continue;
+                }
+                user[t] = it->second;
+                looked_up += hs.size();
+                const gn_path_entry* p = &paths.entries[user[t] * depth];
+                if (hs.size() >= kAlone)
+                {
+                    const uint64_t one[2] = { 0, hs.size() };
+                    probe(hs.data(), one, p, { t });
+                    continue;
+                }
+                pool.insert(pool.end(), hs.begin(), hs.end());
+                off.push_back(pool.size());
+                pp.insert(pp.end(), p, p + depth);
+                who.push_back(t);
+                if (pool.size() >= kBatch)
+                    flush();
+            }
+            flush();
+        }
+        const double member_s = since(t0);
+
+        // false positives: the same P probes against every user bin of the file, paths sorted by (leaf ibf, first bin)
+        t0 = std::chrono::steady_clock::now();
+        const bool            fp_pass = k <= 31; // (k = 32: a hash can take any 64-bit value, no probe is a certain negative)
+        std::vector<uint64_t> false_hits(n_user, 0);
+        if (fp_pass && n_user)
+        {
+            std::vector<uint64_t> probes(kVerifyProbes), order(n_user), got(n_user, 0);
+            for (uint64_t i = 0; i < kVerifyProbes; ++i)
+                probes[i] = verify_probe(i);
+            for (uint64_t u = 0; u < n_user; ++u)
+                order[u] = u;
+            std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+                const gn_path_entry &x = paths.entries[a * depth], &y = paths.entries[b * depth];
+                return std::make_pair(x.ibf, x.first_bin) < std::make_pair(y.ibf, y.first_bin);
+            });
+            std::vector<gn_path_entry> sorted;
+            for (uint64_t u : order)
+                sorted.insert(sorted.end(), paths.entries.begin() + u * depth, paths.entries.begin() + (u + 1) * depth);
+            if (gn_filter_probe_paths_shared(flt, probes.data(), probes.size(), sorted.data(), (uint32_t)n_user, depth, got.data()) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+            for (uint64_t j = 0; j < n_user; ++j)
+                false_hits[order[j]] = got[j];
+        }
+        const double fp_s = since(t0);
+        const double P = (double)kVerifyProbes;
+        const uint64_t warn_above = (uint64_t)std::ceil(P * fpr + 4.0 * std::sqrt(P * fpr * (1.0 - fpr)));
+
+        std::cout << "index\t" << c.verify_index << "\tk=" << k << " w=" << meta.ibf_config.window_size << " h=" << h << " ibfs=" << meta.shapes.size()
+                  << " levels=" << depth << " user_bins=" << n_user << " fpr=" << fpr << "\n";
+        std::cout << "#target\tuser_bin\tleaf_ibf\tbins\tdepth\tdistinct_hashes\tmissing\tfalse_hits\tobserved_fp\tverdict\n";
+        uint64_t          n_checked = 0, n_bad = 0, fp_sum = 0, fp_max = 0;
+        std::vector<bool> named(n_user, false);
+        std::cout << std::fixed << std::setprecision(6);
+        for (size_t t = 0; t < targets.size(); ++t)
+        {
+            const std::vector<uint64_t>& hs = targets[t].hashes;
+            if (user[t] == none)
+            {
+                // a target without a hash has no user bin in an index built from these inputs: nothing to look for
+                std::cout << targets[t].name << "\t-\t-\t0\t0\t" << hs.size() << "\t0\t" << (fp_pass ? "0" : "n/a") << "\t" << (fp_pass ? "0.000000" : "n/a") << "\t"
+                          << (hs.empty() ? "ok" : "FAIL: no such user bin") << "\n";
+                n_bad += !hs.empty();
+                continue;
+            }
+            const gn_path_entry* p = &paths.entries[user[t] * depth];
+            uint32_t             used = 0;
+            while (used < depth && p[used].n_bins)
+                ++used;
+            const uint64_t missing = hs.size() - found[t], hits = false_hits[user[t]];
+            const bool     warn    = fp_pass && hits > warn_above;
+            ++n_checked;
+            named[user[t]] = true;
+            n_bad += missing != 0;
+            fp_sum += hits, fp_max = std::max(fp_max, hits);
+            std::cout << targets[t].name << "\t" << user[t] << "\t" << p[0].ibf << "\t" << p[0].n_bins << "\t" << used << "\t" << hs.size() << "\t" << missing << "\t";
+            if (fp_pass)
+                std::cout << hits << "\t" << hits / P;
+            else
+                std::cout << "n/a\tn/a";
+            std::cout << "\t" << (missing ? "FAIL" : warn ? "WARN fp" : "ok") << "\n";
+            if (missing)
+            {
+                // the first false negative: its hash, the first entry of the path that lacks it, its h rows there and the bits found
+                const uint64_t        v = hs[first_lost[t]], one[2] = { 0, 1 };
+                uint64_t              f1 = 0, fl = 0;
+                std::vector<uint64_t> l1(depth, 0);
+                if (gn_filter_probe_path(flt, &v, one, 1, p, depth, &f1, l1.data(), &fl) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+                uint32_t d = 0;
+                while (d + 1 < used && l1[d] == 0)
+                    ++d;
+                const gnhost::IbfShape& m = meta.shapes.at(p[d].ibf);
+                std::vector<uint64_t>   rows(m.hash_funs), words(m.hash_funs * m.bin_words);
+                for (unsigned i = 0; i < m.hash_funs; ++i)
+                    rows[i] = gnhost::ibf_row(v, i, m);
+                if (gn_filter_download_row_list(flt, p[d].ibf, rows.data(), rows.size(), words.data()) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+                std::cout << "  first false negative: hash " << v << " (index " << first_lost[t] << " of the sorted distinct hashes); lost at level " << d << ", ibf "
+                          << p[d].ibf << ", bins " << p[d].first_bin << ".." << p[d].first_bin + p[d].n_bins - 1 << "; rows";
+                for (auto r : rows)
+                    std::cout << " " << r;
+                std::cout << "; bits [bin: one per hash function]";
+                for (uint32_t b = p[d].first_bin; b < p[d].first_bin + p[d].n_bins && b < p[d].first_bin + 8; ++b)
+                {
+                    std::cout << " [" << b << ":";
+                    for (unsigned i = 0; i < m.hash_funs; ++i)
+                        std::cout << " " << ((words[i * m.bin_words + (b >> 6)] >> (b & 63)) & 1);
+                    std::cout << "]";
+                }
+                std::cout << "\n";
+            }
+        }
+        uint64_t unnamed = 0;
+        for (uint64_t u = 0; u < n_user; ++u)
+            unnamed += !named[u];
+        std::cout << "result\t" << (n_bad ? "FAIL" : "ok") << "\t" << n_checked << " target(s) checked, " << n_bad << " failing, " << unnamed
+                  << " user bin(s) of the index not named by the input, " << looked_up << " distinct minimisers looked up, max_observed_fp ";
+        if (fp_pass)
+            std::cout << fp_max / P << ", mean_observed_fp " << (n_checked ? fp_sum / P / (double)n_checked : 0.0);
+        else
+            std::cout << "n/a, mean_observed_fp n/a";
+        std::cout << std::endl;
+        if (c.verbose && !c.quiet)
+            std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " membership " << member_s << " fp " << fp_s << std::endl;
+        return n_bad == 0 && n_checked > 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(std::string("ERROR: ") + e.what());
+    }
+}
+
 bool run(Config c)
 {
     if (!validate(c))
@@ -1066,6 +1437,8 @@ bool run(Config c)
     }
     counting.stop();
 
+    if (c.verify_given)
+        return run_verify(c, targets, counting);
     if (c.hibf)
         return run_hibf(c, targets, totals, whole, counting);
 

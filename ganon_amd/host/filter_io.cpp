@@ -627,6 +627,14 @@ void load_filter_file(const std::string& path, bool hibf, FilterMeta& meta, Filt
         load_ibf(path, meta, sink);
 }
 
+void read_hibf_meta(const std::string& path, FilterMeta& meta)
+{
+    meta = FilterMeta();
+    Reader                r(path);
+    std::vector<uint64_t> payload_at;
+    parse_hibf(r, meta, payload_at);
+}
+
 bool inspect_filter_file(const std::string& path, bool hibf, std::ostream& out)
 {
     FilterMeta meta;

@@ -16,6 +16,8 @@
 // instead of classifying against a misread filter.
 #pragma once
 
+#include "ganon_ibf_hash.h"
+
 #include <cstdint>
 #include <iosfwd>
 #include <map>
@@ -30,6 +32,17 @@ struct IbfShape
     uint64_t bins = 0, technical_bins = 0, bin_size = 0, hash_shift = 0, bin_words = 0, hash_funs = 0;
     uint64_t payload_bytes() const { return bin_size * bin_words * 8; }
 };
+
+// seqan3::interleaved_bloom_filter::hash_and_fit: the row of hash v under hash function i in an IBF of this shape.
+// For the reports of a false negative (verify.cpp, `ganon-build --verify-index`); the kernels have their own (gn_build_row.h).
+inline uint64_t ibf_row(uint64_t v, unsigned i, const IbfShape& m)
+{
+    static const uint64_t seeds[GN_IBF_MAX_HASH_FUNS] = GN_IBF_SEED_LIST; // include/ganon_ibf_hash.h
+    uint64_t              x = v * seeds[i];
+    x ^= x >> m.hash_shift;
+    x *= GN_IBF_MULTIPLIER;
+    return (uint64_t)(((unsigned __int128)x * m.bin_size) >> 64);
+}
 
 // IBFConfig.hpp:3-41
 struct IBFConfig
@@ -84,6 +97,9 @@ const LoadTiming& last_load_timing();
 // Parse `path` (.ibf, or .hibf when `hibf`), fill `meta`, stream the bits into `sink`.  Throws std::runtime_error
 // with a descriptive message on malformed input or when the sink reports an error.
 void load_filter_file(const std::string& path, bool hibf, FilterMeta& meta, FilterSink& sink);
+
+// Everything of a raptor .hibf but its bits (what load_filter_file leaves in `meta`): no sink, no device.  Throws likewise.
+void read_hibf_meta(const std::string& path, FilterMeta& meta);
 
 // `ganon-classify --inspect-filter`: parse the file's metadata only (no device, no bits), print every header field with its
 // offset and every redundancy check (technical_bins == 64*bin_words, hash_shift == countl_zero(bin_size), the bit_vector

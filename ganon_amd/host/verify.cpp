@@ -14,7 +14,6 @@
 #include "seq_io.hpp"
 
 #include "ganon_hip.h"
-#include "ganon_ibf_hash.h"
 
 #include <fstream>
 #include <iostream>
@@ -105,16 +104,6 @@ private:
     gn_filter* f_     = nullptr;
     Stage      stage_[2];
 };
-
-// seqan3::interleaved_bloom_filter::hash_and_fit, for the report of a false negative only
-uint64_t ibf_row(uint64_t v, unsigned i, const IbfShape& m)
-{
-    static const uint64_t seeds[GN_IBF_MAX_HASH_FUNS] = GN_IBF_SEED_LIST; // include/ganon_ibf_hash.h
-    uint64_t              x = v * seeds[i];
-    x ^= x >> m.hash_shift;
-    x *= GN_IBF_MULTIPLIER;
-    return (uint64_t)(((unsigned __int128)x * m.bin_size) >> 64);
-}
 
 } // namespace
 

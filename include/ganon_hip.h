@@ -423,6 +423,29 @@ int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* siz
 int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
                            uint32_t depth);
 
+/* `ganon-build --hibf --verify-index`: the insert read back.  Same sets, same paths, same hashes; loads where gn_filter_emplace_path ORs.
+ * set s = hashes[set_off[s] .. set_off[s+1]) (host memory; any order, repeats allowed).  A hash is CONTAINED in an entry when, for at
+ * least one bin of first_bin .. first_bin + n_bins - 1, all h rows have that bin's bit set (hashes_per_bin is ignored: a foreign
+ * builder may have dealt the hashes to the run's bins in another order).  n_bins == 0 ends a path shorter than `depth`, as above; the
+ * entries from there on are unused.
+ * gn_filter_probe_path:
+ *   lost_at[s * depth + d] = hashes of set s not contained in entry d, each entry counted on its own (0 for unused entries); may be NULL
+ *   found[s]               = hashes of set s contained in every used entry
+ *   first_lost[s]          = smallest index within set s of a hash that is not, ~0 when none
+ * gn_filter_probe_paths_shared: the same n probes against each of n_paths paths, found[p] = probes contained in every used entry of
+ *   path p.  Results do not depend on the order of the paths; sorted by (leaf ibf, first bin) neighbouring paths share what they read.
+ * Both: GN_EINVAL for a filter that is not an HIBF, a null argument (lost_at excepted), an IBF or a bin out of range -- everything is
+ * checked before anything is launched.  n_sets == 0, n_paths == 0, n == 0 and empty sets are legal (found 0, first_lost ~0).
+ *
+ * The probes `ganon-build --verify-index` measures false positives with -- values no (k,w)-minimiser hash with k <= 31 can take,
+ * since such a hash is below 4^k <= 2^62: for i = 0 .. P - 1, in 64-bit wrapping arithmetic,
+ *     z = (i + 1) * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31
+ *     probe_i = z | 2^63 */
+int gn_filter_probe_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                         uint32_t depth, uint64_t* found, uint64_t* lost_at, uint64_t* first_lost);
+int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths,
+                                 uint32_t depth, uint64_t* found);
+
 /* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.

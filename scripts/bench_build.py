@@ -9,6 +9,9 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
                   similarity build also reports layout_s, the part of union_s that went into sketches, union tables and search,
                   a similarity build its split (layout_sketches_s, layout_tables_s, layout_pairs_s, layout_host_s) and the
                   tree it kept.
+  --verify        [--hibf] after each --hibf build of a run the file is checked (`ganon-build --hibf --verify-index`): verify_hash_s,
+                  verify_load_s, verify_membership_s (beside emplace_s of the same build: the same hashes along the same paths) and
+                  verify_fp_s, max_observed_fp / mean_observed_fp against --max-fp, the number of WARN and of FAIL lines
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
@@ -25,11 +28,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": ""}
-pos, hibf, argv = [], False, sys.argv[1:]
+pos, hibf, check, argv = [], False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
     if a == "--hibf":
         hibf = True
+    elif a == "--verify":
+        check = True
     elif a in opts:
         opts[a] = argv.pop(0)
     else:
@@ -132,6 +137,29 @@ def hibf_run(layout=""):
     if p.returncode == 0:
         res["hibf_bytes"] = os.path.getsize(os.path.join(d, "db.hibf"))
         res["mbp_per_s"] = round(total_bases / 1e6 / res.get("total_s", res["wall_s"]), 1)
+        if check:
+            res.update(verify_run())
+    return res
+
+
+def verify_run():
+    """the index just written against the inputs it was built from"""
+    res = {}
+    t0 = time.time()
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "--hibf", "--verify-index", os.path.join(d, "db.hibf"), "-t", str(threads), "--verbose"],
+                       capture_output=True, text=True)
+    res["verify_rc"], res["verify_wall_s"] = p.returncode, round(time.time() - t0, 2)
+    m = re.search(r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) membership ([0-9.eE+-]+) fp ([0-9.eE+-]+)", p.stderr)
+    if m:
+        res["verify_hash_s"], res["verify_load_s"], res["verify_membership_s"], res["verify_fp_s"] = (float(x) for x in m.groups())
+    m = re.search(r"max_observed_fp ([0-9.]+), mean_observed_fp ([0-9.]+)", p.stdout)
+    if m:
+        res["max_observed_fp"], res["mean_observed_fp"] = float(m.group(1)), float(m.group(2))
+    lines = [ln for ln in p.stdout.splitlines()[2:] if not ln.startswith(("result\t", "  first false negative"))]
+    res["verify_warn_lines"] = sum(ln.endswith("\tWARN fp") for ln in lines)
+    res["verify_fail_lines"] = sum("\tFAIL" in ln for ln in lines)
+    m = re.search(r"^result\t.*", p.stdout, re.M)
+    res["verify_result"] = m.group(0) if m else (p.stderr or p.stdout)[-300:]
     return res
 
 
