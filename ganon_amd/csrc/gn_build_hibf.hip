@@ -6,6 +6,8 @@
 //                            and ORed into h rows of EVERY IBF on its path (the user bin's own run of bins in its leaf IBF, one
 //                            merged bin in each IBF above).  Inserting every member's set into a merged bin sets the bits the
 //                            union of the sets would: the unions are never materialised.
+//   gn_filter_bin_popcounts  set bits per technical bin of an IBF: how full each bin of an index is (towards `--update`)
+//   gn_filter_copy_ibf       an IBF into one with more bins, device to device
 // No counterpart in the reference's own sources: `ganon build --filter-type hibf` runs `raptor build`
 // (/root/reference/src/ganon/build_update.py:411-518).  HBM-bound integer work: depth * h atomic ORs per hash, each to a row
 // of its own.
@@ -511,5 +513,333 @@ extern "C" int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes
     GN_HIP(hipGetLastError());
     GN_HIP(hipStreamSynchronize(f->load_st));
     GN_HIP(hipMemcpy(found, d_found, (size_t)n_paths * 8, hipMemcpyDeviceToHost));
+    return GN_OK;
+}
+
+// ---- gn_filter_bin_popcounts: how full is every technical bin? -------------------------------------------------------------------
+// A .hibf does not record how many hashes went into a bin; the set bits of the bin's column are all there is (`ganon-build --hibf
+// --update` decides from them where a new user bin still fits).  counts[b] = rows whose bit b is set: a column sum over the whole
+// bit matrix, every word read once.
+//
+// A lane owns one 64-bit word column and walks a tile of rows; neighbouring lanes read neighbouring words:
+//   rows of at most 64 words   the matrix is one flat array: the wave reads g = 64 / Ws whole rows (g * Ws contiguous words) per step,
+//                              lane l owns column l % Ws.  Where 64 is a multiple of Ws every lane works; otherwise 64 % Ws lanes idle.
+//   wider rows                 chunks of 64 word columns: lane l of chunk c owns column 64 c + l and reads one row per step.
+// Both are one address rule: word (tile * T + j) * step + c0 + l for j = 0 .. T - 1, valid while below S * Ws.
+// The 64 per-bit counters of a lane are not touched per word.  16 loads are issued, then the 16 words go through a carry-save adder
+// tree (15 adders of 5 logic operations on 64 bits) into 8 vertical bit planes -- plane k holds bit k of every bit position's count --
+// and after 240 words (<= 255, what 8 planes hold) the planes are added into 64 32-bit counters in registers, the plane bits of four
+// bit positions gathered into the bytes of one register at a time.  The steps in which every lane has a word run without a
+// predicate; what is left of a tile (fewer than 16 steps, the matrix's last one perhaps cut) is one predicated block.
+// At the end of the tile lanes that own the same column add up (Ws a power of two) and every counter leaves as one 64-bit atomicAdd.
+#define GN_POP_FLUSH 240u // words between two flushes of the planes: a multiple of 16, at most 255
+
+struct GnPopParams
+{
+    const uint64_t* rows;
+    uint64_t        n_words; // S * Ws
+    uint64_t        step;    // words from one of a lane's words to its next
+    uint64_t        tile;    // steps a wave walks (a multiple of GN_POP_FLUSH)
+    uint64_t        whole_steps; // steps, from the matrix's first, in which every lane with a column has a word
+    uint64_t        n_tiles;
+    uint32_t        Ws, W, B;
+    uint32_t        lanes;   // lanes of a wave that own a column (flat), 64 (chunks)
+    uint32_t        chunked; // 0: flat, 1: chunks of 64 word columns
+    uint32_t        fold;    // flat, Ws a power of two below 64: lanes l and l + Ws own the same column
+};
+
+// a value that is the same in every lane, moved to where the compiler knows it
+__device__ __forceinline__ uint64_t gn_uniform64(uint64_t v)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
+}
+
+#define GN_CSA(hi, lo, a, b, c)                \
+    {                                          \
+        const uint64_t u_ = (a) ^ (b);         \
+        const uint64_t c_ = (c);               \
+        hi                = ((a) & (b)) | (u_ & c_); \
+        lo                = u_ ^ c_;           \
+    }
+
+// 8 words into the planes ones / twos / fours; the carry of weight 8 is returned
+__device__ __forceinline__ uint64_t gn_pop_eight(const uint64_t (&x)[8], uint64_t& ones, uint64_t& twos, uint64_t& fours)
+{
+    uint64_t ta, tb, fa, fb, e;
+    GN_CSA(ta, ones, ones, x[0], x[1]);
+    GN_CSA(tb, ones, ones, x[2], x[3]);
+    GN_CSA(fa, twos, twos, ta, tb);
+    GN_CSA(ta, ones, ones, x[4], x[5]);
+    GN_CSA(tb, ones, ones, x[6], x[7]);
+    GN_CSA(fb, twos, twos, ta, tb);
+    GN_CSA(e, fours, fours, fa, fb);
+    return e;
+}
+
+// planes -> counters: for bit positions s, s + 8, s + 16, s + 24 of one 32-bit half, the 8 plane bits are gathered into one byte each
+__device__ __forceinline__ void gn_pop_flush(uint64_t (&p)[8], uint32_t (&cnt)[64])
+{
+#pragma unroll
+    for (uint32_t half = 0; half < 2; ++half)
+    {
+        uint32_t q[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k)
+            q[k] = (uint32_t)(p[k] >> (32u * half));
+#pragma unroll
+        for (uint32_t s = 0; s < 8; ++s)
+        {
+            uint32_t v = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k)
+                v |= (k >= s ? q[k] << (k - s) : q[k] >> (s - k)) & (0x01010101u << k);
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i)
+                cnt[half * 32u + i * 8u + s] += (v >> (8u * i)) & 0xFFu;
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k)
+        p[k] = 0;
+}
+
+__global__ __launch_bounds__(256) void gn_bin_popcount_kernel(const GnPopParams P, unsigned long long* __restrict__ counts)
+{
+    // (tile and chunk are the same in every lane: through readfirstlane, so that everything derived from them is scalar arithmetic)
+    const uint64_t tile = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    const uint32_t c0   = blockIdx.y * 64u; // (0 unless chunked)
+    if (tile >= P.n_tiles) // (the waves that fill up the last block)
+        return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t col  = P.chunked ? c0 + lane : lane % P.Ws;
+    const bool     mine = P.chunked ? col < P.W : lane < P.lanes;
+    // A load is a wave-uniform base (scalar arithmetic) plus the lane's own 32-bit byte offset, which never changes.  A lane without a
+    // column reads what the wave's first lane reads (inside the matrix wherever that lane is) and drops its counters.
+    // (there is no scalar 64-bit multiply: the products are made once, handed to the scalar unit, and only added to from there on)
+    const uint64_t step0 = gn_uniform64(tile * P.tile);            // the tile's first step ...
+    const uint64_t first = gn_uniform64(step0 * P.step + c0);      // ... and the wave's first word: below n_words, since the tile exists
+    const uint64_t whole = P.whole_steps > step0 ? min(P.whole_steps - step0, P.tile) : 0; // steps of the tile every lane has a word in
+    const uint32_t loff  = mine ? lane : 0u;
+    const uint32_t boff  = loff * 8u;
+    typedef const __attribute__((address_space(1))) char GnGlobalConstByte;
+    GnGlobalConstByte* src = (GnGlobalConstByte*)P.rows;
+
+    uint32_t cnt[64];
+#pragma unroll
+    for (uint32_t b = 0; b < 64; ++b)
+        cnt[b] = 0;
+    uint64_t p[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k)
+        p[k] = 0;
+
+    // 16 words through the adder tree: 15 adders, and a half adder per plane above for the carry of weight 16
+    auto add16 = [&](const uint64_t (&xa)[8], const uint64_t (&xb)[8]) {
+        const uint64_t ea = gn_pop_eight(xa, p[0], p[1], p[2]);
+        const uint64_t eb = gn_pop_eight(xb, p[0], p[1], p[2]);
+        uint64_t       carry;
+        GN_CSA(carry, p[3], p[3], ea, eb);
+#pragma unroll
+        for (uint32_t k = 4; k < 8; ++k)
+        {
+            const uint64_t t = p[k] & carry;
+            p[k] ^= carry;
+            carry = t;
+        }
+    };
+
+    uint64_t at    = first; // the wave's word of the next step
+    uint32_t since = 0;     // words in the planes
+    for (uint64_t j = 0; j + 16u <= whole; j += 16u)
+    {
+        uint64_t xa[8], xb[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i, at += P.step)
+            xa[i] = *(GnGlobalConstWord*)(src + at * 8u + boff);
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i, at += P.step)
+            xb[i] = *(GnGlobalConstWord*)(src + at * 8u + boff);
+        add16(xa, xb);
+        since += 16u;
+        if (since == GN_POP_FLUSH)
+        {
+            gn_pop_flush(p, cnt);
+            since = 0;
+        }
+    }
+    // What is left of the tile is less than 16 steps: up to 15 whole ones and the matrix's last, which may end inside the wave.  A step
+    // outside reads the wave's first word and counts as zero; lim = the lanes' offsets that are inside (the same in every lane).
+    const uint64_t done = whole & ~15ull;
+    if (done < P.tile && at < P.n_words)
+    {
+        uint64_t x[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i, at += P.step)
+        {
+            const uint32_t lim = (done + i < P.tile && at < P.n_words) ? (uint32_t)min((uint64_t)64u, P.n_words - at) : 0u;
+            const uint64_t v   = *(GnGlobalConstWord*)(src + (lim ? at : first) * 8u + (loff < lim ? boff : 0u));
+            x[i]               = loff < lim ? v : 0;
+        }
+        uint64_t xa[8], xb[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i)
+        {
+            xa[i] = x[i];
+            xb[i] = x[8 + i];
+        }
+        add16(xa, xb);
+        since += 16u;
+    }
+    if (since)
+        gn_pop_flush(p, cnt);
+
+    if (P.fold)
+        for (uint32_t off = 32; off >= P.Ws; off >>= 1)
+#pragma unroll
+            for (uint32_t b = 0; b < 64; ++b)
+                cnt[b] += (uint32_t)__shfl_xor((int)cnt[b], (int)off);
+    if (!mine || col >= P.W || (P.fold && lane >= P.Ws))
+        return;
+#pragma unroll
+    for (uint32_t b = 0; b < 64; ++b)
+    {
+        const uint32_t bin = col * 64u + b;
+        uint32_t       c;
+        // (a copy the compiler cannot see through: otherwise every counter lives in the lower half of a register PAIR from the start,
+        // the upper half kept free for the zero of this 64-bit operand -- 64 registers and a wave per SIMD)
+        asm volatile("v_mov_b32 %0, %1" : "=&v"(c) : "v"(cnt[b]));
+        if (bin < P.B && c)
+            atomicAdd(&counts[bin], (unsigned long long)c);
+    }
+}
+
+// IBF `ibf_idx` of a filter (0 of a flat one), or nullptr
+static const GnIbfHost* gn_build_ibf(const gn_filter* f, uint32_t ibf_idx)
+{
+    if (f->is_hibf)
+        return ibf_idx < f->ibfs.size() ? &f->ibfs[ibf_idx] : nullptr;
+    return ibf_idx == 0 ? &f->ibf : nullptr;
+}
+
+extern "C" int gn_filter_bin_popcounts(const gn_filter* f, uint32_t ibf_idx, uint64_t* counts)
+{
+    if (!f || !counts)
+        return gn_fail(GN_EINVAL, "gn_filter_bin_popcounts: null argument");
+    const GnIbfHost* ib = gn_build_ibf(f, ibf_idx);
+    if (!ib || !ib->d_rows)
+        return gn_fail(GN_EINVAL, "gn_filter_bin_popcounts: ibf %u of %zu", ibf_idx, f->is_hibf ? f->ibfs.size() : (size_t)1);
+    GnPopParams P{};
+    P.rows    = ib->d_rows.get();
+    P.n_words = ib->S * ib->Ws;
+    P.Ws      = (uint32_t)ib->Ws;
+    P.W       = (uint32_t)ib->W;
+    P.B       = (uint32_t)ib->B;
+    P.chunked = ib->Ws > 64 ? 1u : 0u;
+    uint64_t steps, chunks = 1;
+    if (P.chunked)
+    {
+        P.step  = ib->Ws;
+        P.lanes = 64;
+        steps   = ib->S;
+        chunks  = (ib->W + 63) / 64;
+        P.whole_steps = ib->S;
+    }
+    else
+    {
+        const uint64_t g = 64 / ib->Ws; // whole rows a wave reads per step
+        P.step           = g * ib->Ws;
+        P.lanes          = (uint32_t)P.step;
+        P.fold           = (ib->Ws < 64 && (ib->Ws & (ib->Ws - 1)) == 0) ? 1u : 0u;
+        steps            = (ib->S + g - 1) / g;
+        P.whole_steps    = ib->S / g;
+    }
+    // about 8192 waves over the device, and tiles of at least 960 steps: a wave's 64 * Ws atomics then follow 60 KiB of reads or more
+    const uint64_t per_chunk = std::max<uint64_t>(1, 8192 / chunks);
+    uint64_t       tile      = std::max<uint64_t>(4 * GN_POP_FLUSH, (steps + per_chunk - 1) / per_chunk);
+    tile                     = (tile + GN_POP_FLUSH - 1) / GN_POP_FLUSH * GN_POP_FLUSH;
+    P.tile                   = tile;
+    P.n_tiles                = (steps + tile - 1) / tile;
+    if ((P.n_tiles + 3) / 4 > 0x7FFFFFFFull || chunks > 65535 || tile > (1ull << 25)) // (a 32-bit counter takes a tile of up to 64 lanes)
+        return gn_fail(GN_ERANGE, "gn_filter_bin_popcounts: %llu rows of %llu words in one call", (unsigned long long)ib->S, (unsigned long long)ib->Ws);
+    GN_HIP(hipSetDevice(f->device));
+    GnDev<unsigned long long> d_counts;
+    GN_HIP(d_counts.alloc(ib->B));
+    GN_HIP(hipMemsetAsync(d_counts, 0, ib->B * 8, nullptr));
+    hipLaunchKernelGGL(gn_bin_popcount_kernel, dim3((uint32_t)((P.n_tiles + 3) / 4), (uint32_t)chunks), dim3(256), 0, nullptr, P, d_counts.get());
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipMemcpy(counts, d_counts, ib->B * 8, hipMemcpyDeviceToHost)); // (the null stream: after the kernel)
+    return GN_OK;
+}
+
+// ---- gn_filter_copy_ibf: an IBF into one with more bins ----------------------------------------------------------------------------
+// Row by row, device to device: words [0, W_src) of a row are the source's, the words from there to the destination's stride are zero.
+// A thread moves V words (V = 2: 16 bytes, when both strides are even); it finds its row and word once and then steps by the grid.
+template <uint32_t V>
+__global__ __launch_bounds__(256) void gn_copy_ibf_kernel(uint64_t* __restrict__ dst, const uint64_t* __restrict__ src, uint64_t S, uint32_t Ws_dst,
+                                                          uint32_t Ws_src, uint32_t W_src, uint64_t step_rows, uint32_t step_units)
+{
+    const uint32_t units = Ws_dst / V; // of V words, in a destination row
+    const uint64_t gid   = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t       r     = gid / units;
+    uint32_t       u     = (uint32_t)(gid % units);
+    for (; r < S; r += step_rows)
+    {
+        const uint32_t w = u * V;
+        if (V == 2)
+        {
+            ulonglong2 v = make_ulonglong2(0, 0);
+            if (w < W_src) // (w + 1 is below the source's even stride; the source's words beyond W_src are not trusted to be zero)
+            {
+                v = *reinterpret_cast<const ulonglong2*>(src + r * Ws_src + w);
+                if (w + 1 >= W_src)
+                    v.y = 0;
+            }
+            *reinterpret_cast<ulonglong2*>(dst + r * Ws_dst + w) = v;
+        }
+        else
+            dst[r * Ws_dst + w] = w < W_src ? src[r * Ws_src + w] : 0;
+        u += step_units;
+        if (u >= units)
+        {
+            u -= units;
+            ++r;
+        }
+    }
+}
+
+extern "C" int gn_filter_copy_ibf(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf)
+{
+    if (!dst || !src)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: null argument");
+    if (!dst->is_hibf || !src->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf needs two HIBF filters");
+    if (dst->device != src->device)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: the filters are on devices %d and %d", dst->device, src->device);
+    if (dst_ibf >= dst->ibfs.size() || src_ibf >= src->ibfs.size())
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: ibf %u of %zu into ibf %u of %zu", src_ibf, src->ibfs.size(), dst_ibf, dst->ibfs.size());
+    GnIbfHost&       d = dst->ibfs[dst_ibf];
+    const GnIbfHost& s = src->ibfs[src_ibf];
+    if (d.d_rows.get() == s.d_rows.get())
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: an IBF onto itself");
+    if (d.S != s.S || d.h != s.h)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: %llu rows and %u hash functions into %llu rows and %u", (unsigned long long)s.S, s.h,
+                       (unsigned long long)d.S, d.h);
+    if (d.W < s.W)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf: rows of %llu words into rows of %llu", (unsigned long long)s.W, (unsigned long long)d.W);
+    GN_HIP(hipSetDevice(dst->device));
+    const bool     wide    = (d.Ws % 2 == 0) && (s.Ws % 2 == 0);
+    const uint64_t units   = d.Ws / (wide ? 2 : 1);
+    const uint64_t total   = d.S * units;
+    const uint64_t blocks  = std::min<uint64_t>((total + 255) / 256, (uint64_t)dst->n_cu * 16);
+    const uint64_t threads = blocks * 256;
+    if (wide)
+        hipLaunchKernelGGL(gn_copy_ibf_kernel<2>, dim3((uint32_t)blocks), dim3(256), 0, nullptr, d.d_rows.get(), s.d_rows.get(), d.S, (uint32_t)d.Ws,
+                           (uint32_t)s.Ws, (uint32_t)s.W, threads / units, (uint32_t)(threads % units));
+    else
+        hipLaunchKernelGGL(gn_copy_ibf_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, nullptr, d.d_rows.get(), s.d_rows.get(), d.S, (uint32_t)d.Ws,
+                           (uint32_t)s.Ws, (uint32_t)s.W, threads / units, (uint32_t)(threads % units));
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipDeviceSynchronize());
     return GN_OK;
 }

@@ -33,6 +33,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
+               "gn_filter_bin_popcounts", "gn_filter_copy_ibf",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
 
 
@@ -164,6 +165,8 @@ def load_library():
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
     L.gn_filter_probe_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
     L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
+    L.gn_filter_bin_popcounts.argtypes = [vp, u32, vp]
+    L.gn_filter_copy_ibf.argtypes = [vp, u32, vp, u32]
     L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
     L.gn_sketches_free.argtypes = [vp]
     L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
@@ -552,9 +555,10 @@ class HipSketches:
 class HipFilter:
     """Device-resident, immutable IBF / HIBF (gn_filter)."""
 
-    def __init__(self, handle, keep=None):
+    def __init__(self, handle, keep=None, bins=None):
         self._h = handle
         self._keep = keep
+        self._bins = list(bins) if bins is not None else None  # technical bins per IBF (one entry for a flat filter), when known
 
     @classmethod
     def ibf(cls, rows: Optional[np.ndarray], bins: int, bin_size: int, hash_funs: int,
@@ -568,7 +572,7 @@ class HipFilter:
         d = _desc(rows, bins, bin_size, hash_funs)
         h = C.c_void_p()
         _check(load_library().gn_filter_upload_ibf(device, C.byref(d), _p(bin2target), n_targets, C.byref(h)))
-        return cls(h)
+        return cls(h, bins=[bins])
 
     @classmethod
     def hibf(cls, ibfs: Sequence[Tuple[np.ndarray, int, int, int]], next_ibf_id: Sequence[np.ndarray],
@@ -582,7 +586,7 @@ class HipFilter:
         bup = (C.c_void_p * n)(*[a.ctypes.data for a in bu])
         h = C.c_void_p()
         _check(load_library().gn_filter_upload_hibf(device, n, descs, nxp, bup, n_user_bins, C.byref(h)))
-        return cls(h, keep=(nx, bu))
+        return cls(h, keep=(nx, bu), bins=[b for _, b, _, _ in ibfs])
 
     def emplace(self, hashes: np.ndarray, bins: np.ndarray, ibf_idx: int = 0) -> None:
         hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
@@ -625,6 +629,26 @@ class HipFilter:
         _check(load_library().gn_filter_probe_paths_shared(self._h, _p(probes), len(probes), paths.ctypes.data_as(C.c_void_p), paths.shape[0],
                                                            paths.shape[1], _p(found)))
         return found
+
+    def bin_popcounts(self, bins: Optional[int] = None, ibf_idx: int = 0) -> np.ndarray:
+        """gn_filter_bin_popcounts: set bits per technical bin of IBF ibf_idx -> uint64 [bins of that IBF].  The library writes as many
+        counts as the IBF has bins, so the buffer is sized from the shapes the filter was created with; `bins`, when given, has to agree
+        (a filter wrapped around a bare handle knows no shapes: `bins` is then required and trusted)."""
+        if self._bins is not None:
+            if not 0 <= ibf_idx < len(self._bins):
+                raise GanonHipError(-22, f"gn_filter_bin_popcounts: ibf {ibf_idx} of {len(self._bins)}")
+            if bins is not None and bins != self._bins[ibf_idx]:
+                raise ValueError(f"IBF {ibf_idx} has {self._bins[ibf_idx]} bins, not {bins}")
+            bins = self._bins[ibf_idx]
+        elif bins is None:
+            raise ValueError("bins is required for a filter whose shapes are not known")
+        out = np.zeros(bins, dtype=np.uint64)
+        _check(load_library().gn_filter_bin_popcounts(self._h, ibf_idx, _p(out)))
+        return out
+
+    def copy_ibf(self, dst_ibf: int, src: "HipFilter", src_ibf: int) -> None:
+        """gn_filter_copy_ibf: IBF src_ibf of the HIBF `src` into this HIBF's IBF dst_ibf (same rows, at least as many bins)"""
+        _check(load_library().gn_filter_copy_ibf(self._h, dst_ibf, src._h, src_ibf))
 
     def probe(self, hashes: np.ndarray, bins: np.ndarray) -> Tuple[int, int, int]:
         """gn_filter_probe -> (hits summed over the bins, hashes in none of the bins, index of the first such hash or -1)"""

@@ -38,6 +38,7 @@
 #include "hasher.hpp"
 #include "hibf_layout.hpp"
 #include "hibf_paths.hpp"
+#include "hibf_update.hpp"
 #include "hibf_layout_similarity.hpp"
 #include "hibf_layout_sketch.hpp"
 #include "hostmem.hpp"
@@ -91,6 +92,8 @@ struct Config // Config.hpp:10-27
                                  //  similarity = hibf_layout_similarity.hpp: sketch over an order that groups related targets)
     bool        layout_given = false;
     std::string verify_index;    // (--hibf only: check this index against the inputs instead of building one)
+    std::string update;          // (--hibf only: add the inputs' targets to this index and write the result to --output-file)
+    bool        update_given = false, max_fp_given = false, mode_given = false;
     bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
 };
 
@@ -107,6 +110,62 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--layout needs --hibf");
     if (c.layout_given && c.layout != "rule" && c.layout != "sketch" && c.layout != "similarity")
         return say("--layout has to be rule, sketch or similarity");
+    if (c.update_given)
+    {
+        if (!c.hibf)
+            return say("--update needs --hibf (it adds targets to a hierarchical index; a flat .ibf is rebuilt)");
+        if (!c.output_given || c.output_file.empty())
+            return say("--update needs --output-file (the updated index is written there; the index given is left as it is)");
+        if (c.verify_given)
+            return say("--update cannot be used with --verify-index (update first, then check the file written)");
+        if (c.layout_given)
+            return say("--update cannot be used with --layout (the tree of the index is kept)");
+        if (c.tmax_given)
+            return say("--update cannot be used with --tmax (the tree of the index is kept; an updated IBF is not held to a tmax)");
+        if (c.filter_size_given)
+            return say("--update cannot be used with --filter-size (the IBFs keep their rows)");
+        if (c.mode_given)
+            return say("--update cannot be used with --mode");
+        if (c.update.empty() || !fs::exists(c.update))
+        {
+            if (!c.quiet)
+                std::cerr << "--update not found: " << c.update << std::endl;
+            return false;
+        }
+        {
+            std::error_code ec;
+            if (fs::exists(c.output_file) && fs::equivalent(c.update, c.output_file, ec))
+                return say("--update: --output-file is the index itself (it is read while the new one is written: give another file)");
+        }
+        // k, w, the number of hash functions and the false-positive rate are the file's; a value given on the command line has to agree
+        try
+        {
+            gnhost::FilterMeta meta;
+            gnhost::read_hibf_meta(c.update, meta);
+            const unsigned k = meta.ibf_config.kmer_size, w = meta.ibf_config.window_size, h = (unsigned)meta.shapes.at(0).hash_funs;
+            const double   fpr = meta.ibf_config.max_fp;
+            auto differs = [&](const char* opt, double given, double file) {
+                if (!c.quiet)
+                    std::cerr << "--update: " << opt << " " << given << " differs from the index, which was built with " << file << std::endl;
+                return false;
+            };
+            if (c.kmer_given && c.kmer_size != k)
+                return differs("--kmer-size", c.kmer_size, k);
+            if (c.window_given && c.window_size != w)
+                return differs("--window-size", c.window_size, w);
+            if (c.hashes_given && c.hash_functions != h)
+                return differs("--hash-functions", c.hash_functions, h);
+            if (c.max_fp_given && c.max_fp != fpr)
+                return differs("--max-fp", c.max_fp, fpr);
+            c.kmer_size = (uint8_t)k, c.window_size = (uint16_t)w, c.hash_functions = (uint8_t)h, c.max_fp = fpr;
+        }
+        catch (const std::exception& e)
+        {
+            if (!c.quiet)
+                std::cerr << "--update: " << e.what() << std::endl;
+            return false;
+        }
+    }
     if (c.verify_given)
     {
         if (!c.hibf)
@@ -212,6 +271,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--layout            " << c.layout << '\n';
     if (c.verify_given)
         std::cerr << "--verify-index      " << c.verify_index << '\n';
+    if (c.update_given)
+        std::cerr << "--update            " << c.update << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -246,6 +307,14 @@ const char* kHelp =
     "                               target's minimiser the user bin answers to (WARN fp when clearly above the index's fpr;\n"
     "                               a warning does not fail).  k, w and the hash functions come from the index; give the\n"
     "                               --min-length of the build.  Not with --output-file\n"
+    "      --update arg             [--hibf] add the targets of --input-file to the index `arg` and write the result to\n"
+    "                               --output-file; `arg` is left as it is.  The old genomes are not needed: how full every bin is\n"
+    "                               is read off the index's bits.  The tree is kept: a new target goes below a merged bin that\n"
+    "                               has room for it, otherwise it widens the IBF it reached (the root at worst) -- no IBF is\n"
+    "                               created or resized in its rows, and --tmax does not bound an updated IBF; the report says\n"
+    "                               how many bins each IBF gained, so that one sees when a rebuild is due.  k, w, the hash\n"
+    "                               functions and the false-positive rate come from the index.  A target the index holds\n"
+    "                               already is refused.  Not with --verify-index, --layout, --tmax, --filter-size, --mode\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -295,7 +364,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -352,8 +421,10 @@ int parse_args(int argc, char** argv, Config& c)
             c.hash_functions = (uint8_t)u("--hash-functions", 255), c.hashes_given = true;
         if (vals.count("--verify-index"))
             c.verify_index = vals["--verify-index"], c.verify_given = true;
+        if (vals.count("--update"))
+            c.update = vals["--update"], c.update_given = true;
         if (vals.count("--max-fp"))
-            c.max_fp = d("--max-fp");
+            c.max_fp = d("--max-fp"), c.max_fp_given = true;
         if (vals.count("--filter-size"))
             c.filter_size = d("--filter-size"), c.filter_size_given = true;
         if (vals.count("--tmax"))
@@ -362,7 +433,7 @@ int parse_args(int argc, char** argv, Config& c)
             c.layout = vals["--layout"], c.layout_given = true;
         c.hibf = vals.count("--hibf") && vals["--hibf"] != "false";
         if (vals.count("--mode"))
-            c.mode = vals["--mode"];
+            c.mode = vals["--mode"], c.mode_given = true;
         if (vals.count("--min-length"))
             c.min_length = u("--min-length", ~0ull);
         if (vals.count("--tmp-output-folder"))
@@ -657,8 +728,10 @@ struct HibfShape // IBF i of the tree as it is created and written
 
 // The raptor 3.0.1 index (reader: GanonClassify.cpp:875-938 with hibf.hpp:163-169,293-298), field for field what
 // ganon_amd/ibf_file.py:save_hibf writes; the matrices streamed IBF after IBF out of HBM.
-bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions, const std::vector<std::string>& files,
-               std::string& err)
+// bin_path: the files of every user bin (this builder writes one each; a raptor file that `--update` carries over may list several);
+// user_files: user_bin_filenames, one per user bin.
+bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions,
+               const std::vector<std::vector<std::string>>& bin_path, const std::vector<std::string>& user_files, std::string& err)
 {
     const int fd = ::open(c.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0)
@@ -680,11 +753,12 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
     w.raw<uint64_t>(c.kmer_size >= 64 ? ~0ull : (1ull << c.kmer_size) - 1);
     w.raw<uint8_t>(1);                                      // parts
     w.raw<uint8_t>(0);                                      // compressed
-    w.raw<uint64_t>(files.size());                          // bin_path: one file per user bin
-    for (const std::string& f : files)
+    w.raw<uint64_t>(bin_path.size());                       // bin_path
+    for (const std::vector<std::string>& lst : bin_path)
     {
-        w.raw<uint64_t>(1);
-        w.str(f);
+        w.raw<uint64_t>(lst.size());
+        for (const std::string& f : lst)
+            w.str(f);
     }
     w.raw<double>(c.max_fp);                                // fpr
     w.raw<uint8_t>(1);                                      // is_hibf
@@ -741,8 +815,8 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
         }
     };
     tables(true);                                           // next_ibf_id
-    w.raw<uint64_t>(files.size());                          // user_bins: user_bin_filenames
-    for (const std::string& f : files)
+    w.raw<uint64_t>(user_files.size());                     // user_bins: user_bin_filenames
+    for (const std::string& f : user_files)
         w.str(f);
     tables(false);                                          //            ibf_bin_to_filename_position
     flush(w);
@@ -876,6 +950,19 @@ std::string user_bin_file_name(const std::string& target)
     for (size_t p = 0; (p = name.find(' ', p)) != std::string::npos; p += 3)
         name.replace(p, 1, "---");
     return name;
+}
+
+// the loader's own reading of the name this builder would write for a target (filter_io.cpp:parse_hibf)
+std::string name_as_read(const std::string& target)
+{
+    std::string f     = fs::path(user_bin_file_name(target) + ".minimiser").filename().string();
+    size_t      found = f.find(".minimiser");
+    if (found != std::string::npos)
+        f = f.substr(0, found);
+    for (const auto& [from, to] : { std::pair<std::string, std::string>{ "|||", "." }, { "---", " " } })
+        for (size_t p = 0; (p = f.find(from, p)) != std::string::npos; p += to.size())
+            f.replace(p, from.size(), to);
+    return f;
 }
 
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
@@ -1028,7 +1115,10 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
 
     writing.start();
     std::string err;
-    const bool  saved = save_hibf(c, flt, ibfs, h, files, err);
+    std::vector<std::vector<std::string>> bin_path; // one file per user bin
+    for (const std::string& f : files)
+        bin_path.push_back({ f });
+    const bool saved = save_hibf(c, flt, ibfs, h, bin_path, files, err);
     gn_filter_free(flt);
     if (!saved)
         return fail(err);
@@ -1200,17 +1290,7 @@ bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counti
         std::map<std::string, uint64_t> user_of; // names as the loader recovers them -> user bin
         for (size_t t = 0; t < meta.targets.size(); ++t)
             user_of[meta.targets[t]] = meta.target_bins[t].at(0);
-        // the loader's own reading of the name this builder would write for a target
-        auto as_read = [](const std::string& target) {
-            std::string f     = fs::path(user_bin_file_name(target) + ".minimiser").filename().string();
-            size_t      found = f.find(".minimiser");
-            if (found != std::string::npos)
-                f = f.substr(0, found);
-            for (const auto& [from, to] : { std::pair<std::string, std::string>{ "|||", "." }, { "---", " " } })
-                for (size_t p = 0; (p = f.find(from, p)) != std::string::npos; p += to.size())
-                    f.replace(p, from.size(), to);
-            return f;
-        };
+        auto as_read = [](const std::string& target) { return name_as_read(target); };
 
         // membership: every target's set along its user bin's path, pooled as run_hibf pools its inserts
         t0 = std::chrono::steady_clock::now();
@@ -1379,6 +1459,247 @@ bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counti
     }
 }
 
+// ---- --hibf --update -------------------------------------------------------------------------------------------------------------
+// Adds the inputs' targets to an index without its genomes: the file into filter A, how full every bin is off A's bits
+// (gn_filter_bin_popcounts), the placement (hibf_update.hpp), filter B with the new bins, every IBF moved over (gn_filter_copy_ibf),
+// the new sets along their paths, B written with the file's own header fields and strings and the new names behind them.
+bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counting)
+{
+    auto fail = [](const std::string& m) {
+        std::cerr << m << std::endl;
+        return false;
+    };
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> fresh_target; // targets with a hash, in input order: new user bin n_user_old + position
+    std::vector<uint64_t> fresh_counts;
+    for (uint32_t t = 0; t < targets.size(); ++t)
+    {
+        if (targets[t].hashes.empty())
+            continue;
+        if (!unite_files(c, targets[t]))
+            return fail(gn_last_error());
+        fresh_target.push_back(t);
+        fresh_counts.push_back(targets[t].hashes.size());
+    }
+    if (fresh_counts.empty())
+        return fail("No valid sequences to build");
+    const double hash_s = counting.seconds() + since(t0);
+    gn_filter*   b_flt  = nullptr;
+    try
+    {
+        {
+            gnhost::FilterMeta names;
+            gnhost::read_hibf_meta(c.update, names);
+            const std::set<std::string> have(names.targets.begin(), names.targets.end());
+            for (uint32_t t : fresh_target)
+                if (have.count(name_as_read(targets[t].name)))
+                    return fail("--update: target " + targets[t].name + " is already in the index (adding sequences to an existing user bin is not supported); nothing written");
+        }
+        t0 = std::chrono::steady_clock::now();
+        gnhost::FilterMeta meta;
+        auto               sink = std::make_unique<HibfDeviceSink>(c.device);
+        gnhost::load_filter_file(c.update, true, meta, *sink);
+        const double load_s = since(t0);
+        const uint64_t n_ibf = meta.shapes.size(), n_old = meta.n_user_bins;
+        const uint8_t  h   = (uint8_t)meta.shapes.at(0).hash_funs;
+        const double   fpr = meta.ibf_config.max_fp;
+        if (meta.raw_bin_path.size() != n_old || meta.raw_user_bin_filenames.size() != n_old)
+            return fail("--update: the index names " + std::to_string(meta.raw_bin_path.size()) + " file lists for " + std::to_string(n_old) + " user bins");
+        std::vector<uint64_t> bins, rows;
+        for (const gnhost::IbfShape& m : meta.shapes)
+        {
+            bins.push_back(m.bins), rows.push_back(m.bin_size);
+            if (m.hash_funs != h)
+                return fail("--update: the IBFs of the index differ in their hash functions");
+        }
+
+        t0 = std::chrono::steady_clock::now();
+        std::vector<std::vector<uint64_t>> pop(n_ibf);
+        for (uint64_t i = 0; i < n_ibf; ++i)
+        {
+            pop[i].assign(bins[i], 0);
+            if (gn_filter_bin_popcounts(sink->filter(), (uint32_t)i, pop[i].data()) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+        }
+        const double count_s = since(t0);
+
+        t0 = std::chrono::steady_clock::now();
+        const gnhibf::UpdatePlan plan = gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_old, h, fpr, pop, fresh_counts);
+        const uint32_t           depth = plan.paths.depth;
+        const double             plan_s = since(t0);
+
+        // filter B: the same rows, the new bins.  A and B are on the device together until every IBF is moved
+        t0 = std::chrono::steady_clock::now();
+        std::vector<HibfShape> ibfs(n_ibf);
+        uint64_t               a_bytes = 0, b_bytes = 0;
+        for (uint64_t i = 0; i < n_ibf; ++i)
+        {
+            ibfs[i].bins = plan.bins[i], ibfs[i].rows = rows[i];
+            ibfs[i].next_ibf_id = plan.next_ibf_id[i], ibfs[i].bin_to_user = plan.bin_to_user[i];
+            a_bytes += rows[i] * gn_hibf_row_stride_words((bins[i] + 63) >> 6) * 8;
+            b_bytes += rows[i] * gn_hibf_row_stride_words((plan.bins[i] + 63) >> 6) * 8;
+        }
+        {
+            uint64_t free_b = 0, total_b = 0;
+            if (gn_device_memory(c.device, &free_b, &total_b) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+            // (free_b is what is left beside A.  The 256 MiB on top of B are for what is still to come on this device: the staging buffer
+            // of the inserts (32 M hashes, 256 MiB at most, usually far less), their item and path tables, the bit counts, and whatever
+            // the hasher streams of the counting phase have not yet given back)
+            if (b_bytes + (256ull << 20) > free_b)
+                return fail("--update: the index (" + std::to_string(a_bytes) + " bytes on the device) and the updated one (" + std::to_string(b_bytes) +
+                            " bytes) do not fit device " + std::to_string(c.device) + " together (" + std::to_string(free_b) + " bytes free beside the index)");
+        }
+        {
+            std::vector<gn_ibf_desc>    descs(n_ibf);
+            std::vector<const int64_t*> nx(n_ibf), bu(n_ibf);
+            for (uint64_t i = 0; i < n_ibf; ++i)
+            {
+                descs[i] = gn_ibf_desc{ nullptr, rows[i], (ibfs[i].bins + 63) >> 6, ibfs[i].bins, h, (uint32_t)__builtin_clzll(rows[i]) };
+                nx[i] = ibfs[i].next_ibf_id.data(), bu[i] = ibfs[i].bin_to_user.data();
+            }
+            if (gn_filter_upload_hibf(c.device, (uint32_t)n_ibf, descs.data(), nx.data(), bu.data(), plan.n_user_bins, &b_flt) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+        }
+        for (uint64_t i = 0; i < n_ibf; ++i)
+            if (gn_filter_copy_ibf(b_flt, (uint32_t)i, sink->filter(), (uint32_t)i) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+        sink.reset(); // (frees A)
+        const double copy_s = since(t0);
+
+        // the new sets along their paths, pooled as run_hibf pools them
+        t0 = std::chrono::steady_clock::now();
+        {
+            constexpr uint64_t         kBatch = 16ull << 20, kAlone = 4ull << 20;
+            std::vector<uint64_t>      pool, off{ 0 };
+            std::vector<gn_path_entry> pp;
+            auto                       flush = [&] {
+                if (off.size() > 1 && gn_filter_emplace_path(b_flt, pool.data(), off.data(), (uint32_t)off.size() - 1, pp.data(), depth) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+                pool.clear(), pp.clear(), off.assign(1, 0);
+            };
+            for (size_t j = 0; j < fresh_target.size(); ++j)
+            {
+                const std::vector<uint64_t>& hs = targets[fresh_target[j]].hashes;
+                const gn_path_entry*         p  = &plan.paths.entries[j * depth];
+                if (hs.size() >= kAlone)
+                {
+                    const uint64_t one[2] = { 0, hs.size() };
+                    if (gn_filter_emplace_path(b_flt, hs.data(), one, 1, p, depth) != GN_OK)
+                        throw std::runtime_error(gn_last_error());
+                    continue;
+                }
+                pool.insert(pool.end(), hs.begin(), hs.end());
+                off.push_back(pool.size());
+                pp.insert(pp.end(), p, p + depth);
+                if (pool.size() >= kBatch)
+                    flush();
+            }
+            flush();
+        }
+        const double emplace_s = since(t0);
+
+        // B's bit counts, for the IBFs the report speaks of: those that gained bins or lie on a new path
+        t0 = std::chrono::steady_clock::now();
+        std::vector<bool> shown(n_ibf, false);
+        for (uint64_t i = 0; i < n_ibf; ++i)
+            shown[i] = plan.bins[i] != bins[i];
+        for (const gn_path_entry& e : plan.paths.entries)
+            if (e.n_bins)
+                shown[e.ibf] = true;
+        std::vector<std::vector<uint64_t>> pop_b(n_ibf);
+        for (uint64_t i = 0; i < n_ibf; ++i)
+            if (shown[i])
+            {
+                pop_b[i].assign(plan.bins[i], 0);
+                if (gn_filter_bin_popcounts(b_flt, (uint32_t)i, pop_b[i].data()) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+            }
+        const double count_b_s = since(t0);
+
+        // the file: its header fields and strings as they are, the new names behind them in the form run_hibf writes
+        t0 = std::chrono::steady_clock::now();
+        std::vector<std::vector<std::string>> bin_path   = meta.raw_bin_path;
+        std::vector<std::string>              user_files = meta.raw_user_bin_filenames;
+        const std::string dir = !c.tmp_output_folder.empty() ? c.tmp_output_folder
+                                : fs::path(c.output_file).has_parent_path() ? fs::path(c.output_file).parent_path().string()
+                                                                            : std::string(".");
+        for (uint32_t t : fresh_target)
+        {
+            const std::string f = dir + "/" + user_bin_file_name(targets[t].name) + ".minimiser";
+            bin_path.push_back({ f });
+            user_files.push_back(f);
+        }
+        std::string err;
+        const bool  saved = save_hibf(c, b_flt, ibfs, h, bin_path, user_files, err); // (c holds the file's k, w and fpr: validate())
+        gn_filter_free(b_flt);
+        b_flt = nullptr;
+        if (!saved)
+            return fail(err);
+        const double write_s = since(t0);
+
+        // the report
+        const double bound_fill = std::pow(fpr, 1.0 / h);
+        std::cout << "index\t" << c.update << "\t->\t" << c.output_file << "\tk=" << unsigned(c.kmer_size) << " w=" << c.window_size << " h=" << unsigned(h)
+                  << " ibfs=" << n_ibf << " levels=" << depth << " user_bins=" << n_old << "->" << plan.n_user_bins << " fpr=" << fpr << "\n";
+        std::cout << "#target\tuser_bin\tdistinct_hashes\tleaf_ibf\tfirst_bin\tbins\tdepth\tpath\n";
+        uint64_t bins_added = 0;
+        for (size_t j = 0; j < fresh_target.size(); ++j)
+        {
+            const gn_path_entry* p    = &plan.paths.entries[j * depth];
+            uint32_t             used = 0;
+            while (used < depth && p[used].n_bins)
+                ++used;
+            std::cout << "target\t" << targets[fresh_target[j]].name << "\t" << n_old + j << "\t" << fresh_counts[j] << "\t" << p[0].ibf << "\t" << p[0].first_bin << "\t"
+                      << p[0].n_bins << "\t" << used << "\t";
+            for (uint32_t d = used; d-- > 0;)
+                std::cout << p[d].ibf << ":" << p[d].first_bin << (d ? " " : "");
+            std::cout << "\n";
+            bins_added += p[0].n_bins;
+        }
+        std::cout << "#ibf\trows\tbins_before\tbins_after\tmax_fill_before\tmax_fill_after\n" << std::fixed << std::setprecision(6);
+        for (uint64_t i = 0; i < n_ibf; ++i)
+            if (shown[i])
+                std::cout << "ibf\t" << i << "\t" << rows[i] << "\t" << bins[i] << "\t" << plan.bins[i] << "\t"
+                          << *std::max_element(pop[i].begin(), pop[i].end()) / (double)rows[i] << "\t"
+                          << *std::max_element(pop_b[i].begin(), pop_b[i].end()) / (double)rows[i] << "\n";
+        std::cout << "#merged\tibf\tbin\tbits_before\tbits_predicted\tbits_after\n";
+        uint64_t fullest = 0, fullest_rows = 1;
+        bool     any_touched = false;
+        for (const gnhibf::UpdateTouched& t : plan.touched)
+        {
+            const uint64_t after = pop_b[t.ibf][t.bin];
+            std::cout << "merged\t" << t.ibf << "\t" << t.bin << "\t" << t.bits_before << "\t" << std::setprecision(1) << t.bits_predicted << std::setprecision(6) << "\t"
+                      << after << (after > bound_fill * rows[t.ibf] ? "\tWARN fill" : "") << "\n";
+            if (!any_touched || after * (double)fullest_rows > fullest * (double)rows[t.ibf])
+                fullest = after, fullest_rows = rows[t.ibf];
+            any_touched = true;
+        }
+        std::error_code ec;
+        std::cout << "result\tok\t" << fresh_target.size() << " user bin(s) added, " << bins_added << " bin(s) added, " << fs::file_size(c.update, ec) << " -> "
+                  << fs::file_size(c.output_file, ec) << " bytes, fullest touched merged bin ";
+        if (!any_touched)
+            std::cout << "n/a";
+        else if (fullest >= fullest_rows)
+            std::cout << "full";
+        else
+            std::cout << std::setprecision(0) << -((double)fullest_rows / h) * std::log(1.0 - (double)fullest / fullest_rows) << " estimated hashes at fill " << std::setprecision(6)
+                      << (double)fullest / fullest_rows;
+        std::cout << std::endl;
+        if (c.verbose && !c.quiet)
+            std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " count " << count_s + count_b_s << " plan " << plan_s << " copy " << copy_s
+                      << " emplace " << emplace_s << " write " << write_s << std::endl;
+        return true;
+    }
+    catch (const std::exception& e)
+    {
+        if (b_flt)
+            gn_filter_free(b_flt);
+        return fail(std::string("ERROR: ") + e.what());
+    }
+}
+
 bool run(Config c)
 {
     if (!validate(c))
@@ -1439,6 +1760,8 @@ bool run(Config c)
 
     if (c.verify_given)
         return run_verify(c, targets, counting);
+    if (c.update_given)
+        return run_update(c, targets, counting);
     if (c.hibf)
         return run_hibf(c, targets, totals, whole, counting);
 

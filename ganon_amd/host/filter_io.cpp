@@ -573,6 +573,8 @@ void parse_hibf(Reader& r, FilterMeta& out, std::vector<uint64_t>& payload_at)
         if (b[0] >= nub)
             throw std::runtime_error(path + ": bin_path has more entries than user bins");
     out.bin_count = nub;
+    out.raw_bin_path           = std::move(bin_path);
+    out.raw_user_bin_filenames = std::move(user_bin_filenames);
     if (r.trace)
     {
         r.check("per-bin tables cover every IBF's bins; bin_path entries name user bins", true);

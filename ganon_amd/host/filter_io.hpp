@@ -69,6 +69,10 @@ struct FilterMeta
     std::vector<std::vector<int64_t>> next_ibf_id;
     std::vector<std::vector<int64_t>> bin_to_user;
     uint64_t                          n_user_bins = 0;
+    // ... and the file's own strings, verbatim, for a writer that has to keep them (`ganon-build --hibf --update`): a raptor file may
+    // list several files per user bin
+    std::vector<std::vector<std::string>> raw_bin_path;
+    std::vector<std::string>              raw_user_bin_filenames;
 };
 
 // Receives a filter: begin(meta) -> rows(...)* -> end().  rows() may return before `src` has been consumed (an

@@ -446,6 +446,22 @@ int gn_filter_probe_path(gn_filter* f, const uint64_t* hashes, const uint64_t* s
 int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths,
                                  uint32_t depth, uint64_t* found);
 
+/* `ganon-build --hibf --update`: what an index on the device says about itself, and its move into a wider one (no counterpart in the
+ * reference: `ganon update` rebuilds the filter, update() in src/ganon/build_update.py).
+ * gn_filter_bin_popcounts: counts[b], for every b below the bins of IBF `ibf_idx` (host memory, that many entries), = the number of
+ *   rows of the IBF whose bit b is set -- how full technical bin b is; a .hibf records nothing else about it.  ibf_idx = 0 of a flat
+ *   filter (one created without a bin map included), any IBF of an HIBF.  The device's padded row stride (gn_hibf_row_stride_words)
+ *   does not show: padding bins and padding words are not reported.  Every word of the IBF is read once; exact, whatever the order
+ *   the device adds in (integers).  GN_EINVAL for a null argument or an IBF the filter does not have.
+ * gn_filter_copy_ibf: IBF src_ibf of `src` into IBF dst_ibf of `dst`, device to device: words [0, W_src) of every row are the
+ *   source's (W = ceil(bins / 64)), the words from there to the destination's row stride are zero -- bin b of the source is bin b of
+ *   the destination, every further bin is empty.  The source's last word is taken as it is: its padding bins are clear in a filter
+ *   that was finalised or streamed from a file.  GN_EINVAL unless both are HIBF filters on the same device, the two IBFs have the
+ *   same number of rows and of hash functions, and the destination has at least the source's words a row; everything is checked
+ *   before anything is launched.  Returns when the copy is complete. */
+int gn_filter_bin_popcounts(const gn_filter* f, uint32_t ibf_idx, uint64_t* counts);
+int gn_filter_copy_ibf(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf);
+
 /* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.

@@ -12,6 +12,10 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --verify        [--hibf] after each --hibf build of a run the file is checked (`ganon-build --hibf --verify-index`): verify_hash_s,
                   verify_load_s, verify_membership_s (beside emplace_s of the same build: the same hashes along the same paths) and
                   verify_fp_s, max_observed_fp / mean_observed_fp against --max-fp, the number of WARN and of FAIL lines
+  --update M      [--hibf] per layout: an index built from all but the last M files, `ganon-build --hibf --update` with those M (laps: hash,
+                  load, count, plan, copy, emplace, write), the updated file checked over ALL files (--verify-index), beside one full
+                  rebuild of all N checked the same way: seconds, bytes and max_observed_fp of both.  Prints "update" per layout;
+                  the flat / hibf medians are not run
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
@@ -27,7 +31,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": ""}
 pos, hibf, check, argv = [], False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -110,10 +114,10 @@ def flat_run(max_fp="0.05", extra=()):
     return res
 
 
-def hibf_run(layout=""):
+def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     res = {}
     t0 = time.time()
-    cmd = [exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.hibf"), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
+    cmd = [exe, "-i", os.path.join(d, tsv), "-o", os.path.join(d, db), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
            "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
@@ -135,18 +139,46 @@ def hibf_run(layout=""):
     m = re.search(r" - hibf: .*", p.stderr)
     res["summary"] = m.group(0).strip() if m else p.stderr[-300:]
     if p.returncode == 0:
-        res["hibf_bytes"] = os.path.getsize(os.path.join(d, "db.hibf"))
+        res["hibf_bytes"] = os.path.getsize(os.path.join(d, db))
         res["mbp_per_s"] = round(total_bases / 1e6 / res.get("total_s", res["wall_s"]), 1)
         if check:
-            res.update(verify_run())
+            res.update(verify_run(db))
     return res
 
 
-def verify_run():
-    """the index just written against the inputs it was built from"""
+def update_run(layout, m):
+    """build from all but the last m files, update with those, check the result over all; beside a rebuild of all"""
+    lines = open(os.path.join(d, "in.tsv")).read().splitlines(True)
+    open(os.path.join(d, "old.tsv"), "w").writelines(lines[:-m])
+    open(os.path.join(d, "new.tsv"), "w").writelines(lines[-m:])
+    res = {"base": hibf_run(layout, "old.tsv", "old.hibf")}
+    t0 = time.time()
+    p = subprocess.run([exe, "-i", os.path.join(d, "new.tsv"), "--hibf", "--update", os.path.join(d, "old.hibf"), "-o", os.path.join(d, "upd.hibf"), "-t", str(threads),
+                        "--verbose"], capture_output=True, text=True)
+    upd = {"rc": p.returncode, "wall_s": round(time.time() - t0, 2)}
+    mm = re.search(r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
+    if mm:
+        for key, x in zip(("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s"), mm.groups()):
+            upd[key] = float(x)
+    mm = re.search(r"^result\t.*", p.stdout, re.M)
+    upd["result"] = mm.group(0) if mm else (p.stderr or p.stdout)[-300:]
+    upd["ibf_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith("ibf\t")][:8]
+    upd["warn_fill_lines"] = sum(ln.endswith("WARN fill") for ln in p.stdout.splitlines())
+    if p.returncode == 0:
+        upd["hibf_bytes"] = os.path.getsize(os.path.join(d, "upd.hibf"))
+        upd.update(verify_run("upd.hibf"))
+    res["update"] = upd
+    res["rebuild"] = hibf_run(layout)
+    if not check and res["rebuild"]["rc"] == 0:
+        res["rebuild"].update(verify_run())
+    return res
+
+
+def verify_run(db="db.hibf"):
+    """an index just written against all the inputs"""
     res = {}
     t0 = time.time()
-    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "--hibf", "--verify-index", os.path.join(d, "db.hibf"), "-t", str(threads), "--verbose"],
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "--hibf", "--verify-index", os.path.join(d, db), "-t", str(threads), "--verbose"],
                        capture_output=True, text=True)
     res["verify_rc"], res["verify_wall_s"] = p.returncode, round(time.time() - t0, 2)
     m = re.search(r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) membership ([0-9.eE+-]+) fp ([0-9.eE+-]+)", p.stderr)
@@ -175,6 +207,9 @@ def median_of(runs):
 
 if not hibf:
     out.update(flat_run())
+elif opts["--update"]:
+    out["max_fp"], out["hash_functions"], out["updated_with"] = float(opts["--max-fp"]), int(opts["--hash-functions"]), int(opts["--update"])
+    out["update"] = {name or "rule": update_run(name, int(opts["--update"])) for name in opts["--layout"].split(",")}
 else:
     flat_extra = ["-s", opts["--hash-functions"]]
     layouts = opts["--layout"].split(",")
