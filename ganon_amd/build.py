@@ -21,7 +21,7 @@ LIB = os.path.join(CSRC, "libganon_hip.so")
 BIN = os.path.join(HOST, "ganon-classify")
 BIN_BUILD = os.path.join(HOST, "ganon-build")
 BIN_REASSIGN = os.path.join(HOST, "ganon-reassign")
-BUILD_ONLY = ("build.cpp", "build_params.cpp")  # sources of ganon-build that ganon-classify does not link
+BUILD_SHARED = ("seq_io.cpp", "pgzip.cpp", "filter_io.cpp")  # what ganon-build links besides its own build*.cpp: the sequence and index readers
 REASSIGN_ONLY = ("reassign.cpp", "reassign_main.cpp")  # ganon-reassign (the EM over .all)
 
 HIP_SOURCES = ["gn_kernels.hip", "gn_split.hip", "gn_minimiser_lpr.hip", "gn_hibf.hip", "gn_postfilter.hip", "gn_build.hip", "gn_build_hibf.hip", "gn_build_sketch.hip", "gn_gather.hip", "gn_fastq.hip", "gn_reassign.hip", "gn_inflate.hip", "gn_capi.hip"]
@@ -80,8 +80,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     every = sorted(f for f in os.listdir(HOST) if f.endswith(".cpp"))
     hdrs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "ganon_hip.h"), os.path.join(ROOT, "include", "ganon_ibf_hash.h")]
     build_hip(force=False, verbose=verbose)
-    for binary, names in ((BIN, [f for f in every if f not in BUILD_ONLY + REASSIGN_ONLY]),
-                          (BIN_BUILD, [f for f in every if f in BUILD_ONLY] + ["seq_io.cpp", "pgzip.cpp", "filter_io.cpp"]),
+    builder = [f for f in every if f.startswith("build")]  # ganon-build's own sources, one per mode; ganon-classify links none of them
+    for binary, names in ((BIN, [f for f in every if f not in builder and f not in REASSIGN_ONLY]),
+                          (BIN_BUILD, builder + list(BUILD_SHARED)),
                           (BIN_REASSIGN, [f for f in every if f in REASSIGN_ONLY])):
         srcs = [os.path.join(HOST, f) for f in names]
         if not srcs:

@@ -1,0 +1,195 @@
+// build_common.hpp -- what the modes of `ganon-build` share: build.cpp (arguments, hashing, the flat .ibf), build_hibf.cpp (--hibf),
+// build_verify.cpp (--hibf --verify-index), build_update.cpp (--hibf --update) and build_write.cpp (the two file writers).
+#pragma once
+
+#include "build_params.hpp"
+#include "device_sink.hpp"
+
+#include "ganon_hip.h"
+
+#include <chrono>
+#include <cstdint>
+#include <ctime>
+#include <filesystem>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace gnbuild
+{
+
+namespace fs = std::filesystem;
+
+constexpr int kVersionTuple[3] = { 2, 1, 1 };
+
+struct Config // Config.hpp:10-27
+{
+    std::string input_file, output_file, tmp_output_folder, mode = "avg";
+    double      max_fp = 0.05, filter_size = 0;
+    uint8_t     kmer_size = 19;
+    uint16_t    window_size = 31;
+    uint8_t     hash_functions = 0; // (parsed into an int first: 0..255)
+    uint64_t    min_length = 0;
+    uint16_t    threads = 1;
+    bool        verbose = false, quiet = false;
+    int         device = 0; // (not in the reference: which GPU)
+    bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
+    uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
+    bool        tmax_given = false, filter_size_given = false;
+    std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates,
+                                 //  similarity = hibf_layout_similarity.hpp: sketch over an order that groups related targets)
+    bool        layout_given = false;
+    std::string verify_index;    // (--hibf only: check this index against the inputs instead of building one)
+    std::string update;          // (--hibf only: add the inputs' targets to this index and write the result to --output-file)
+    bool        update_given = false, max_fp_given = false, mode_given = false;
+    bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
+};
+
+struct Target
+{
+    std::string              name;
+    std::vector<std::string> files;
+    std::vector<uint64_t>    hashes; // per file: its distinct hashes, ascending; files behind each other (:236-238)
+    std::vector<uint64_t>    file_ends; // where each file's hashes end in `hashes` (--hibf unites the files of a target)
+};
+
+// a target's hashes as the pooler (hibf_pool.hpp) asks for a set
+inline std::pair<const uint64_t*, uint64_t> hash_set(const Target& t)
+{
+    return { t.hashes.data(), t.hashes.size() };
+}
+
+struct Totals // :52-59
+{
+    uint64_t files = 0, invalid_files = 0, sequences = 0, skipped_sequences = 0, length_bp = 0;
+};
+
+struct HibfShape // IBF i of the tree as it is created and written
+{
+    uint64_t             bins = 0, rows = 0;
+    std::vector<int64_t> next_ibf_id, bin_to_user;
+};
+
+inline std::string stamp(std::chrono::system_clock::time_point t)
+{
+    const std::time_t tt = std::chrono::system_clock::to_time_t(t);
+    char              b[64];
+    std::strftime(b, sizeof(b), "%Y-%m-%d %H:%M:%S", std::localtime(&tt));
+    return b;
+}
+
+struct Lap
+{
+    std::chrono::system_clock::time_point b, e;
+    void   start() { b = std::chrono::system_clock::now(); }
+    void   stop() { e = std::chrono::system_clock::now(); }
+    double seconds() const { return std::chrono::duration<double>(e - b).count(); }
+};
+
+inline double since(std::chrono::steady_clock::time_point t)
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+}
+
+inline bool fail(const std::string& m)
+{
+    std::cerr << m << std::endl;
+    return false;
+}
+
+// where the user bins' files are said to lie: --tmp-output-folder, else the folder of --output-file
+inline std::string output_folder(const Config& c)
+{
+    return !c.tmp_output_folder.empty()                  ? c.tmp_output_folder
+           : fs::path(c.output_file).has_parent_path() ? fs::path(c.output_file).parent_path().string()
+                                                       : std::string(".");
+}
+
+// the name of a target's user bin as an index file gives it back: written as <folder>/<name, "---" for a space>.minimiser by this
+// builder (and by `ganon build`, build_update.py:411-518), read as filter_io.cpp:parse_hibf reads it (GanonClassify.cpp:908-935)
+inline std::string user_bin_file_name(const std::string& target)
+{
+    std::string name = target;
+    for (size_t p = 0; (p = name.find(' ', p)) != std::string::npos; p += 3)
+        name.replace(p, 1, "---");
+    return name;
+}
+
+// the loader's own reading of the name this builder would write for a target (filter_io.cpp:parse_hibf)
+inline std::string name_as_read(const std::string& target)
+{
+    std::string f     = fs::path(user_bin_file_name(target) + ".minimiser").filename().string();
+    size_t      found = f.find(".minimiser");
+    if (found != std::string::npos)
+        f = f.substr(0, found);
+    for (const auto& [from, to] : { std::pair<std::string, std::string>{ "|||", "." }, { "---", " " } })
+        for (size_t p = 0; (p = f.find(from, p)) != std::string::npos; p += to.size())
+            f.replace(p, from.size(), to);
+    return f;
+}
+
+// a target's set = the union of its files' sets, ascending
+inline bool unite_files(const Config& c, Target& tg)
+{
+    if (tg.file_ends.size() <= 1)
+        return true;
+    std::vector<const uint64_t*> sets;
+    std::vector<uint64_t>        sizes;
+    uint64_t                     a = 0;
+    for (uint64_t e : tg.file_ends)
+    {
+        sets.push_back(tg.hashes.data() + a);
+        sizes.push_back(e - a);
+        a = e;
+    }
+    std::vector<uint64_t> all(tg.hashes.size());
+    uint64_t              n = 0;
+    if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), all.data(), all.size(), &n) != GN_OK)
+        return false;
+    all.resize(n);
+    tg.hashes.swap(all);
+    tg.file_ends.assign(1, n);
+    return true;
+}
+
+// the end of a build: with --verbose the five laps (print_stats_verbose, :730-757; `second` and its label are the mode's: sizing
+// or layout), then what was processed and what was skipped (print_stats, :706-728).  The lines that follow are the mode's.
+inline void print_stats(const Config& c, const Totals& totals, const Lap& counting, const char* second_label, const Lap& second, const Lap& filling,
+                        const Lap& writing, const Lap& whole)
+{
+    if (c.verbose)
+    {
+        auto block = [](const char* a, const Lap& l) {
+            const char* pad = "                ";
+            std::cerr << a << stamp(l.b) << '\n' << pad << "    end: " << stamp(l.e) << '\n' << pad << "elapsed (s): " << l.seconds() << '\n';
+        };
+        block("Count/save hashes start: ", counting);
+        block(second_label, second);
+        block("Building filter   start: ", filling);
+        block("Saving filer      start: ", writing);
+        block("ganon-build       start: ", whole);
+        std::cerr << std::endl;
+    }
+    const double elapsed = whole.seconds();
+    std::cerr << "ganon-build processed " << totals.sequences << " sequences / " << totals.files << " files ("
+              << totals.length_bp / 1000000.0 << " Mbp) in " << elapsed << " seconds ("
+              << (totals.length_bp / 1000000.0) / (elapsed / 60.0) << " Mbp/m)" << std::endl;
+    if (totals.invalid_files > 0)
+        std::cerr << " - " << totals.invalid_files << " invalid files skipped" << std::endl;
+    if (totals.skipped_sequences > 0)
+        std::cerr << " - " << totals.skipped_sequences << " sequences skipped" << std::endl;
+}
+
+// build_write.cpp: header from the host, the bit matrices streamed out of HBM
+bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins,
+                 std::string& err);
+bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions,
+               const std::vector<std::vector<std::string>>& bin_path, const std::vector<std::string>& user_files, std::string& err);
+
+// the modes, after the inputs are hashed (build.cpp: run)
+bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting);   // build_hibf.cpp
+bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counting);                                  // build_verify.cpp
+bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counting);                                  // build_update.cpp
+
+} // namespace gnbuild

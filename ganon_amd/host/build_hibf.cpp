@@ -1,0 +1,257 @@
+// build_hibf.cpp -- `ganon-build --hibf` (this project's extension, like --device): the hash sets of the targets go into a hierarchical
+// filter, written as the raptor 3.0.1 index `ganon build --filter-type hibf` gets from `raptor prepare / layout / build`
+// (/root/reference/src/ganon/build_update.py:411-518; read at src/ganon-classify/GanonClassify.cpp:875-938):
+//   one user bin per target -> tree of IBFs (hibf_layout.hpp) -> exact cardinalities of the merged bins (gn_hashes_union)
+//   -> rows per IBF (gnbuild::hibf_run_bits) -> zero-filled HIBF in HBM -> every user bin ORed in along its whole path
+//   (gn_filter_emplace_path) -> IBF after IBF streamed into the file (save_hibf: the twin of ganon_amd/ibf_file.py:save_hibf).
+#include "build_common.hpp"
+#include "hibf_layout.hpp"
+#include "hibf_layout_similarity.hpp"
+#include "hibf_layout_sketch.hpp"
+#include "hibf_paths.hpp"
+#include "hibf_pool.hpp"
+
+#include <cmath>
+#include <iomanip>
+#include <memory>
+
+namespace gnbuild
+{
+
+namespace
+{
+
+// --layout sketch | similarity: one HyperLogLog sketch per user bin on the device, the estimated unions of up to `width` neighbours
+// in an order for every start (tiled over the starts: gn_sketches_union_table bounds a call), then the search of
+// hibf_layout_sketch.hpp.  similarity (hibf_layout_similarity.hpp) asks for that table twice, one after the other -- the size order's
+// and the similarity order's -- and in between for one gn_sketches_pair_table per interval of the size order.
+struct SketchLaps // seconds inside the `layout` lap: the rest of it is the host's ordering and searches
+{
+    double sketches = 0, tables = 0, pairs = 0;
+};
+
+bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, const std::vector<uint32_t>& user_target, const std::vector<uint64_t>& counts,
+                         uint32_t tmax, uint8_t h, gnhibf::Layout& lay, SketchLaps& laps, std::string& err)
+{
+    constexpr uint64_t kTableBytes = 4ull << 30; // the most host memory a union table may take
+    const uint64_t     n = counts.size(), width = gnhibf::sketch_width(n, tmax);
+    const bool         similarity = c.layout == "similarity";
+    gn_sketches*       sk = nullptr;
+    if (width >= 2) // (width 1: one IBF, no union is asked for)
+    {
+        if (n * width > kTableBytes / 8)
+        {
+            err = "--layout " + c.layout + ": the union estimates of " + std::to_string(n) + " user bins, " + std::to_string(width) +
+                  " neighbours each, take " + std::to_string(n * width * 8) + " bytes of host memory, more than " + std::to_string(kTableBytes) +
+                  "; use another --tmax (which sets how many neighbours a merged bin may hold) or --layout rule";
+            return false;
+        }
+        const auto                   t0 = std::chrono::steady_clock::now();
+        std::vector<const uint64_t*> sets(n);
+        for (uint64_t u = 0; u < n; ++u)
+            sets[u] = targets[user_target[u]].hashes.data();
+        if (gn_sketches_create(c.device, sets.data(), counts.data(), (uint32_t)n, &sk) != GN_OK)
+        {
+            err = gn_last_error();
+            return false;
+        }
+        laps.sketches = since(t0);
+    }
+    struct DeviceError // a device call inside a callback failed: the search ends there
+    {
+        std::string what;
+    };
+    // the union table of an order, held by the estimate that reads it
+    const gnhibf::OrderUnions unions = [&](const std::vector<uint32_t>& order) -> gnhibf::UnionEstimate {
+        const auto t0    = std::chrono::steady_clock::now();
+        auto       table = std::make_shared<std::vector<uint64_t>>(n * width, 0);
+        const uint64_t per = std::max<uint64_t>(1, GN_SKETCH_TABLE_MAX / width);
+        for (uint64_t j = 0; j < n; j += per)
+            if (gn_sketches_union_table(sk, order.data(), (uint32_t)n, (uint32_t)j, (uint32_t)std::min(n, j + per), (uint32_t)width,
+                                        table->data() + j * width) != GN_OK)
+                throw DeviceError{ gn_last_error() };
+        laps.tables += since(t0);
+        return [table, width](uint64_t j, uint64_t l) { return (*table)[j * width + l - 1]; };
+    };
+    const std::vector<uint32_t> size_order = gnhibf::sketch_order(counts);
+    // the pair table of one interval of the size order, held likewise
+    const gnhibf::IntervalPairs pairs = [&](uint64_t a, uint64_t b) -> gnhibf::PairEstimate {
+        const auto     t0    = std::chrono::steady_clock::now();
+        const uint64_t m     = b - a;
+        auto           table = std::make_shared<std::vector<uint64_t>>(m * m, 0);
+        if (gn_sketches_pair_table(sk, size_order.data() + a, (uint32_t)m, table->data()) != GN_OK)
+            throw DeviceError{ gn_last_error() };
+        laps.pairs += since(t0);
+        return [table, m](uint64_t p, uint64_t q) { return (*table)[p * m + q]; };
+    };
+    bool ok = true;
+    try
+    {
+        if (similarity)
+        {
+            gnhibf::SimilarityLayout got = gnhibf::lay_out_similarity(counts, tmax, c.max_fp, h, unions, pairs);
+            lay                          = std::move(got.layout);
+            if (c.verbose)
+                std::cerr << "layout similarity: " << got.intervals << " intervals, " << got.moved << " of " << n << " user bins moved, kept " << got.kept
+                          << std::endl;
+        }
+        else if (width >= 2)
+            lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, unions(size_order));
+        else
+            lay = gnhibf::lay_out_sketch(counts, tmax, c.max_fp, h, [](uint64_t, uint64_t) -> uint64_t { return 0; });
+    }
+    catch (const DeviceError& e)
+    {
+        err = e.what;
+        ok  = false;
+    }
+    if (sk)
+        gn_sketches_free(sk);
+    return ok;
+}
+
+} // namespace
+
+bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
+{
+    Lap            uniting, laying, filling, writing;
+    const uint8_t  h = c.hash_functions == 0 ? 4 : c.hash_functions; // (what `ganon build` passes to raptor, config.py:138-145)
+
+    // one user bin per target with a hash, in first-appearance order; its set = the union of its files' sets
+    uniting.start();
+    std::vector<uint32_t>    user_target;
+    std::vector<uint64_t>    counts;
+    std::vector<std::string> files;
+    const std::string        dir = output_folder(c);
+    for (uint32_t t = 0; t < targets.size(); ++t)
+    {
+        Target& tg = targets[t];
+        if (tg.hashes.empty())
+            continue;
+        if (!unite_files(c, tg))
+            return fail(gn_last_error());
+        user_target.push_back(t);
+        counts.push_back(tg.hashes.size());
+        files.push_back(dir + "/" + user_bin_file_name(tg.name) + ".minimiser");
+    }
+    if (counts.empty())
+        return fail("No valid sequences to build");
+    const uint64_t n_user = counts.size();
+    uint64_t       tmax   = c.tmax;
+    if (!c.tmax_given)
+        tmax = (uint64_t)std::ceil(std::sqrt((double)n_user) / 64.0) * 64; // build_update.py:487
+    laying.start();
+    gnhibf::Layout lay;
+    SketchLaps     sketch_laps;
+    if (c.layout == "sketch" || c.layout == "similarity")
+    {
+        std::string err;
+        if (!lay_out_by_sketches(c, targets, user_target, counts, (uint32_t)tmax, h, lay, sketch_laps, err))
+            return fail(err);
+    }
+    else
+        lay = gnhibf::lay_out(counts, (uint32_t)tmax);
+    laying.stop();
+
+    // rows per IBF: the largest need of its runs; a merged bin holds the union of the sets below it
+    std::vector<HibfShape> ibfs(lay.ibfs.size());
+    uint64_t               device_bits = 0;
+    for (uint32_t i = 0; i < lay.ibfs.size(); ++i)
+    {
+        const gnhibf::Ibf& f = lay.ibfs[i];
+        uint64_t           rows = 0;
+        for (const gnhibf::Run& r : f.runs)
+        {
+            uint64_t n = 0;
+            if (r.user >= 0)
+                n = counts[r.user];
+            else
+            {
+                std::vector<const uint64_t*> sets;
+                std::vector<uint64_t>        sizes;
+                for (uint32_t u : lay.ibfs[r.child].members)
+                {
+                    sets.push_back(targets[user_target[u]].hashes.data());
+                    sizes.push_back(counts[u]);
+                }
+                if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), nullptr, 0, &n) != GN_OK)
+                    return fail(gn_last_error());
+            }
+            rows = std::max(rows, gnbuild::hibf_run_bits(n, r.n_bins, c.max_fp, h));
+        }
+        ibfs[i].bins = f.bins;
+        ibfs[i].rows = rows;
+        gnhibf::tables_of(lay, i, ibfs[i].next_ibf_id, ibfs[i].bin_to_user);
+        device_bits += rows * gn_hibf_row_stride_words((f.bins + 63) >> 6) * 64;
+    }
+    uniting.stop();
+    if (c.verbose)
+    {
+        std::cerr << "hibf_config:" << '\n'
+                  << "user_bins      " << n_user << '\n'
+                  << "tmax           " << tmax << '\n'
+                  << "ibfs           " << ibfs.size() << '\n'
+                  << "levels         " << lay.levels << '\n'
+                  << "layout         " << c.layout << '\n'
+                  << "hash_functions " << unsigned(h) << '\n'
+                  << "max_fp         " << c.max_fp << '\n';
+        std::cerr << "Filter size: " << device_bits << " Bits (" << device_bits / static_cast<double>(8388608u) << " Megabytes)" << std::endl;
+    }
+
+    filling.start();
+    gnhost::HibfDescs descs;
+    for (const HibfShape& s : ibfs)
+        descs.add(s.bins, s.rows, h, s.next_ibf_id, s.bin_to_user);
+    gnhost::OwnedFilter flt = descs.upload(c.device, n_user);
+    if (!flt)
+        return fail(gn_last_error());
+    // every user bin's path: its run in its leaf IBF, then the merged bin that leads there in each IBF above
+    const gnhibf::Paths paths = gnhibf::paths_of(lay, counts);
+    try
+    {
+        gnhibf::for_each_pooled(
+            n_user,
+            [&](size_t u) { return hash_set(targets[user_target[u]]); },
+            [&](size_t u) { return &paths.entries[u * paths.depth]; }, paths.depth,
+            [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>&) {
+                if (gn_filter_emplace_path(flt.get(), hashes, off, (uint32_t)n, p, paths.depth) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+            });
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e.what());
+    }
+    filling.stop();
+
+    writing.start();
+    std::string err;
+    std::vector<std::vector<std::string>> bin_path; // one file per user bin
+    for (const std::string& f : files)
+        bin_path.push_back({ f });
+    const bool saved = save_hibf(c, flt.get(), ibfs, h, bin_path, files, err);
+    flt.reset();
+    if (!saved)
+        return fail(err);
+    writing.stop();
+    whole.stop();
+
+    if (!c.quiet)
+    {
+        print_stats(c, totals, counting, "Layout and unions start: ", uniting, filling, writing, whole);
+        std::cerr << " - hibf: " << n_user << " user bins in " << ibfs.size() << " IBFs on " << lay.levels << " level(s), tmax " << tmax << std::endl;
+        std::cerr << std::fixed << std::setprecision(2) << " - filter size: " << device_bits / static_cast<double>(8388608u) << "MB" << std::endl;
+        // (one line a caller can parse: where the time went)
+        std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
+                  << " write " << writing.seconds();
+        if (c.layout == "sketch" || c.layout == "similarity") // (part of `union`: sketches, union table and search)
+            std::cerr << " layout " << laying.seconds();
+        std::cerr << std::endl;
+        if (c.layout == "similarity") // (where the layout lap went; host = the ordering and the searches)
+            std::cerr << " - layout seconds: sketches " << sketch_laps.sketches << " tables " << sketch_laps.tables << " pairs " << sketch_laps.pairs << " host "
+                      << laying.seconds() - sketch_laps.sketches - sketch_laps.tables - sketch_laps.pairs << std::endl;
+    }
+    return true;
+}
+
+} // namespace gnbuild

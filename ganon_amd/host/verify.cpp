@@ -8,6 +8,7 @@
 // seed or shift arithmetic fails at once, and the first false negative is printed with its hash, its h rows and the bits found
 // there.  This is the first thing to run on a filter written by the reference's ganon-build (scripts/first_contact.sh).
 #include "config.hpp"
+#include "device_sink.hpp"
 #include "filter_io.hpp"
 #include "hasher.hpp"
 #include "hostmem.hpp"
@@ -22,90 +23,6 @@
 
 namespace gnhost
 {
-
-namespace
-{
-
-// the filter's bits into HBM of one device through the streaming loader (what DeviceSet does for a replica, placement.hpp)
-class OneDeviceSink final : public FilterSink
-{
-public:
-    explicit OneDeviceSink(int device) : device_(device) {}
-    ~OneDeviceSink() override
-    {
-        if (f_)
-            gn_filter_free(f_);
-        for (auto& s : stage_)
-            if (s.ptr)
-                gn_pinned_free(s.ptr);
-    }
-    bool begin(const FilterMeta& f, std::string& err) override
-    {
-        const IbfShape&       m = f.shapes.at(0);
-        std::vector<uint32_t> bin2target(m.bins, 0xFFFFFFFFu);
-        for (size_t t = 0; t < f.targets.size(); ++t)
-            for (uint64_t b : f.target_bins[t])
-                bin2target[b] = (uint32_t)t;
-        gn_ibf_desc d{ nullptr, m.bin_size, m.bin_words, m.bins, (uint32_t)m.hash_funs, (uint32_t)m.hash_shift };
-        words_ = m.bin_words;
-        if (gn_filter_upload_ibf(device_, &d, bin2target.data(), (uint32_t)f.targets.size(), &f_) != GN_OK)
-        {
-            err = gn_last_error();
-            return false;
-        }
-        return true;
-    }
-    uint64_t* staging(int which, size_t bytes) override
-    {
-        Stage& s = stage_[which & 1];
-        if (s.bytes < bytes)
-        {
-            if (s.ptr)
-                gn_pinned_free(s.ptr);
-            s = Stage{};
-            void* p = nullptr;
-            if (gn_pinned_alloc(bytes, &p) != GN_OK)
-                return nullptr;
-            s.ptr = p, s.bytes = bytes;
-        }
-        return static_cast<uint64_t*>(s.ptr);
-    }
-    bool rows(uint32_t, uint64_t row_begin, uint64_t n_rows, const uint64_t* src, std::string& err) override
-    {
-        if (gn_filter_write_rows(f_, 0, row_begin, n_rows, src, words_, 0) == GN_OK)
-            return true;
-        err = gn_last_error();
-        return false;
-    }
-    bool drain(std::string& err) override
-    {
-        if (gn_filter_write_sync(f_) == GN_OK)
-            return true;
-        err = gn_last_error();
-        return false;
-    }
-    bool end(std::string& err) override
-    {
-        if (gn_filter_finalize(f_) == GN_OK)
-            return true;
-        err = gn_last_error();
-        return false;
-    }
-    gn_filter* filter() const { return f_; }
-
-private:
-    struct Stage
-    {
-        void*  ptr   = nullptr;
-        size_t bytes = 0;
-    };
-    int        device_;
-    uint64_t   words_ = 0;
-    gn_filter* f_     = nullptr;
-    Stage      stage_[2];
-};
-
-} // namespace
 
 bool verify_filter(const Config& config)
 {
@@ -124,8 +41,8 @@ bool verify_filter(const Config& config)
     const int device = config.devices.empty() ? 0 : config.devices.front();
     try
     {
-        FilterMeta    meta;
-        OneDeviceSink sink(device);
+        FilterMeta meta;
+        DeviceSink sink(device);
         load_filter_file(config.ibf[0], false, meta, sink);
         const IbfShape& m = meta.shapes.at(0);
         const uint32_t  k = meta.ibf_config.kmer_size, w = meta.ibf_config.window_size;
