@@ -12,6 +12,7 @@
 // (/root/reference/src/ganon/build_update.py:411-518).  HBM-bound integer work: depth * h atomic ORs per hash, each to a row
 // of its own.
 #include "gn_build_row.h"
+#include "gn_scan.h"
 #include <hipcub/hipcub.hpp>
 #include <vector>
 
@@ -180,6 +181,24 @@ static int gn_paths_resolve(const char* who, const gn_filter* f, const uint64_t*
     return GN_OK;
 }
 
+// hashes of a round of gn_path_rounds: all of them, at most 32 M
+static inline uint64_t gn_path_step(uint64_t total) { return total < (32ull << 20) ? total : (32ull << 20); }
+
+// Items gn_path_rounds cuts hashes [lo, hi) of the call into when they are one set: a set is cut at every round boundary (a multiple
+// of `step`) and from there into items of GN_PATH_CHUNK.  Items are numbered through the call in the order they are launched: sets in
+// order, rounds in order, so a set's items are consecutive.
+static inline uint64_t gn_path_items_of(uint64_t lo, uint64_t hi, uint64_t step)
+{
+    uint64_t n = 0;
+    while (lo < hi)
+    {
+        const uint64_t end = std::min(hi, (lo / step + 1) * step);
+        n += (end - lo + GN_PATH_CHUNK - 1) / GN_PATH_CHUNK;
+        lo = end;
+    }
+    return n;
+}
+
 // Argument checks, GnPathDev resolution, GnPathItem cutting and the staging upload of gn_filter_emplace_path and gn_filter_probe_path:
 // every bin a hash can reach is checked before anything is launched (the row is below S by construction, gn_build_row); then
 // launch(stage, items, n_items, paths) is called on f->load_st once per round of at most 32 M hashes, and waited for.
@@ -201,7 +220,7 @@ static int gn_path_rounds(const char* who, gn_filter* f, const uint64_t* hashes,
     if (!f->load_st)
         GN_HIP(hipStreamCreateWithFlags(&f->load_st, hipStreamNonBlocking));
     // staged through the device buffer that stays with the filter, at most 32 M hashes at a time (as gn_filter_emplace_split)
-    const uint64_t step = total < (32ull << 20) ? total : (32ull << 20);
+    const uint64_t step = gn_path_step(total);
     GN_HIP(f->d_emplace_stage.reserve(step, step));
     const uint64_t          max_items = step / GN_PATH_CHUNK + n_sets + 2;
     std::vector<GnPathItem> items; // (before the buffers it is copied into: they are freed, which waits for the device, first)
@@ -514,6 +533,295 @@ extern "C" int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes
     GN_HIP(hipStreamSynchronize(f->load_st));
     GN_HIP(hipMemcpy(found, d_found, (size_t)n_paths * 8, hipMemcpyDeviceToHost));
     return GN_OK;
+}
+
+// ---- gn_filter_extend_path: more hashes for user bins that are filled already ------------------------------------------------------
+// Two sweeps over the items of the whole call, as gn_path_rounds cuts them; item g of the call is item g - item_base of its round.
+// Sweep 1 is the probe restricted to entry 0 (the user bin's leaf run): per word of the run all 8 * H row words are loaded before any is
+// looked at, ANDed and masked to the run.  Instead of a count the wave leaves its eight 64-bit ballots of "has a hash and the run does not
+// hold it" -- flags[g * 8 + j], bit l = slot j of lane l -- and their population, counts[g].  Nothing is ORed before every round of sweep 1
+// is through: sweep 2 reads the flags and never the filter, so that no wave's new bits turn another wave's absent hash into a present one.
+template <uint32_t H>
+__global__ __launch_bounds__(256) void gn_extend_mark_kernel(const uint64_t* __restrict__ stage, const GnPathItem* __restrict__ items, uint32_t n_items,
+                                                             const GnPathDev* __restrict__ paths, uint32_t depth, uint64_t item_base,
+                                                             unsigned long long* __restrict__ flags, uint32_t* __restrict__ counts)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t   lane = threadIdx.x & 63u;
+    const GnPathItem it   = items[item];
+    uint64_t         v[GN_PATH_PER_LANE];
+    uint32_t         valid = 0; // bit j: slot j holds a hash of the item
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+        valid |= (q < it.cnt ? 1u : 0u) << j;
+    }
+    const GnPathDev    e    = paths[(uint64_t)it.seg * depth]; // (n_bins >= 1: the host refuses a set with hashes and no leaf run)
+    GnGlobalConstWord* rows = (GnGlobalConstWord*)e.rows;
+    const uint32_t     w1   = (e.first_bin + e.n_bins - 1) >> 6;
+    uint32_t           hit  = 0;
+    for (uint32_t w = e.first_bin >> 6; w <= w1; ++w)
+    {
+        const uint64_t mask = gn_run_mask(e.first_bin, e.n_bins, w);
+        uint64_t       r[GN_PATH_PER_LANE][H];
+#pragma unroll
+        for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+#pragma unroll
+            for (uint32_t i = 0; i < H; ++i)
+                r[j][i] = rows[(uint64_t)gn_build_row(v[j], i, e.shift, e.S) * e.Ws + w];
+#pragma unroll
+        for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+        {
+            uint64_t a = r[j][0];
+#pragma unroll
+            for (uint32_t i = 1; i < H; ++i)
+                a &= r[j][i];
+            hit |= ((a & mask) != 0 ? 1u : 0u) << j;
+        }
+    }
+    const uint32_t     absent = valid & ~hit;
+    unsigned long long mine   = 0; // lane j < 8 keeps ballot j: the eight leave as one 64-byte store
+    uint32_t           n      = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+    {
+        const unsigned long long b = __ballot((absent >> j) & 1u);
+        n += (uint32_t)__popcll(b);
+        mine = lane == j ? b : mine;
+    }
+    const uint64_t g = item_base + item;
+    if (lane < GN_PATH_PER_LANE)
+        flags[g * GN_PATH_PER_LANE + lane] = mine;
+    if (lane == 0)
+        counts[g] = n;
+}
+
+// Sweep 2.  ranks[g] is the exclusive sum of counts[] over the call, so ranks[g] - ranks[set_first[seg]] is the rank within its set of the
+// item's first absent hash; the absent hash in slot j of lane l follows the absent ones of the slots below and of the lanes below in its
+// slot.  cum + cum_at[seg] is the set's running sum of quotas, n_bins + 1 entries from 0: rank r belongs to the bin j with
+// cum[j] <= r < cum[j + 1].  The bins of the item's first and last absent hash are searched once for the wave (item, flags and table
+// come through scalar loads); a lane searches, between those two, only when they differ.  Then every hash of the item, present or not,
+// goes into the merged bins above, as gn_emplace_path_kernel puts it there.
+__global__ __launch_bounds__(256) void gn_extend_insert_kernel(const uint64_t* __restrict__ stage, const GnPathItem* __restrict__ items, uint32_t n_items,
+                                                               const GnPathDev* __restrict__ paths, uint32_t depth, uint32_t h, uint64_t item_base,
+                                                               const unsigned long long* __restrict__ flags, const uint64_t* __restrict__ ranks,
+                                                               const uint64_t* __restrict__ set_first, const uint64_t* __restrict__ cum,
+                                                               const uint64_t* __restrict__ cum_at)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t   lane = threadIdx.x & 63u;
+    const GnPathItem it   = items[item];
+    uint64_t         v[GN_PATH_PER_LANE];
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+    }
+    const uint64_t     g = item_base + item;
+    unsigned long long b[GN_PATH_PER_LANE];
+    uint32_t           n_absent = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+    {
+        b[j] = flags[g * GN_PATH_PER_LANE + j];
+        n_absent += (uint32_t)__popcll(b[j]);
+    }
+    const GnPathDev* __restrict__ p = paths + (uint64_t)it.seg * depth;
+    if (n_absent)
+    {
+        const GnPathDev e    = p[0];
+        const uint64_t  base = ranks[g] - ranks[set_first[it.seg]];
+        const uint64_t* __restrict__ c = cum + cum_at[it.seg] + 1; // c[j]: the quotas of bins 0 .. j of the run, summed
+        // the first j of lo .. hi with c[j] > r, hi when there is none below it (j < hi <= n_bins - 1 is all that is read)
+        auto bin_of = [&](uint64_t r, uint32_t lo, uint32_t hi) {
+            while (lo < hi)
+            {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (c[mid] <= r)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            return lo;
+        };
+        const uint32_t b_lo = bin_of(base, 0u, e.n_bins - 1u), b_hi = bin_of(base + n_absent - 1u, b_lo, e.n_bins - 1u);
+        uint32_t       below = 0; // absent hashes of the item in the slots before this one
+#pragma unroll
+        for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+        {
+            if ((b[j] >> lane) & 1ull)
+            {
+                const uint64_t rank = base + below + (uint32_t)__popcll(b[j] & ((1ull << lane) - 1ull));
+                const uint32_t bin  = e.first_bin + (b_lo == b_hi ? b_lo : bin_of(rank, b_lo, b_hi));
+                GnGlobalWord*  word = (GnGlobalWord*)e.rows + (bin >> 6);
+                const uint64_t bit  = 1ULL << (bin & 63);
+                for (uint32_t i = 0; i < h; ++i)
+                    (void)__hip_atomic_fetch_or(word + (uint64_t)gn_build_row(v[j], i, e.shift, e.S) * e.Ws, bit, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+            }
+            below += (uint32_t)__popcll(b[j]);
+        }
+    }
+    for (uint32_t d = 1; d < depth; ++d)
+    {
+        const GnPathDev e = p[d];
+        if (e.n_bins == 0)
+            break;
+        GnGlobalWord*  word = (GnGlobalWord*)e.rows + (e.first_bin >> 6); // (n_bins == 1: checked on the host)
+        const uint64_t bit  = 1ULL << (e.first_bin & 63);
+#pragma unroll
+        for (uint32_t j = 0; j < GN_PATH_PER_LANE; ++j)
+        {
+            if (j * 64u + lane >= it.cnt)
+                continue;
+            for (uint32_t i = 0; i < h; ++i)
+                (void)__hip_atomic_fetch_or(word + (uint64_t)gn_build_row(v[j], i, e.shift, e.S) * e.Ws, bit, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+template <uint32_t H>
+static hipError_t gn_extend_mark_launch(hipStream_t st, const uint64_t* stage, const GnPathItem* items, uint32_t n_items, const GnPathDev* paths, uint32_t depth,
+                                        uint64_t item_base, unsigned long long* flags, uint32_t* counts)
+{
+    hipLaunchKernelGGL(gn_extend_mark_kernel<H>, dim3((n_items + 3) / 4), dim3(256), 0, st, stage, items, n_items, paths, depth, item_base, flags, counts);
+    return hipSuccess;
+}
+
+extern "C" int gn_filter_extend_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                                     uint32_t depth, const uint64_t* deal_off, const uint64_t* deal)
+{
+    static const char* const who = "gn_filter_extend_path";
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_extend_path needs an HIBF filter");
+    if (n_sets == 0)
+        return GN_OK;
+    if (!set_off || !paths || !deal_off || depth == 0 || (set_off[n_sets] && !hashes))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    const uint32_t h = f->ibfs[0].h;
+    if (h < 1 || h > GN_IBF_MAX_HASH_FUNS)
+        return gn_fail(GN_EINVAL, "%s: %u hash functions", who, h);
+    const uint64_t total = set_off[n_sets];
+    // the host's checks: the shape of every path, one quota per bin of the leaf run, strictly ascending sets
+    std::vector<uint64_t> quota(n_sets, 0); // a set's quotas summed; above `total` where the sum does not fit
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        if (set_off[s + 1] < set_off[s] || set_off[s + 1] > total) // (the sets are read below: none may reach beyond the last offset)
+            return gn_fail(GN_EINVAL, "%s: set offsets descend at set %u", who, s);
+        const gn_path_entry* p = paths + (size_t)s * depth;
+        if (deal_off[s + 1] < deal_off[s] || deal_off[s + 1] - deal_off[s] != p[0].n_bins)
+            return gn_fail(GN_EINVAL, "%s: set %u: %llu quotas for a run of %u bins", who, s, (unsigned long long)(deal_off[s + 1] - deal_off[s]), p[0].n_bins);
+        if (p[0].n_bins == 0 && set_off[s + 1] != set_off[s])
+            return gn_fail(GN_EINVAL, "%s: set %u has hashes and no leaf run", who, s);
+        if (p[0].n_bins && !deal)
+            return gn_fail(GN_EINVAL, "%s: null argument", who);
+        for (uint32_t d = 1; d < depth && p[d - 1].n_bins && p[d].n_bins; ++d)
+            if (p[d].n_bins != 1)
+                return gn_fail(GN_EINVAL, "%s: set %u level %u: a run of %u bins above the leaf", who, s, d, p[d].n_bins);
+        for (uint64_t j = deal_off[s]; j < deal_off[s + 1]; ++j)
+            quota[s] = deal[j] > total || quota[s] > total ? total + 1 : quota[s] + deal[j];
+        for (uint64_t i = set_off[s] + 1; i < set_off[s + 1]; ++i)
+            if (hashes[i] <= hashes[i - 1])
+                return gn_fail(GN_EINVAL, "%s: set %u is not strictly ascending at hash %llu", who, s, (unsigned long long)(i - set_off[s]));
+    }
+    const uint64_t step = gn_path_step(total);
+    std::vector<uint64_t> set_first(n_sets + 1, 0), cum, cum_at(n_sets);
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        set_first[s + 1] = set_first[s] + (total ? gn_path_items_of(set_off[s], set_off[s + 1], step) : 0);
+        cum_at[s]        = cum.size();
+        cum.push_back(0);
+        for (uint64_t j = deal_off[s]; j < deal_off[s + 1]; ++j)
+            cum.push_back(cum.back() + std::min(deal[j], total + 1)); // (read by sweep 2 only when the sum is the absent count)
+    }
+    const uint64_t n_items = set_first[n_sets];
+    if (n_items + 1 > 0x7FFFFFFFull) // (the scan takes its item count as an int)
+        return gn_fail(GN_ERANGE, "%s: %llu hashes in one call", who, (unsigned long long)total);
+
+    GnDev<unsigned long long> d_flags;
+    GnDev<uint32_t>           d_counts;
+    GnDev<uint64_t>           d_ranks, d_set_first, d_cum, d_cum_at;
+    GnDev<uint8_t>            d_tmp;
+    std::vector<uint64_t>     ranks(n_items + 1, 0);
+    if (total)
+    {
+        GN_HIP(hipSetDevice(f->device));
+        GN_HIP(d_flags.alloc(n_items * GN_PATH_PER_LANE));
+        GN_HIP(d_counts.alloc(n_items + 1));
+        GN_HIP(d_ranks.alloc(n_items + 1));
+    }
+    uint64_t at = 0; // items launched so far
+    int      rc = gn_path_rounds(who, f, hashes, set_off, n_sets, paths, depth, false,
+                                 [&](const uint64_t* stage, const GnPathItem* items, uint32_t n, const GnPathDev* d_paths) -> hipError_t {
+                                     if (at + n > n_items)
+                                         return hipErrorInvalidValue; // (cannot happen: gn_path_items_of counts what gn_path_rounds cuts)
+                                     const uint64_t base = at;
+                                     at += n;
+                                     // (the entry behind the last item stays 0: its rank is the call's absent count)
+                                     if (base == 0)
+                                         if (const hipError_t e = hipMemsetAsync(d_counts, 0, (n_items + 1) * sizeof(uint32_t), f->load_st))
+                                             return e;
+                                     switch (h)
+                                     {
+                                     case 1: return gn_extend_mark_launch<1>(f->load_st, stage, items, n, d_paths, depth, base, d_flags, d_counts);
+                                     case 2: return gn_extend_mark_launch<2>(f->load_st, stage, items, n, d_paths, depth, base, d_flags, d_counts);
+                                     case 3: return gn_extend_mark_launch<3>(f->load_st, stage, items, n, d_paths, depth, base, d_flags, d_counts);
+                                     case 4: return gn_extend_mark_launch<4>(f->load_st, stage, items, n, d_paths, depth, base, d_flags, d_counts);
+                                     default: return gn_extend_mark_launch<5>(f->load_st, stage, items, n, d_paths, depth, base, d_flags, d_counts);
+                                     }
+                                 });
+    if (rc != GN_OK)
+        return rc;
+    if (total)
+    {
+        if (at != n_items)
+            GN_HIP(hipErrorInvalidValue);
+        // between the sweeps: the items' ranks, and every set's absent count against its quotas (every round was waited for)
+        size_t tmp_bytes = 0;
+        GN_HIP(gn_scan_counts(nullptr, tmp_bytes, d_counts.get(), d_ranks.get(), (int)(n_items + 1), f->load_st));
+        GN_HIP(d_tmp.alloc(tmp_bytes));
+        GN_HIP(gn_scan_counts(d_tmp.get(), tmp_bytes, d_counts.get(), d_ranks.get(), (int)(n_items + 1), f->load_st));
+        GN_HIP(hipMemcpyAsync(ranks.data(), d_ranks, (n_items + 1) * 8, hipMemcpyDeviceToHost, f->load_st));
+        GN_HIP(hipStreamSynchronize(f->load_st));
+    }
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        const uint64_t absent = ranks[set_first[s + 1]] - ranks[set_first[s]];
+        if (quota[s] != absent)
+        {
+            if (quota[s] > total)
+                return gn_fail(GN_EINVAL, "%s: set %u: the quotas sum to more than the call's %llu hashes, %llu of the set's %llu are absent from its run; nothing written",
+                               who, s, (unsigned long long)total, (unsigned long long)absent, (unsigned long long)(set_off[s + 1] - set_off[s]));
+            return gn_fail(GN_EINVAL, "%s: set %u: the quotas sum to %llu, %llu of the set's %llu hashes are absent from its run; nothing written", who, s,
+                           (unsigned long long)quota[s], (unsigned long long)absent, (unsigned long long)(set_off[s + 1] - set_off[s]));
+        }
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(d_set_first.upload(set_first.data(), set_first.size()));
+    GN_HIP(d_cum.upload(cum.data(), cum.size()));
+    GN_HIP(d_cum_at.upload(cum_at.data(), cum_at.size()));
+    at = 0;
+    rc = gn_path_rounds(who, f, hashes, set_off, n_sets, paths, depth, false,
+                        [&](const uint64_t* stage, const GnPathItem* items, uint32_t n, const GnPathDev* d_paths) -> hipError_t {
+                            if (at + n > n_items)
+                                return hipErrorInvalidValue; // (cannot happen: the same cut as sweep 1)
+                            const uint64_t base = at;
+                            at += n;
+                            hipLaunchKernelGGL(gn_extend_insert_kernel, dim3((n + 3) / 4), dim3(256), 0, f->load_st, stage, items, n, d_paths, depth, h, base,
+                                               (const unsigned long long*)d_flags, (const uint64_t*)d_ranks, (const uint64_t*)d_set_first,
+                                               (const uint64_t*)d_cum, (const uint64_t*)d_cum_at);
+                            return hipSuccess;
+                        });
+    return rc;
 }
 
 // ---- gn_filter_bin_popcounts: how full is every technical bin? -------------------------------------------------------------------

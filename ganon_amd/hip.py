@@ -33,7 +33,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
-               "gn_filter_bin_popcounts", "gn_filter_copy_ibf",
+               "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_extend_path",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
 
 
@@ -167,6 +167,7 @@ def load_library():
     L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
     L.gn_filter_bin_popcounts.argtypes = [vp, u32, vp]
     L.gn_filter_copy_ibf.argtypes = [vp, u32, vp, u32]
+    L.gn_filter_extend_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp]
     L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
     L.gn_sketches_free.argtypes = [vp]
     L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
@@ -603,6 +604,22 @@ class HipFilter:
         hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
         hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
         _check(load_library().gn_filter_emplace_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1]))
+
+    def extend_path(self, sets: Sequence[np.ndarray], paths: np.ndarray, quotas: Sequence[np.ndarray]) -> None:
+        """gn_filter_extend_path: sets[s] (strictly ascending uint64) along paths[s] (PATH_DTYPE, [len(sets), depth]) of an HIBF that holds
+        part of them already; quotas[s][j] = how many of the set's absent hashes bin first_bin + j of its leaf run takes"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(sets) == len(quotas)
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(a) for a in sets])
+        hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        deal_off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        deal_off[1:] = np.cumsum([len(q) for q in quotas])
+        deal = np.concatenate([np.asarray(q, dtype=np.uint64) for q in quotas]) if len(sets) else np.zeros(0, np.uint64)
+        deal = np.ascontiguousarray(deal, dtype=np.uint64)
+        _check(load_library().gn_filter_extend_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1],
+                                                    _p(deal_off), _p(deal)))
 
     def probe_path(self, sets: Sequence[np.ndarray], paths: np.ndarray, with_lost_at: bool = True):
         """gn_filter_probe_path: sets[s] along paths[s] (PATH_DTYPE, [len(sets), depth]) -> (found uint64 [n], lost_at uint64 [n, depth] or

@@ -97,6 +97,8 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--layout needs --hibf");
     if (c.layout_given && c.layout != "rule" && c.layout != "sketch" && c.layout != "similarity")
         return say("--layout has to be rule, sketch or similarity");
+    if (c.extend && !c.update_given)
+        return say("--extend needs --update (it adds the inputs' sequences to targets of the index --update names)");
     if (c.update_given)
     {
         if (!c.hibf)
@@ -195,6 +197,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--verify-index      " << c.verify_index << '\n';
     if (c.update_given)
         std::cerr << "--update            " << c.update << '\n';
+    if (c.extend)
+        std::cerr << "--extend            " << c.extend << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -237,6 +241,11 @@ const char* kHelp =
     "                               how many bins each IBF gained, so that one sees when a rebuild is due.  k, w, the hash\n"
     "                               functions and the false-positive rate come from the index.  A target the index holds\n"
     "                               already is refused.  Not with --verify-index, --layout, --tmax, --filter-size, --mode\n"
+    "      --extend                 [--update] a target whose name the index holds once is not refused: its user bin gains the\n"
+    "                               hashes of the target's input files that it does not hold yet, dealt to the bins of its run by\n"
+    "                               how full the bits show them; the merged bins above take all of them.  A run is never moved or\n"
+    "                               widened: when a bin is predicted over its bound nothing is written and the targets are named\n"
+    "                               (leave them out or rebuild).  Unknown names are added as new targets, as without the flag\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -279,7 +288,7 @@ int parse_args(int argc, char** argv, Config& c)
         auto s = shorts.find(a);
         if (s != shorts.end())
             a = s->second;
-        if (a == "--help" || a == "--version" || a == "--verbose" || a == "--quiet" || a == "--hibf")
+        if (a == "--help" || a == "--version" || a == "--verbose" || a == "--quiet" || a == "--hibf" || a == "--extend")
         {
             vals[a] = has ? v : "true";
             continue;
@@ -366,6 +375,7 @@ int parse_args(int argc, char** argv, Config& c)
             c.device = (int)u("--device", 1 << 20);
         c.verbose = vals.count("--verbose") && vals["--verbose"] != "false";
         c.quiet   = vals.count("--quiet") && vals["--quiet"] != "false";
+        c.extend  = vals.count("--extend") && vals["--extend"] != "false";
     }
     catch (const std::exception& e)
     {

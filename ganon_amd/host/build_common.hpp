@@ -43,6 +43,7 @@ struct Config // Config.hpp:10-27
     std::string verify_index;    // (--hibf only: check this index against the inputs instead of building one)
     std::string update;          // (--hibf only: add the inputs' targets to this index and write the result to --output-file)
     bool        update_given = false, max_fp_given = false, mode_given = false;
+    bool        extend = false;  // (--update only: a target the index holds gains the inputs' sequences)
     bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
 };
 

@@ -10,7 +10,9 @@
 #include <cmath>
 #include <iomanip>
 #include <memory>
+#include <numeric>
 #include <set>
+#include <sstream>
 
 namespace gnbuild
 {
@@ -18,8 +20,10 @@ namespace gnbuild
 bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counting)
 {
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> fresh_target; // targets with a hash, in input order: new user bin n_user_old + position
+    std::vector<uint32_t> fresh_target; // the new targets with a hash, in input order: new user bin n_user_old + position
     std::vector<uint64_t> fresh_counts;
+    std::vector<uint32_t> ext_target;   // --extend: the targets the index holds, in input order, and their user bins
+    std::vector<uint64_t> ext_user;
     for (uint32_t t = 0; t < targets.size(); ++t)
     {
         if (targets[t].hashes.empty())
@@ -27,9 +31,8 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         if (!unite_files(c, targets[t]))
             return fail(gn_last_error());
         fresh_target.push_back(t);
-        fresh_counts.push_back(targets[t].hashes.size());
     }
-    if (fresh_counts.empty())
+    if (fresh_target.empty())
         return fail("No valid sequences to build");
     const double hash_s = counting.seconds() + since(t0);
     try
@@ -38,9 +41,31 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             gnhost::FilterMeta names;
             gnhost::read_hibf_meta(c.update, names);
             const std::set<std::string> have(names.targets.begin(), names.targets.end());
+            std::vector<uint32_t>       added;
             for (uint32_t t : fresh_target)
-                if (have.count(name_as_read(targets[t].name)))
+            {
+                const std::string name = name_as_read(targets[t].name);
+                if (!have.count(name))
+                {
+                    added.push_back(t);
+                    continue;
+                }
+                if (!c.extend)
                     return fail("--update: target " + targets[t].name + " is already in the index (adding sequences to an existing user bin is not supported); nothing written");
+                uint64_t held = 0, user = 0;
+                for (size_t i = 0; i < names.targets.size(); ++i)
+                    if (names.targets[i] == name)
+                    {
+                        held += i < names.target_bins.size() ? names.target_bins[i].size() : 1;
+                        user = i < names.target_bins.size() && !names.target_bins[i].empty() ? names.target_bins[i][0] : i;
+                    }
+                if (held != 1)
+                    return fail("--update --extend: " + std::to_string(held) + " user bins of the index are named " + targets[t].name + "; nothing written");
+                ext_target.push_back(t), ext_user.push_back(user);
+            }
+            fresh_target.swap(added);
+            for (uint32_t t : fresh_target)
+                fresh_counts.push_back(targets[t].hashes.size());
         }
         t0 = std::chrono::steady_clock::now();
         gnhost::FilterMeta meta;
@@ -71,9 +96,48 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         const double count_s = since(t0);
 
         t0 = std::chrono::steady_clock::now();
-        const gnhibf::UpdatePlan plan = gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_old, h, fpr, pop, fresh_counts);
-        const uint32_t           depth = plan.paths.depth;
-        const double             plan_s = since(t0);
+        // --extend: what every extension set's path lacks (A's bits), the quotas of its run and the fills the new user bins start from
+        gnhibf::Paths      old_paths;
+        gnhibf::ExtendPlan ex;
+        double             probe_s = 0;
+        if (!ext_target.empty())
+        {
+            old_paths = gnhibf::derive_paths(bins, meta.next_ibf_id, meta.bin_to_user, n_old);
+            const uint32_t                   d0 = old_paths.depth;
+            std::vector<gnhibf::ExtendInput> in(ext_target.size());
+            for (size_t j = 0; j < in.size(); ++j)
+            {
+                if (ext_user[j] >= n_old)
+                    return fail("--update --extend: the index names user bin " + std::to_string(ext_user[j]) + " of " + std::to_string(n_old));
+                in[j].user_bin = ext_user[j], in[j].hashes = targets[ext_target[j]].hashes.size();
+                in[j].lost_at.assign(d0, 0);
+            }
+            gnhibf::for_each_pooled(
+                in.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &old_paths.entries[(size_t)ext_user[j] * d0]; }, d0,
+                [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>& ids) {
+                    std::vector<uint64_t> found(n), first(n), lost(n * d0);
+                    if (gn_filter_probe_path(sink->filter(), hashes, off, (uint32_t)n, p, d0, found.data(), lost.data(), first.data()) != GN_OK)
+                        throw std::runtime_error(gn_last_error());
+                    for (size_t k = 0; k < n; ++k)
+                        in[ids[k]].lost_at.assign(lost.begin() + k * d0, lost.begin() + (k + 1) * d0);
+                });
+            probe_s = since(t0);
+            ex      = gnhibf::plan_extend(old_paths, bins, rows, h, fpr, pop, in);
+            if (!ex.over.empty())
+            {
+                std::ostringstream m;
+                m << "--update --extend: " << ex.over.size() << " bin(s) would be over their bound; nothing written:";
+                for (const gnhibf::ExtendOver& o : ex.over)
+                    m << "\n  target " << targets[ext_target[o.extension]].name << ": IBF " << o.ibf << " bin " << o.bin << " predicted " << std::fixed << std::setprecision(1)
+                      << o.bits_predicted << " bits, bound " << o.bound;
+                m << "\na run is never moved or widened: leave it out or rebuild";
+                return fail(m.str());
+            }
+        }
+        const gnhibf::UpdatePlan plan =
+            gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_old, h, fpr, pop, fresh_counts, ext_target.empty() ? nullptr : &ex.fills);
+        const uint32_t depth  = plan.paths.depth;
+        const double   plan_s = since(t0) - probe_s;
 
         // filter B: the same rows, the new bins.  A and B are on the device together until every IBF is moved
         t0 = std::chrono::steady_clock::now();
@@ -109,8 +173,23 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         sink.reset(); // (frees A)
         const double copy_s = since(t0);
 
-        // the new sets along their paths, pooled as run_hibf pools them
+        // the new sets along their paths, pooled as run_hibf pools them; before them the extensions, by their quotas
+        // (the pooler may cut the extensions into several calls.  A later call takes presence against B after the earlier ORs, not against A,
+        // where lost_at was counted; the counts still agree, because presence is a matter of the run's own columns and only the run's own set
+        // writes them -- one extension per user bin, and the new targets are inserted afterwards)
         t0 = std::chrono::steady_clock::now();
+        gnhibf::for_each_pooled(
+            ext_target.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &old_paths.entries[(size_t)ext_user[j] * depth]; }, depth,
+            [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>& ids) {
+                std::vector<uint64_t> deal_off{ 0 }, deal;
+                for (size_t k = 0; k < n; ++k)
+                {
+                    deal.insert(deal.end(), ex.quotas[ids[k]].begin(), ex.quotas[ids[k]].end());
+                    deal_off.push_back(deal.size());
+                }
+                if (gn_filter_extend_path(b_flt.get(), hashes, off, (uint32_t)n, p, depth, deal_off.data(), deal.data()) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+            });
         gnhibf::for_each_pooled(
             fresh_target.size(),
             [&](size_t j) { return hash_set(targets[fresh_target[j]]); },
@@ -129,6 +208,9 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         for (const gn_path_entry& e : plan.paths.entries)
             if (e.n_bins)
                 shown[e.ibf] = true;
+        for (const uint64_t u : ext_user)
+            for (uint32_t d = 0; d < depth && old_paths.entries[(size_t)u * depth + d].n_bins; ++d)
+                shown[old_paths.entries[(size_t)u * depth + d].ibf] = true;
         std::vector<std::vector<uint64_t>> pop_b(n_ibf);
         for (uint64_t i = 0; i < n_ibf; ++i)
             if (shown[i])
@@ -176,6 +258,28 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             std::cout << "\n";
             bins_added += p[0].n_bins;
         }
+        if (c.extend)
+        {
+            std::cout << "#extended\ttarget\tuser_bin\thashes\talready_present\tinserted\tleaf_ibf\tfirst_bin\tbins\tpath\n";
+            for (size_t j = 0; j < ext_target.size(); ++j)
+            {
+                const gn_path_entry* p        = &old_paths.entries[(size_t)ext_user[j] * depth];
+                const uint64_t       n        = targets[ext_target[j]].hashes.size();
+                const uint64_t       inserted = std::accumulate(ex.quotas[j].begin(), ex.quotas[j].end(), uint64_t(0));
+                uint32_t             used     = 0;
+                while (used < depth && p[used].n_bins)
+                    ++used;
+                std::cout << "extended\t" << targets[ext_target[j]].name << "\t" << ext_user[j] << "\t" << n << "\t" << n - inserted << "\t" << inserted << "\t" << p[0].ibf
+                          << "\t" << p[0].first_bin << "\t" << p[0].n_bins << "\t";
+                for (uint32_t d = used; d-- > 0;)
+                    std::cout << p[d].ibf << ":" << p[d].first_bin << (d ? " " : "");
+                std::cout << "\n";
+            }
+            std::cout << "#run\tibf\tbin\tdealt\tbits_before\tbits_predicted\tbits_after\n";
+            for (const gnhibf::ExtendRunBin& r : ex.run)
+                std::cout << "run\t" << r.ibf << "\t" << r.bin << "\t" << r.dealt << "\t" << r.bits_before << "\t" << std::fixed << std::setprecision(1) << r.bits_predicted << "\t"
+                          << pop_b[r.ibf][r.bin] << "\n";
+        }
         std::cout << "#ibf\trows\tbins_before\tbins_after\tmax_fill_before\tmax_fill_after\n" << std::fixed << std::setprecision(6);
         for (uint64_t i = 0; i < n_ibf; ++i)
             if (shown[i])
@@ -185,7 +289,16 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         std::cout << "#merged\tibf\tbin\tbits_before\tbits_predicted\tbits_after\n";
         uint64_t fullest = 0, fullest_rows = 1;
         bool     any_touched = false;
-        for (const gnhibf::UpdateTouched& t : plan.touched)
+        std::vector<gnhibf::UpdateTouched> touched = ex.touched; // the extensions' merged bins, then the new user bins'; a bin of both once,
+        for (const gnhibf::UpdateTouched& t : plan.touched)      // with the later prediction (which starts from the earlier)
+        {
+            auto at = std::find_if(touched.begin(), touched.end(), [&](const gnhibf::UpdateTouched& x) { return x.ibf == t.ibf && x.bin == t.bin; });
+            if (at == touched.end())
+                touched.push_back(t);
+            else
+                at->bits_predicted = t.bits_predicted;
+        }
+        for (const gnhibf::UpdateTouched& t : touched)
         {
             const uint64_t after = pop_b[t.ibf][t.bin];
             std::cout << "merged\t" << t.ibf << "\t" << t.bin << "\t" << t.bits_before << "\t" << std::setprecision(1) << t.bits_predicted << std::setprecision(6) << "\t"
@@ -195,7 +308,10 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             any_touched = true;
         }
         std::error_code ec;
-        std::cout << "result\tok\t" << fresh_target.size() << " user bin(s) added, " << bins_added << " bin(s) added, " << fs::file_size(c.update, ec) << " -> "
+        std::cout << "result\tok\t";
+        if (c.extend)
+            std::cout << ext_target.size() << " user bin(s) extended, ";
+        std::cout << fresh_target.size() << " user bin(s) added, " << bins_added << " bin(s) added, " << fs::file_size(c.update, ec) << " -> "
                   << fs::file_size(c.output_file, ec) << " bytes, fullest touched merged bin ";
         if (!any_touched)
             std::cout << "n/a";
@@ -206,7 +322,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
                       << (double)fullest / fullest_rows;
         std::cout << std::endl;
         if (c.verbose && !c.quiet)
-            std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " count " << count_s + count_b_s << " plan " << plan_s << " copy " << copy_s
+            std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " count " << count_s + count_b_s + probe_s << " plan " << plan_s << " copy " << copy_s
                       << " emplace " << emplace_s << " write " << write_s << std::endl;
         return true;
     }

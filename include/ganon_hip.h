@@ -462,6 +462,26 @@ int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes, uint64_t 
 int gn_filter_bin_popcounts(const gn_filter* f, uint32_t ibf_idx, uint64_t* counts);
 int gn_filter_copy_ibf(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf);
 
+/* `ganon-build --hibf --update --extend`: more hashes for user bins that are filled already.  gn_filter_emplace_path cannot do it: it
+ * deals hash i to bin first_bin + i / hashes_per_bin, a reader sums the counts of a user bin's technical bins, and a hash that lands in a
+ * second bin of the run is counted twice.  How the run was dealt is not known either, so what a bin still takes is said by the caller.
+ * gn_filter_extend_path: sets and paths as gn_filter_emplace_path takes them -- entry 0 of a path is the user bin's leaf run, the
+ *   entries above it are merged bins (n_bins == 1), n_bins == 0 ends a path, hashes_per_bin is ignored -- and every set STRICTLY
+ *   ascending.  deal[deal_off[s] + j] is the quota of bin first_bin + j of set s's leaf run; deal_off[s + 1] - deal_off[s] is that
+ *   run's n_bins.  All of the following is taken against the filter as it is when the call starts:
+ *     a hash of set s is PRESENT when it is contained in entry 0 (the rule of gn_filter_probe_path: for at least one bin of the run all
+ *       h rows have that bin's bit set); the ABSENT hashes of the set, in set order, have ranks 0 .. a_s - 1
+ *     the absent hash of rank r is ORed into the leaf bin j with cum[j] <= r < cum[j + 1], cum the running sum of the set's quotas
+ *     a present hash sets no leaf bit: a reader finds it where it is
+ *     every hash of the set, present or not, is ORed into every merged entry above the leaf (a hash that is falsely present in the leaf
+ *       may be missing above)
+ *   GN_EINVAL, and NOTHING written, when the quotas of a set do not sum to a_s (the message names the set and both numbers), for a
+ *   filter that is not an HIBF, a null argument, a set that is not strictly ascending, a quota list that is not as long as the run, a
+ *   run of several bins above the leaf, an IBF or a bin out of range: every check and the whole marking sweep come before the first OR.
+ *   n_sets == 0 and empty sets are legal.  The result is a function of the arguments and the filter's bits alone. */
+int gn_filter_extend_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
+                          uint32_t depth, const uint64_t* deal_off, const uint64_t* deal);
+
 /* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.

@@ -16,6 +16,12 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
                   load, count, plan, copy, emplace, write), the updated file checked over ALL files (--verify-index), beside one full
                   rebuild of all N checked the same way: seconds, bytes and max_observed_fp of both.  Prints "update" per layout;
                   the flat / hibf medians are not run
+  --extend        [--update M] the last M files do not bring new targets: file N - M + j becomes one more file of the target of file j
+                  (with --families F:D, M <= F and N - M a multiple of F, a member of the same family), and the update runs with `--extend`.  One run to warm
+                  up and --runs (5) runs of the update, and as many rebuilds from all N files under the same target names: emplace_s
+                  and total_s of both as min / median / max.  The files of the extended targets, old and new, are 30 % shorter than the
+                  others, so that their bins have room (an index gives a bin that sets its IBF's rows none: the plan refuses,
+                  which is reported as such)
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
@@ -32,11 +38,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": ""}
-pos, hibf, check, argv = [], False, False, sys.argv[1:]
+pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
     if a == "--hibf":
         hibf = True
+    elif a == "--extend":
+        extend = True
     elif a == "--verify":
         check = True
     elif a in opts:
@@ -54,6 +62,9 @@ cols = 70
 lengths = [L] * n_files
 if opts["--lognormal"]:
     lengths = [max(1000, int(L * math.exp(float(opts["--lognormal"]) * z))) for z in np.random.default_rng(2).standard_normal(n_files)]
+if extend and opts["--update"]:  # the files of the extended targets are 30 % shorter than the others: their bins have room
+    for j in range(int(opts["--update"])):
+        lengths[j], lengths[n_files - int(opts["--update"]) + j] = int(0.7 * lengths[j]), int(0.7 * lengths[n_files - int(opts["--update"]) + j])
 n_families, divergence, ancestors = 0, 0.0, []
 if opts["--families"]:
     n_families, divergence = int(opts["--families"].split(":")[0]), float(opts["--families"].split(":")[1])
@@ -146,17 +157,39 @@ def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     return res
 
 
+def spread(values):
+    v = sorted(values)
+    return {"min": v[0], "median": v[len(v) // 2], "max": v[-1], "runs": len(v)} if v else {}
+
+
 def update_run(layout, m):
     """build from all but the last m files, update with those, check the result over all; beside a rebuild of all"""
     lines = open(os.path.join(d, "in.tsv")).read().splitlines(True)
+    if extend:  # the last m files under the names of the first m targets; the check and the rebuild read the same names
+        assert m <= (n_families or n_files - m)
+        lines = lines[:-m] + [ln.split("\t")[0] + "\t" + lines[j].split("\t")[1] for j, ln in enumerate(lines[-m:])]
+        open(os.path.join(d, "in.tsv"), "w").writelines(lines)
     open(os.path.join(d, "old.tsv"), "w").writelines(lines[:-m])
     open(os.path.join(d, "new.tsv"), "w").writelines(lines[-m:])
     res = {"base": hibf_run(layout, "old.tsv", "old.hibf")}
+    cmd = [exe, "-i", os.path.join(d, "new.tsv"), "--hibf", "--update", os.path.join(d, "old.hibf"), "-o", os.path.join(d, "upd.hibf"), "-t", str(threads),
+           "--verbose"] + (["--extend"] if extend else [])
+    lap = r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)"
+    if extend:  # one warm-up, then the runs: the update's own seconds and the process's wall time
+        emplace, total = [], []
+        for r in range(int(opts["--runs"]) + 1):
+            t0 = time.time()
+            p = subprocess.run(cmd, capture_output=True, text=True)
+            mm = re.search(lap, p.stderr)
+            if p.returncode != 0 or not mm:
+                break
+            if r:
+                emplace.append(float(mm.group(6))), total.append(round(time.time() - t0, 3))
+        res["extend_emplace_s"], res["extend_total_s"] = spread(emplace), spread(total)
     t0 = time.time()
-    p = subprocess.run([exe, "-i", os.path.join(d, "new.tsv"), "--hibf", "--update", os.path.join(d, "old.hibf"), "-o", os.path.join(d, "upd.hibf"), "-t", str(threads),
-                        "--verbose"], capture_output=True, text=True)
+    p = subprocess.run(cmd, capture_output=True, text=True)
     upd = {"rc": p.returncode, "wall_s": round(time.time() - t0, 2)}
-    mm = re.search(r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
+    mm = re.search(lap, p.stderr)
     if mm:
         for key, x in zip(("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s"), mm.groups()):
             upd[key] = float(x)
@@ -164,11 +197,17 @@ def update_run(layout, m):
     upd["result"] = mm.group(0) if mm else (p.stderr or p.stdout)[-300:]
     upd["ibf_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith("ibf\t")][:8]
     upd["warn_fill_lines"] = sum(ln.endswith("WARN fill") for ln in p.stdout.splitlines())
+    if extend:
+        upd["extended_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith("extended\t")][:8]
     if p.returncode == 0:
         upd["hibf_bytes"] = os.path.getsize(os.path.join(d, "upd.hibf"))
         upd.update(verify_run("upd.hibf"))
     res["update"] = upd
     res["rebuild"] = hibf_run(layout)
+    if extend and res["rebuild"]["rc"] == 0:
+        again = [hibf_run(layout) for _ in range(int(opts["--runs"]))]
+        res["rebuild_emplace_s"] = spread([r["emplace_s"] for r in again if "emplace_s" in r])
+        res["rebuild_total_s"] = spread([r["wall_s"] for r in again])
     if not check and res["rebuild"]["rc"] == 0:
         res["rebuild"].update(verify_run())
     return res
