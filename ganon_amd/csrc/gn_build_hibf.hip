@@ -8,9 +8,11 @@
 //                            union of the sets would: the unions are never materialised.
 //   gn_filter_bin_popcounts  set bits per technical bin of an IBF: how full each bin of an index is (towards `--update`)
 //   gn_filter_copy_ibf       an IBF into one with more bins, device to device
+//   gn_filter_copy_ibf_spans the same with runs of bins left out or moved (`--update --remove`)
 // No counterpart in the reference's own sources: `ganon build --filter-type hibf` runs `raptor build`
 // (/root/reference/src/ganon/build_update.py:411-518).  HBM-bound integer work: depth * h atomic ORs per hash, each to a row
 // of its own.
+#include "gn_bin_spans.h"
 #include "gn_build_row.h"
 #include "gn_scan.h"
 #include <hipcub/hipcub.hpp>
@@ -1149,5 +1151,177 @@ extern "C" int gn_filter_copy_ibf(gn_filter* dst, uint32_t dst_ibf, const gn_fil
                            (uint32_t)s.Ws, (uint32_t)s.W, threads / units, (uint32_t)(threads % units));
     GN_HIP(hipGetLastError());
     GN_HIP(hipDeviceSynchronize());
+    return GN_OK;
+}
+
+// ---- gn_filter_copy_ibf_spans: an IBF into another one, with bins left out -------------------------------------------------------------
+// The copy above with the columns compacted on the way (`ganon-build --hibf --update --remove`): the spans are turned into a table of
+// segments per destination word on the host (gn_bin_spans.h, where the arithmetic and its traps are described) and uploaded once.
+// A thread owns V destination words of a row (V = 2: one 16-byte store, when the destination's stride is even) and keeps them for every
+// row it walks, so that the segments of its words are read once: the first two of a word live in registers -- a word below a removed
+// run has two, most words have one -- and only a word with more reads the rest from the table per row (L2-resident: the table is a few
+// bytes per destination word).  The loads of a row are issued together, without a branch between the two words of a window.  A word is composed from all of its segments and stored once: no read-modify-write, no atomics, one
+// writer per word whatever spans end in it.  Neighbouring lanes own neighbouring words:
+//   rows of at least 256 units   blockIdx.x picks 256 units of the row, blockIdx.y the first row; the rows step by gridDim.y
+//   narrower rows                a block covers 256 / units whole rows, which lie one behind the other: the flat array the popcount
+//                                kernel reads; 256 % units threads idle (none for the power-of-two strides up to 16 words)
+// A window is at most two neighbouring source words; its second word is on the line the first one fetched or on the next, so the source is
+// read from HBM once, as by the plain copy.  Two destination words that are two whole neighbouring aligned source words -- every pair of
+// an identity span -- are one 16-byte load.
+struct GnSpanCopyParams
+{
+    uint64_t*        dst;
+    const uint64_t*  src;
+    const uint32_t*  seg_off;
+    const GnSpanSeg* segs;
+    uint64_t         S;
+    uint32_t         Ws_dst, Ws_src;
+    uint32_t         units; // of V words, in a destination row
+    uint32_t         rpb;   // whole rows a block covers; 0: wide rows
+};
+
+template <uint32_t V>
+__global__ __launch_bounds__(256) void gn_copy_ibf_spans_kernel(const GnSpanCopyParams P)
+{
+    uint32_t u;
+    uint64_t r, step;
+    if (P.rpb)
+    {
+        const uint32_t rr = threadIdx.x / P.units;
+        if (rr >= P.rpb)
+            return;
+        u    = threadIdx.x % P.units;
+        r    = (uint64_t)blockIdx.y * P.rpb + rr;
+        step = (uint64_t)gridDim.y * P.rpb;
+    }
+    else
+    {
+        u = blockIdx.x * 256u + threadIdx.x;
+        if (u >= P.units)
+            return;
+        r    = blockIdx.y;
+        step = gridDim.y;
+    }
+    const uint32_t w0 = u * V; // (w0 + V <= Ws_dst: units = Ws_dst / V, exactly)
+    uint32_t       first[V], n[V];
+    GnSpanSeg      a[V], b[V];
+#pragma unroll
+    for (uint32_t v = 0; v < V; ++v)
+    {
+        first[v] = P.seg_off[w0 + v];
+        n[v]     = P.seg_off[w0 + v + 1] - first[v];
+        a[v] = b[v] = GnSpanSeg{ 0, 0, 0, 0, 0 };
+        if (n[v] >= 1)
+            a[v] = P.segs[first[v]];
+        if (n[v] >= 2)
+            b[v] = P.segs[first[v] + 1];
+    }
+    bool pair = false; // two whole source words, 16 bytes aligned in a source of even stride
+    if (V == 2)
+        pair = n[0] == 1 && n[V - 1] == 1 && gn_span_is_move(a[0]) && gn_span_is_move(a[V - 1]) && a[V - 1].src_word == a[0].src_word + 1u &&
+               (a[0].src_word & 1u) == 0 && (P.Ws_src & 1u) == 0;
+    for (; r < P.S; r += step)
+    {
+        const uint64_t* row = P.src + r * P.Ws_src; // (64-bit: row * stride passes 2^32 words in a large IBF)
+        uint64_t        out[V];
+        if (V == 2 && pair)
+        {
+            const ulonglong2 x = *reinterpret_cast<const ulonglong2*>(row + a[0].src_word);
+            out[0] = x.x, out[V - 1] = x.y;
+        }
+        else
+        {
+            // every load of the row first, then the arithmetic: a word without a segment has a segment of 0 bits of word 0
+            uint64_t alo[V], ahi[V], blo[V], bhi[V];
+#pragma unroll
+            for (uint32_t v = 0; v < V; ++v)
+            {
+                alo[v] = row[a[v].src_word];
+                ahi[v] = row[a[v].src_word + gn_span_second(a[v])];
+            }
+#pragma unroll
+            for (uint32_t v = 0; v < V; ++v)
+            {
+                blo[v] = bhi[v] = 0;
+                if (n[v] >= 2)
+                {
+                    blo[v] = row[b[v].src_word];
+                    bhi[v] = row[b[v].src_word + gn_span_second(b[v])];
+                }
+            }
+#pragma unroll
+            for (uint32_t v = 0; v < V; ++v)
+            {
+                uint64_t x = gn_span_bits(alo[v], ahi[v], a[v]) << a[v].dst_off | gn_span_bits(blo[v], bhi[v], b[v]) << b[v].dst_off;
+                if (n[v] > 2)
+                    x |= gn_span_compose(row, P.segs + first[v] + 2, n[v] - 2);
+                out[v] = x;
+            }
+        }
+        if (V == 2)
+            *reinterpret_cast<ulonglong2*>(P.dst + r * P.Ws_dst + w0) = make_ulonglong2(out[0], out[V - 1]);
+        else
+            P.dst[r * P.Ws_dst + w0] = out[0];
+    }
+}
+
+extern "C" int gn_filter_copy_ibf_spans(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf, const gn_bin_span* spans,
+                                        uint32_t n_spans)
+{
+    if (!dst || !src || (n_spans && !spans))
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: null argument");
+    if (!dst->is_hibf || !src->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans needs two HIBF filters");
+    if (dst->device != src->device)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: the filters are on devices %d and %d", dst->device, src->device);
+    if (dst_ibf >= dst->ibfs.size() || src_ibf >= src->ibfs.size())
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: ibf %u of %zu into ibf %u of %zu", src_ibf, src->ibfs.size(), dst_ibf, dst->ibfs.size());
+    GnIbfHost&       d = dst->ibfs[dst_ibf];
+    const GnIbfHost& s = src->ibfs[src_ibf];
+    if (!d.d_rows || !s.d_rows || d.d_rows.get() == s.d_rows.get())
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: an IBF onto itself");
+    if (d.S != s.S || d.h != s.h)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: %llu rows and %u hash functions into %llu rows and %u", (unsigned long long)s.S, s.h,
+                       (unsigned long long)d.S, d.h);
+    uint32_t    at  = 0;
+    const char* why = gn_spans_check(spans, n_spans, s.B, d.B, &at);
+    if (why)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: span %u {source %u, destination %u, %u bins} of %u: %s (source %llu bins, destination %llu)", at,
+                       spans[at].src_first, spans[at].dst_first, spans[at].n_bins, n_spans, why, (unsigned long long)s.B, (unsigned long long)d.B);
+    if (d.Ws * 64 < d.B || s.W * 64 < s.B || s.Ws < s.W || d.Ws > 0xFFFFFFFFull || s.Ws > 0xFFFFFFFFull)
+        return gn_fail(GN_EINVAL, "gn_filter_copy_ibf_spans: rows of %llu and %llu words for %llu and %llu bins", (unsigned long long)s.Ws, (unsigned long long)d.Ws,
+                       (unsigned long long)s.B, (unsigned long long)d.B);
+    if (d.S == 0)
+        return GN_OK;
+    std::vector<uint32_t>  seg_off;
+    std::vector<GnSpanSeg> segs;
+    gn_spans_table(spans, n_spans, d.Ws, seg_off, segs);
+    GN_HIP(hipSetDevice(dst->device));
+    GnDev<uint32_t>  d_off;
+    GnDev<GnSpanSeg> d_segs;
+    GN_HIP(d_off.upload(seg_off.data(), seg_off.size()));
+    GN_HIP(d_segs.upload(segs.data(), segs.size()));
+    GnSpanCopyParams P{};
+    P.dst = d.d_rows.get(), P.src = s.d_rows.get(), P.seg_off = d_off.get(), P.segs = d_segs.get();
+    P.S = d.S, P.Ws_dst = (uint32_t)d.Ws, P.Ws_src = (uint32_t)s.Ws;
+    const bool two = d.Ws % 2 == 0;
+    P.units        = (uint32_t)(d.Ws / (two ? 2 : 1));
+    P.rpb          = P.units < 256 ? 256 / P.units : 0;
+    const uint64_t budget = (uint64_t)std::max(dst->n_cu, 1) * 16; // blocks, as the plain copy launches
+    uint64_t       gx = 1, gy;
+    if (P.rpb)
+        gy = std::min<uint64_t>((d.S + P.rpb - 1) / P.rpb, budget);
+    else
+    {
+        gx = ((uint64_t)P.units + 255) / 256;
+        gy = std::min<uint64_t>(d.S, std::max<uint64_t>(1, budget / gx));
+    }
+    gy = std::min<uint64_t>(gy, 65535);
+    if (two)
+        hipLaunchKernelGGL(gn_copy_ibf_spans_kernel<2>, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr, P);
+    else
+        hipLaunchKernelGGL(gn_copy_ibf_spans_kernel<1>, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr, P);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipDeviceSynchronize()); // (the table is freed behind it)
     return GN_OK;
 }

@@ -99,6 +99,8 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--layout has to be rule, sketch or similarity");
     if (c.extend && !c.update_given)
         return say("--extend needs --update (it adds the inputs' sequences to targets of the index --update names)");
+    if (c.remove_given && !c.update_given)
+        return say("--remove needs --update (it takes targets out of the index --update names)");
     if (c.update_given)
     {
         if (!c.hibf)
@@ -117,6 +119,8 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
             return say("--update cannot be used with --mode");
         if (c.update.empty() || !fs::exists(c.update))
             return say("--update not found: " + c.update);
+        if (c.remove_given && (c.remove.empty() || !fs::is_regular_file(c.remove)))
+            return say("--remove not found: " + c.remove);
         {
             std::error_code ec;
             if (fs::exists(c.output_file) && fs::equivalent(c.update, c.output_file, ec))
@@ -147,11 +151,12 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         if (!(c.max_fp > 0 && c.max_fp < 1))
             return say("--max-fp has to be above 0 and below 1 with --hibf");
     }
-    if (c.input_file.empty())
+    const bool remove_only = c.remove_given && c.input_file.empty(); // (the one case without inputs: targets leave, none comes)
+    if (c.input_file.empty() && !remove_only)
         return say("--input-file is mandatory");
-    if (!fs::exists(c.input_file))
+    if (!remove_only && !fs::exists(c.input_file))
         return say("--input-file not found: " + c.input_file);
-    if (fs::file_size(c.input_file) == 0)
+    if (!remove_only && fs::file_size(c.input_file) == 0)
         return say("--input-file is empty: " + c.input_file);
     if (c.output_file.empty() && !c.verify_given)
         return say("--output-file is mandatory");
@@ -199,6 +204,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--update            " << c.update << '\n';
     if (c.extend)
         std::cerr << "--extend            " << c.extend << '\n';
+    if (c.remove_given)
+        std::cerr << "--remove            " << c.remove << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -246,6 +253,15 @@ const char* kHelp =
     "                               how full the bits show them; the merged bins above take all of them.  A run is never moved or\n"
     "                               widened: when a bin is predicted over its bound nothing is written and the targets are named\n"
     "                               (leave them out or rebuild).  Unknown names are added as new targets, as without the flag\n"
+    "      --remove arg             [--update] take targets out of the index: `arg` is a file of target names, one per line, as in\n"
+    "                               column 2 of an input file (empty lines and repeats are ignored).  The removed user bins'\n"
+    "                               technical bins are dropped, the bins behind them move left, user bins and IBFs are renumbered,\n"
+    "                               and an IBF left without a bin goes together with the merged bin that led to it; the file written\n"
+    "                               is an ordinary index.  --input-file may then be left out.  A name in both --remove and\n"
+    "                               --input-file is REPLACED: its old user bin goes, the input's sequences enter as a new one.  A\n"
+    "                               name the index does not hold, or the removal of every target, ends the command with nothing\n"
+    "                               written.  Merged bins above a removed target keep its hashes (`stale` lines of the report say\n"
+    "                               how many, estimated); rows never shrink\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -295,7 +311,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update", "--remove" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -354,6 +370,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.verify_index = vals["--verify-index"], c.verify_given = true;
         if (vals.count("--update"))
             c.update = vals["--update"], c.update_given = true;
+        if (vals.count("--remove"))
+            c.remove = vals["--remove"], c.remove_given = true;
         if (vals.count("--max-fp"))
             c.max_fp = d("--max-fp"), c.max_fp_given = true;
         if (vals.count("--filter-size"))
@@ -517,11 +535,15 @@ bool run(Config c)
         return fail("--device " + std::to_string(c.device) + " does not exist (" + std::to_string(n_dev) + " visible)");
 
     Totals              totals;
-    std::vector<Target> targets = read_input_file(c, totals);
-    if (targets.empty())
+    const bool          remove_only = c.remove_given && c.input_file.empty();
+    std::vector<Target> targets;
+    if (!remove_only)
+        targets = read_input_file(c, totals);
+    if (targets.empty() && !remove_only)
         return fail("No valid input files");
 
     counting.start();
+    if (!targets.empty())
     {
         // every hasher page-locks 64 MiB and owns a device stream with GBs of hash and sort buffers: --threads (the wrapper
         // forwards 64 or 128 gladly) buys parser threads only up to what eight such streams keep busy

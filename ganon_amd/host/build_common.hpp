@@ -44,6 +44,8 @@ struct Config // Config.hpp:10-27
     std::string update;          // (--hibf only: add the inputs' targets to this index and write the result to --output-file)
     bool        update_given = false, max_fp_given = false, mode_given = false;
     bool        extend = false;  // (--update only: a target the index holds gains the inputs' sequences)
+    std::string remove;          // (--update only: a file of target names, one per line, that leave the index)
+    bool        remove_given = false;
     bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
 };
 

@@ -2,12 +2,17 @@
 // Adds the inputs' targets to an index without its genomes: the file into filter A, how full every bin is off A's bits
 // (gn_filter_bin_popcounts), the placement (hibf_update.hpp), filter B with the new bins, every IBF moved over (gn_filter_copy_ibf),
 // the new sets along their paths, B written with the file's own header fields and strings and the new names behind them.
+// With `--remove NAMES` targets leave on the way: the tables after the removal (hibf_remove.hpp) are what the placement works on, B is
+// created without the dropped bins and IBFs, and the move compacts the columns (gn_filter_copy_ibf_spans) -- every row is read and
+// written once either way.  A name in both NAMES and the inputs is replaced: the old user bin goes, the inputs enter as a new one.
 #include "build_common.hpp"
 #include "hibf_pool.hpp"
+#include "hibf_remove.hpp"
 #include "hibf_update.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <fstream>
 #include <iomanip>
 #include <memory>
 #include <numeric>
@@ -32,20 +37,58 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             return fail(gn_last_error());
         fresh_target.push_back(t);
     }
-    if (fresh_target.empty())
+    if (fresh_target.empty() && !(c.remove_given && c.input_file.empty())) // (without inputs only where targets leave and none comes)
         return fail("No valid sequences to build");
     const double hash_s = counting.seconds() + since(t0);
+    std::vector<uint64_t>    remove_user;  // --remove: the user bins that leave, ascending, and the name each of them carries
+    std::vector<std::string> remove_name;
     try
     {
         {
             gnhost::FilterMeta names;
             gnhost::read_hibf_meta(c.update, names);
+            std::set<std::string> leaving;
+            if (c.remove_given)
+            {
+                std::vector<std::string> listed;
+                std::ifstream            in(c.remove);
+                for (std::string line; std::getline(in, line);)
+                {
+                    if (!line.empty() && line.back() == '\r')
+                        line.pop_back();
+                    if (!line.empty() && leaving.insert(name_as_read(line)).second)
+                        listed.push_back(name_as_read(line));
+                }
+                const gnhibf::RemoveNames found = gnhibf::resolve_remove(names.targets, names.target_bins, names.bin_count, listed);
+                if (!found.unknown.empty())
+                {
+                    std::string m = "--remove: " + std::to_string(found.unknown.size()) + " name(s) are not in the index; nothing written:";
+                    for (const std::string& n : found.unknown)
+                        m += "\n  " + n;
+                    return fail(m);
+                }
+                if (!found.shared.empty())
+                {
+                    std::string m = "--remove: a user bin that leaves also names a target that stays; nothing written:";
+                    for (const auto& [u, n] : found.shared)
+                        m += "\n  user bin " + std::to_string(u) + " also names " + n;
+                    return fail(m);
+                }
+                remove_user = found.user_bins;
+                for (const uint64_t u : remove_user)
+                    for (size_t i = 0; i < names.targets.size() && i < names.target_bins.size(); ++i)
+                        if (std::find(names.target_bins[i].begin(), names.target_bins[i].end(), u) != names.target_bins[i].end())
+                        {
+                            remove_name.push_back(names.targets[i]);
+                            break;
+                        }
+            }
             const std::set<std::string> have(names.targets.begin(), names.targets.end());
             std::vector<uint32_t>       added;
             for (uint32_t t : fresh_target)
             {
                 const std::string name = name_as_read(targets[t].name);
-                if (!have.count(name))
+                if (!have.count(name) || leaving.count(name)) // (a name that leaves and comes is replaced: a new user bin)
                 {
                     added.push_back(t);
                     continue;
@@ -96,14 +139,35 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         const double count_s = since(t0);
 
         t0 = std::chrono::steady_clock::now();
+        // --extend probes A, along the paths of the file's own tables
+        gnhibf::Paths a_paths;
+        if (!ext_target.empty())
+            a_paths = gnhibf::derive_paths(bins, meta.next_ibf_id, meta.bin_to_user, n_old);
+        // --remove: the tables the rest works on are those after the removal, with A's bit counts carried to the new places
+        const bool                  removing = c.remove_given;
+        const std::vector<uint64_t> bins_a   = bins; // per IBF of the file
+        std::vector<std::vector<int64_t>> loaded_next_ibf_id, loaded_bin_to_user; // the file's tables (--remove: for the report)
+        gnhibf::RemovePlan          gone;
+        if (removing)
+        {
+            gone = gnhibf::plan_remove(bins, meta.next_ibf_id, meta.bin_to_user, n_old, remove_user, rows, h, &pop);
+            std::vector<uint64_t> kept_rows;
+            for (const uint32_t i : gone.old_ibf)
+                kept_rows.push_back(rows[i]);
+            rows.swap(kept_rows);
+            bins = gone.bins, pop = gone.popcounts;
+            loaded_next_ibf_id.swap(meta.next_ibf_id), loaded_bin_to_user.swap(meta.bin_to_user);
+            meta.next_ibf_id = gone.next_ibf_id, meta.bin_to_user = gone.bin_to_user;
+        }
+        const uint64_t n_ibf_b = bins.size(), n_base = removing ? gone.n_user_bins : n_old; // what B starts from
         // --extend: what every extension set's path lacks (A's bits), the quotas of its run and the fills the new user bins start from
-        gnhibf::Paths      old_paths;
-        gnhibf::ExtendPlan ex;
-        double             probe_s = 0;
+        gnhibf::Paths         old_paths;            // of the tables B starts from
+        std::vector<uint64_t> ext_user_b = ext_user; // the extended user bins as B numbers them
+        gnhibf::ExtendPlan    ex;
+        double                probe_s = 0;
         if (!ext_target.empty())
         {
-            old_paths = gnhibf::derive_paths(bins, meta.next_ibf_id, meta.bin_to_user, n_old);
-            const uint32_t                   d0 = old_paths.depth;
+            const uint32_t                   d0 = a_paths.depth;
             std::vector<gnhibf::ExtendInput> in(ext_target.size());
             for (size_t j = 0; j < in.size(); ++j)
             {
@@ -113,7 +177,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
                 in[j].lost_at.assign(d0, 0);
             }
             gnhibf::for_each_pooled(
-                in.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &old_paths.entries[(size_t)ext_user[j] * d0]; }, d0,
+                in.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &a_paths.entries[(size_t)ext_user[j] * d0]; }, d0,
                 [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>& ids) {
                     std::vector<uint64_t> found(n), first(n), lost(n * d0);
                     if (gn_filter_probe_path(sink->filter(), hashes, off, (uint32_t)n, p, d0, found.data(), lost.data(), first.data()) != GN_OK)
@@ -122,7 +186,20 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
                         in[ids[k]].lost_at.assign(lost.begin() + k * d0, lost.begin() + (k + 1) * d0);
                 });
             probe_s = since(t0);
-            ex      = gnhibf::plan_extend(old_paths, bins, rows, h, fpr, pop, in);
+            if (!removing)
+                old_paths = a_paths;
+            else
+            {
+                // a removal changes no bit of a surviving bin and no surviving path but for its numbers: what A lacks, B lacks.  The tree
+                // may have lost levels; a surviving path is as long as it was, so what is cut off lost_at are unused entries
+                old_paths = gnhibf::derive_paths(bins, meta.next_ibf_id, meta.bin_to_user, n_base);
+                for (size_t j = 0; j < in.size(); ++j)
+                {
+                    in[j].user_bin = ext_user_b[j] = (uint64_t)gone.user_map[ext_user[j]];
+                    in[j].lost_at.resize(old_paths.depth);
+                }
+            }
+            ex = gnhibf::plan_extend(old_paths, bins, rows, h, fpr, pop, in);
             if (!ex.over.empty())
             {
                 std::ostringstream m;
@@ -135,19 +212,20 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             }
         }
         const gnhibf::UpdatePlan plan =
-            gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_old, h, fpr, pop, fresh_counts, ext_target.empty() ? nullptr : &ex.fills);
+            gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_base, h, fpr, pop, fresh_counts, ext_target.empty() ? nullptr : &ex.fills);
         const uint32_t depth  = plan.paths.depth;
         const double   plan_s = since(t0) - probe_s;
 
         // filter B: the same rows, the new bins.  A and B are on the device together until every IBF is moved
         t0 = std::chrono::steady_clock::now();
-        std::vector<HibfShape> ibfs(n_ibf);
+        std::vector<HibfShape> ibfs(n_ibf_b);
         uint64_t               a_bytes = 0, b_bytes = 0;
         for (uint64_t i = 0; i < n_ibf; ++i)
+            a_bytes += meta.shapes[i].bin_size * gn_hibf_row_stride_words((bins_a[i] + 63) >> 6) * 8;
+        for (uint64_t i = 0; i < n_ibf_b; ++i)
         {
             ibfs[i].bins = plan.bins[i], ibfs[i].rows = rows[i];
             ibfs[i].next_ibf_id = plan.next_ibf_id[i], ibfs[i].bin_to_user = plan.bin_to_user[i];
-            a_bytes += rows[i] * gn_hibf_row_stride_words((bins[i] + 63) >> 6) * 8;
             b_bytes += rows[i] * gn_hibf_row_stride_words((plan.bins[i] + 63) >> 6) * 8;
         }
         {
@@ -167,8 +245,9 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         gnhost::OwnedFilter b_flt = descs.upload(c.device, plan.n_user_bins);
         if (!b_flt)
             throw std::runtime_error(gn_last_error());
-        for (uint64_t i = 0; i < n_ibf; ++i)
-            if (gn_filter_copy_ibf(b_flt.get(), (uint32_t)i, sink->filter(), (uint32_t)i) != GN_OK)
+        for (uint64_t i = 0; i < n_ibf_b; ++i)
+            if ((removing ? gn_filter_copy_ibf_spans(b_flt.get(), (uint32_t)i, sink->filter(), gone.old_ibf[i], gone.spans[i].data(), (uint32_t)gone.spans[i].size())
+                          : gn_filter_copy_ibf(b_flt.get(), (uint32_t)i, sink->filter(), (uint32_t)i)) != GN_OK)
                 throw std::runtime_error(gn_last_error());
         sink.reset(); // (frees A)
         const double copy_s = since(t0);
@@ -179,7 +258,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         // writes them -- one extension per user bin, and the new targets are inserted afterwards)
         t0 = std::chrono::steady_clock::now();
         gnhibf::for_each_pooled(
-            ext_target.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &old_paths.entries[(size_t)ext_user[j] * depth]; }, depth,
+            ext_target.size(), [&](size_t j) { return hash_set(targets[ext_target[j]]); }, [&](size_t j) { return &old_paths.entries[(size_t)ext_user_b[j] * depth]; }, depth,
             [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>& ids) {
                 std::vector<uint64_t> deal_off{ 0 }, deal;
                 for (size_t k = 0; k < n; ++k)
@@ -202,17 +281,19 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
 
         // B's bit counts, for the IBFs the report speaks of: those that gained bins or lie on a new path
         t0 = std::chrono::steady_clock::now();
-        std::vector<bool> shown(n_ibf, false);
-        for (uint64_t i = 0; i < n_ibf; ++i)
-            shown[i] = plan.bins[i] != bins[i];
+        std::vector<bool> shown(n_ibf_b, false);
+        for (uint64_t i = 0; i < n_ibf_b; ++i)
+            shown[i] = plan.bins[i] != bins[i] || (removing && bins[i] != bins_a[gone.old_ibf[i]]);
+        for (const gnhibf::RemoveStale& st : gone.stale)
+            shown[st.ibf] = true;
         for (const gn_path_entry& e : plan.paths.entries)
             if (e.n_bins)
                 shown[e.ibf] = true;
-        for (const uint64_t u : ext_user)
+        for (const uint64_t u : ext_user_b)
             for (uint32_t d = 0; d < depth && old_paths.entries[(size_t)u * depth + d].n_bins; ++d)
                 shown[old_paths.entries[(size_t)u * depth + d].ibf] = true;
-        std::vector<std::vector<uint64_t>> pop_b(n_ibf);
-        for (uint64_t i = 0; i < n_ibf; ++i)
+        std::vector<std::vector<uint64_t>> pop_b(n_ibf_b);
+        for (uint64_t i = 0; i < n_ibf_b; ++i)
             if (shown[i])
             {
                 pop_b[i].assign(plan.bins[i], 0);
@@ -225,6 +306,18 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         t0 = std::chrono::steady_clock::now();
         std::vector<std::vector<std::string>> bin_path   = meta.raw_bin_path;
         std::vector<std::string>              user_files = meta.raw_user_bin_filenames;
+        if (removing) // the removed user bins' entries go; the others stay verbatim and in order
+        {
+            size_t kept = 0;
+            for (uint64_t u = 0; u < n_old; ++u)
+                if (gone.user_map[u] >= 0)
+                {
+                    if (kept != u) // (a self-move would empty the entry)
+                        bin_path[kept] = std::move(bin_path[u]), user_files[kept] = std::move(user_files[u]);
+                    ++kept;
+                }
+            bin_path.resize(kept), user_files.resize(kept);
+        }
         const std::string dir = output_folder(c);
         for (uint32_t t : fresh_target)
         {
@@ -242,7 +335,10 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         // the report
         const double bound_fill = std::pow(fpr, 1.0 / h);
         std::cout << "index\t" << c.update << "\t->\t" << c.output_file << "\tk=" << unsigned(c.kmer_size) << " w=" << c.window_size << " h=" << unsigned(h)
-                  << " ibfs=" << n_ibf << " levels=" << depth << " user_bins=" << n_old << "->" << plan.n_user_bins << " fpr=" << fpr << "\n";
+                  << " ibfs=" << n_ibf;
+        if (removing)
+            std::cout << "->" << n_ibf_b;
+        std::cout << " levels=" << depth << " user_bins=" << n_old << "->" << plan.n_user_bins << " fpr=" << fpr << "\n";
         std::cout << "#target\tuser_bin\tdistinct_hashes\tleaf_ibf\tfirst_bin\tbins\tdepth\tpath\n";
         uint64_t bins_added = 0;
         for (size_t j = 0; j < fresh_target.size(); ++j)
@@ -251,25 +347,51 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             uint32_t             used = 0;
             while (used < depth && p[used].n_bins)
                 ++used;
-            std::cout << "target\t" << targets[fresh_target[j]].name << "\t" << n_old + j << "\t" << fresh_counts[j] << "\t" << p[0].ibf << "\t" << p[0].first_bin << "\t"
+            std::cout << "target\t" << targets[fresh_target[j]].name << "\t" << n_base + j << "\t" << fresh_counts[j] << "\t" << p[0].ibf << "\t" << p[0].first_bin << "\t"
                       << p[0].n_bins << "\t" << used << "\t";
             for (uint32_t d = used; d-- > 0;)
                 std::cout << p[d].ibf << ":" << p[d].first_bin << (d ? " " : "");
             std::cout << "\n";
             bins_added += p[0].n_bins;
         }
+        if (removing)
+        {
+            // (old numbers: what left is named as the index given knows it; `stale` speaks of the file written)
+            auto estimate = [](uint64_t hashes, bool full) { return full ? std::string("full") : std::to_string(hashes); };
+            const gnhibf::Paths was = gnhibf::derive_paths(bins_a, loaded_next_ibf_id, loaded_bin_to_user, n_old);
+            std::cout << "#removed\ttarget\tuser_bin\tleaf_ibf\tfirst_bin\tbins\tbits\testimated_hashes\tpath\n";
+            for (size_t j = 0; j < gone.removed.size(); ++j)
+            {
+                const gnhibf::RemovedRun& r = gone.removed[j];
+                const gn_path_entry*      p = &was.entries[(size_t)r.user_bin * was.depth];
+                uint32_t                  used = 0;
+                while (used < was.depth && p[used].n_bins)
+                    ++used;
+                std::cout << "removed\t" << (j < remove_name.size() ? remove_name[j] : std::string("?")) << "\t" << r.user_bin << "\t" << r.ibf << "\t" << r.first_bin << "\t" << r.n_bins
+                          << "\t" << r.bits << "\t" << estimate(r.hashes, r.full) << "\t";
+                for (uint32_t d = used; d-- > 0;)
+                    std::cout << p[d].ibf << ":" << p[d].first_bin << (d ? " " : "");
+                std::cout << "\n";
+            }
+            std::cout << "#dropped\tibf\tparent_ibf\tparent_bin\n";
+            for (const gnhibf::RemoveDropped& d : gone.dropped)
+                std::cout << "dropped\t" << d.ibf << "\t" << d.parent_ibf << "\t" << d.parent_bin << "\n";
+            std::cout << "#stale\tibf\tbin\tbits\testimated_stale_hashes\n";
+            for (const gnhibf::RemoveStale& st : gone.stale)
+                std::cout << "stale\t" << st.ibf << "\t" << st.bin << "\t" << pop_b[st.ibf][st.bin] << "\t" << estimate(st.hashes, st.full) << "\n";
+        }
         if (c.extend)
         {
             std::cout << "#extended\ttarget\tuser_bin\thashes\talready_present\tinserted\tleaf_ibf\tfirst_bin\tbins\tpath\n";
             for (size_t j = 0; j < ext_target.size(); ++j)
             {
-                const gn_path_entry* p        = &old_paths.entries[(size_t)ext_user[j] * depth];
+                const gn_path_entry* p        = &old_paths.entries[(size_t)ext_user_b[j] * depth];
                 const uint64_t       n        = targets[ext_target[j]].hashes.size();
                 const uint64_t       inserted = std::accumulate(ex.quotas[j].begin(), ex.quotas[j].end(), uint64_t(0));
                 uint32_t             used     = 0;
                 while (used < depth && p[used].n_bins)
                     ++used;
-                std::cout << "extended\t" << targets[ext_target[j]].name << "\t" << ext_user[j] << "\t" << n << "\t" << n - inserted << "\t" << inserted << "\t" << p[0].ibf
+                std::cout << "extended\t" << targets[ext_target[j]].name << "\t" << ext_user_b[j] << "\t" << n << "\t" << n - inserted << "\t" << inserted << "\t" << p[0].ibf
                           << "\t" << p[0].first_bin << "\t" << p[0].n_bins << "\t";
                 for (uint32_t d = used; d-- > 0;)
                     std::cout << p[d].ibf << ":" << p[d].first_bin << (d ? " " : "");
@@ -281,9 +403,9 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
                           << pop_b[r.ibf][r.bin] << "\n";
         }
         std::cout << "#ibf\trows\tbins_before\tbins_after\tmax_fill_before\tmax_fill_after\n" << std::fixed << std::setprecision(6);
-        for (uint64_t i = 0; i < n_ibf; ++i)
+        for (uint64_t i = 0; i < n_ibf_b; ++i)
             if (shown[i])
-                std::cout << "ibf\t" << i << "\t" << rows[i] << "\t" << bins[i] << "\t" << plan.bins[i] << "\t"
+                std::cout << "ibf\t" << i << "\t" << rows[i] << "\t" << (removing ? bins_a[gone.old_ibf[i]] : bins[i]) << "\t" << plan.bins[i] << "\t"
                           << *std::max_element(pop[i].begin(), pop[i].end()) / (double)rows[i] << "\t"
                           << *std::max_element(pop_b[i].begin(), pop_b[i].end()) / (double)rows[i] << "\n";
         std::cout << "#merged\tibf\tbin\tbits_before\tbits_predicted\tbits_after\n";
@@ -309,6 +431,8 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         }
         std::error_code ec;
         std::cout << "result\tok\t";
+        if (removing)
+            std::cout << gone.removed.size() << " user bin(s) removed, " << gone.dropped.size() << " IBF(s) dropped, ";
         if (c.extend)
             std::cout << ext_target.size() << " user bin(s) extended, ";
         std::cout << fresh_target.size() << " user bin(s) added, " << bins_added << " bin(s) added, " << fs::file_size(c.update, ec) << " -> "

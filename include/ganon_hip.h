@@ -482,6 +482,24 @@ int gn_filter_copy_ibf(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, u
 int gn_filter_extend_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
                           uint32_t depth, const uint64_t* deal_off, const uint64_t* deal);
 
+/* `ganon-build --hibf --update --remove`: the move of an IBF into another one that leaves bins out (no counterpart in the reference).
+ * gn_filter_copy_ibf_spans: for every row, bit dst_first + j of IBF dst_ibf of `dst` is bit src_first + j of IBF src_ibf of `src`, for
+ *   every j < n_bins of every span; every other bit of the destination's row is zero, up to its padded row stride
+ *   (gn_hibf_row_stride_words): the padding bins of the last word and whatever the destination held before included.  The spans are
+ *   ascending and disjoint in the destination; their source positions are free (a permutation of runs is legal, and so is one source
+ *   bin in several spans).  The destination may have fewer or more bins than the source.  The one span {0, 0, bins of the source}
+ *   gives what gn_filter_copy_ibf gives.  n_spans == 0 zeroes the destination (`spans` may then be NULL).
+ *   GN_EINVAL, with everything checked before anything is launched (a refused call writes nothing): a null argument; a filter that is
+ *   not an HIBF, or two filters on different devices; an IBF out of range, or an IBF onto itself; differing rows or hash functions; a
+ *   span of 0 bins; a span beyond the source's or the destination's bins; destination spans that overlap or do not ascend.
+ *   Returns when the copy is complete. */
+typedef struct
+{
+    uint32_t src_first, dst_first, n_bins, reserved;
+} gn_bin_span;
+int gn_filter_copy_ibf_spans(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf, const gn_bin_span* spans,
+                             uint32_t n_spans);
+
 /* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.

@@ -22,6 +22,9 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
                   and total_s of both as min / median / max.  The files of the extended targets, old and new, are 30 % shorter than the
                   others, so that their bins have room (an index gives a bin that sets its IBF's rows none: the plan refuses,
                   which is reported as such)
+  --remove N      [--update M] the update also takes the first N targets of the index out (`--remove`): its laps beside copy_s of the
+                  same update without --remove (the plain move against the compacting one), the file checked over the files that are
+                  left, beside a rebuild from those.  Not with --extend
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
@@ -37,7 +40,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -174,6 +177,7 @@ def update_run(layout, m):
     res = {"base": hibf_run(layout, "old.tsv", "old.hibf")}
     cmd = [exe, "-i", os.path.join(d, "new.tsv"), "--hibf", "--update", os.path.join(d, "old.hibf"), "-o", os.path.join(d, "upd.hibf"), "-t", str(threads),
            "--verbose"] + (["--extend"] if extend else [])
+    n_remove = int(opts["--remove"] or 0)
     lap = r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)"
     if extend:  # one warm-up, then the runs: the update's own seconds and the process's wall time
         emplace, total = [], []
@@ -186,9 +190,20 @@ def update_run(layout, m):
             if r:
                 emplace.append(float(mm.group(6))), total.append(round(time.time() - t0, 3))
         res["extend_emplace_s"], res["extend_total_s"] = spread(emplace), spread(total)
+    plain_copy_s = None
+    if n_remove:  # the same update without --remove first: its copy lap is the plain move of every IBF
+        assert not extend and n_remove < n_files - m
+        mm = re.search(lap, subprocess.run(cmd, capture_output=True, text=True).stderr)
+        plain_copy_s = float(mm.group(5)) if mm else None
+        open(os.path.join(d, "remove.txt"), "w").writelines(ln.rstrip("\n").split("\t")[1] + "\n" for ln in lines[:n_remove])
+        open(os.path.join(d, "in.tsv"), "w").writelines(lines[n_remove:])  # what the check and the rebuild read
+        cmd += ["--remove", os.path.join(d, "remove.txt")]
     t0 = time.time()
     p = subprocess.run(cmd, capture_output=True, text=True)
     upd = {"rc": p.returncode, "wall_s": round(time.time() - t0, 2)}
+    if n_remove:
+        upd["removed"], upd["copy_s_without_remove"] = n_remove, plain_copy_s
+        upd["removed_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith(("removed\t", "dropped\t", "stale\t"))][:12]
     mm = re.search(lap, p.stderr)
     if mm:
         for key, x in zip(("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s"), mm.groups()):
