@@ -4,6 +4,7 @@
 
 #include <hipcub/hipcub.hpp>
 #include "gn_scan.h"
+#include "gn_screen_table.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -46,7 +47,7 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
     {
         const char* name;
         bool GnSwitches::* flag;
-    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"cand_select", &GnSwitches::cand_select},
+    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"cand_select", &GnSwitches::cand_select},
                               {"csr_identity", &GnSwitches::csr_identity},   {"uniform_select", &GnSwitches::uniform_select},
                               {"run_select", &GnSwitches::run_select},       {"max_first", &GnSwitches::max_first},
                               {"const_nb", &GnSwitches::const_nb},           {"split_kernel", &GnSwitches::split_kernel},
@@ -1251,6 +1252,14 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     p.emit_probe = gn_sw().emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
     p.early_exit = gn_sw().early_exit ? 0u : 1u; // (bench.py's every-row measurement and the parity tests of the exit)
     p.skip_ctr   = s->d_ctr + 7;
+    if (f->identity && p.early_exit && !gn_sw().row_screen && (f->geom.lw == 1 || p.W > 128)) // (the instances that screen: gn_launch_fast_one)
+    {
+        // per launch: how many hashes a read of n minimisers is screened on with two of its rows (gn_screen_table.h; all zero = the flow
+        // without a screen, which is also what "every row" needs)
+        uint8_t ds[GN_SCREEN_NMAX + 1];
+        gn_screen_table(p.rel_cutoff, f->ibf.h, (uint32_t)std::min<uint64_t>(f->ibf.W, 64u * f->geom.lw) * 64u, ds);
+        memcpy(p.screen, ds, sizeof(p.screen));
+    }
     if (lo == 0) // (a re-run after a match-buffer regrow starts the tally again)
         GN_HIP(hipMemsetAsync(s->d_ctr + 7, 0, sizeof(unsigned long long), s->st));
     p.sl_nbr = f->d_sl_nbr;

@@ -31,6 +31,7 @@ struct GnSwitches
 {
     // count + select (flat IBF)
     bool early_exit = false;      // fast kernel: fetch every row (no exact early exit)
+    bool row_screen = false;      // fast kernel: no two-row screen in front of the exit (every read takes the unscreened flow)
     bool cand_select = false;     // generic kernel: scan every target instead of the candidate-driven select
     bool csr_identity = false;    // split-bin kernel family: treat an ordered CSR map as a general one
     bool uniform_select = false;  // ... no packed select for equal bins-per-target
@@ -149,6 +150,7 @@ struct GnCountParams
     const uint32_t*           sl_nbr;          // split kernel: bins-per-target bytes in the layout of the byte counters
     uint32_t                  early_exit;      // fast kernel: stop fetching rows of reads that cannot reach the cutoff
     unsigned long long*       skip_ctr;        // row bytes not fetched thanks to early exits
+    uint32_t                  screen[32];      // fast kernel: byte n = hashes a read of n minimisers is screened on with rows 0 and 1 only (0: no screen), gn_screen_table
     unsigned long long*       grab;            // fast kernel: the cursor its waves take their later units from (zero at launch; nullptr: units i, i + waves, ...)
     // fast kernel, with a filter_matches pre-pass set on the stream: matches that the --rel-filter rule is bound to drop are
     // not written at all (see the epilogue).  0 off, 1: the read's minimum is at least its cutoff count T (this filter sees all

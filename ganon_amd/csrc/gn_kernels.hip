@@ -1042,10 +1042,23 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
 // bin >= T extract (bin, count) pairs.  Reads with more minimisers are appended to `deferred` and handled by
 // gn_ibf_count_kernel.  One wave per (read, column slice); no LDS counters, no block barriers.
 // EE = with the exact early exit (instantiated separately: its check costs registers, and the variant without it
-// must keep the occupancy it had).
+// must keep the occupancy it had).  With four hash functions the EE instances of 8-byte lanes and the WIDE one put a
+// two-row screen in front of it ("Screened flow" below: rows 0 and 1 of the first ds hashes, one survey, exact counts
+// for the few bins left; ds from the launch's table, gn_screen_table.h, which assumes rows half full and decides speed
+// only; switch row_screen).  Measured on the 8 GiB, 4096-bin benchmark filter (150 bp reads, half of them random, cutoff 0.75;
+// a temporary tally in a scratch build): 99.3 % of the reads are screened, 32.7 % of all reads are dead at the survey, 66.5 %
+// take the finish, 0.06 % are aborted.
 // WIDE = rows of more than 128 words (1 KiB) with 16-byte lanes: there the third wave a SIMD bought +0.3 % (128 GiB filter, 4 KiB rows) for
 // 64 bytes of scratch per lane, so those rows get the two-wave build with nothing spilled; narrower rows keep three waves (+4 .. 7 %).
-template <int HF, int LW, bool EE, bool WIDE = false>
+// SCRN = the instance with the screen.  It is launched only when the launch's table has an entry (gn_launch_fast_one): a launch
+// whose table is empty -- a low cutoff, row_screen ablated, h != 4 -- runs the instance without it, in which everything the screen added folds away
+// at compile time: the kernel as it was before the screen, but for the byte tally's wrapping sum (at --rel-cutoff 0.2 the screening instance on its unscreened path was 0.8 %
+// slower than that one, 2 % with the wrapper's defaults: a select in every issue, a branch in every consume).
+// EE launches only happen where "a wave is one hash group" (rows of 64 lanes and more); the screening instances take that as a
+// compile-time fact, which spares them registers.  Kernel and launcher both read it from here.
+constexpr uint32_t GN_FAST_EE_GP_LOG2 = 6;
+static_assert((1u << GN_FAST_EE_GP_LOG2) == GN_WAVE, "the EE instances of the fast kernel: one hash group a wave");
+template <int HF, int LW, bool EE, bool WIDE = false, bool SCRN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW == 1 ? GN_FAST_WPE_LW1 : (HF <= 4 && !WIDE ? GN_FAST_WPE_LW2_H4 : GN_FAST_WPE_LW2)) : 1))) void gn_ibf_count_fast_kernel(GnCountParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t gn_lds[];
@@ -1054,14 +1067,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     // counts live in 8-bit SWAR registers (4-bit first level, spilled every 15 iterations): exact up to 127, which
     // also keeps the byte-wise compare below carry-free.  Reads with more minimisers go to the generic kernel.
     constexpr uint32_t NMAX = 127;
+    // with the two-row screen: four hash functions (its register sets are those of four loads an iteration); not the three-wave build of
+    // 16-byte lanes, which would pay for it with 48 bytes of scratch a lane where it has 8
+    constexpr bool     SCR  = SCRN && EE && HF == 4 && (LW == 1 || WIDE);
+    static_assert(SCR == SCRN, "a screening instance: early exit, four hash functions, 8-byte lanes or the wide build");
 
     const int      lane  = threadIdx.x & (GN_WAVE - 1);
     const int      wave  = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave-uniform: unit, read, n, ... live in SGPRs
     const uint32_t wpr   = p.wpr;
-    const uint32_t Gp    = 1u << p.gp_log2;
-    const uint32_t H     = GN_WAVE >> p.gp_log2;
+    const uint32_t gpl   = SCR ? GN_FAST_EE_GP_LOG2 : p.gp_log2; // (a compile-time fact in the screening instances: it spares them registers)
+    const uint32_t Gp    = 1u << gpl;
+    const uint32_t H     = GN_WAVE >> gpl;
     const uint32_t gl    = lane & (Gp - 1);
-    const uint32_t hsub  = lane >> p.gp_log2;
+    const uint32_t hsub  = lane >> gpl;
     uint32_t*      rowtab = gn_lds + (size_t)wave * 128 * HFP;
     uint32_t*      mlist  = gn_lds + (size_t)(blockDim.x >> 6) * 128 * HFP + (size_t)wave * GN_FAST_LIST; // the epilogue's match list (low cutoffs)
 
@@ -1097,8 +1115,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     };
     if (dyn)
         ask(unit);
-    // hash q of a unit feeds row-table entries idx = lane and lane + 64 (idx = q*HF + i)
-    const uint32_t q0 = (uint32_t)lane / HF, q1 = ((uint32_t)lane + GN_WAVE) / HF;
+    // hash q of a unit feeds row-table entries idx = lane and lane + 64 (idx = q*HF + i).  In the screening instances the lane number
+    // goes through an empty asm where q is needed: hoisted out of the persistent loop, q0, q1 and the two hash addresses made of
+    // them hold six registers for the whole unit, which those instances do not have to spare (<4,1,true,false,true> sits at
+    // exactly 128 with nothing in scratch; tests/test_screen_table_cpu.py reads the figures from the code object, so a compiler
+    // that sees through this shows up there and not as a slower kernel)
+    // (the other instances keep the two as values of the whole kernel, as before the screen: written any other way the compiler's
+    // register allocation of <4,1,true> and <4,2,true> comes out one and two spilled registers worse)
+    const uint32_t q0_c = (uint32_t)lane / HF, q1_c = ((uint32_t)lane + GN_WAVE) / HF;
+    auto hash_of = [&](uint32_t& q0, uint32_t& q1) {
+        if constexpr (!SCR)
+        {
+            q0 = q0_c;
+            q1 = q1_c;
+            return;
+        }
+        uint32_t l = (uint32_t)lane;
+        if constexpr (SCR)
+            asm volatile("" : "+v"(l));
+        q0 = l / HF;
+        q1 = (l + GN_WAVE) / HF;
+    };
     auto load_meta = [&](uint64_t u, uint32_t& rd, uint32_t& nn, uint64_t& so) {
         rd = p.read_begin + (uint32_t)(u / wpr);
         nn = p.status[rd] == GN_READ_OK ? p.n_hashes[rd] : 0u;
@@ -1108,6 +1145,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
         h0 = h1 = 0;
         if (nn >= 1 && nn <= NMAX)
         {
+            uint32_t q0, q1;
+            hash_of(q0, q1);
             if (q0 < nn)
                 h0 = p.hashes[so + q0];
             if (q1 < nn)
@@ -1170,6 +1209,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     const bool      col_act = wi < p.W;
 
     gn_wave_lds_sync(); // previous unit's row-table reads are done
+    uint32_t q0, q1;
+    hash_of(q0, q1);
     if ((uint32_t)lane < n * HF)
         rowtab[q0 * HFP + ((uint32_t)lane - q0 * HF)] = gn_ibf_row(hA, (uint32_t)lane - q0 * HF, p.shift, p.S);
     if ((uint32_t)lane + GN_WAVE < n * HF)
@@ -1226,41 +1267,86 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             chk2 = p.early_exit >= 2 && p.early_exit != 3 ? iters - 2 : c + 2; // ... then every iteration up to chk2
         }
     }
+    // Two-row screen (SCR instances; see the screened flow below): the launch's table says on how many hashes a read of n
+    // minimisers is screened, 0 = not at all.  The table only decides speed: whatever it holds, a screen runs only with
+    // ds <= n and a bound T - (n - ds) of at least 1.
+    uint32_t ds = 0;
+    if constexpr (SCR)
+    {
+        if (p.early_exit && T >= 2)
+        {
+            ds = (p.screen[n >> 2] >> (8u * (n & 3u))) & 0xFFu;
+            if (ds > n || ds + T <= n)
+                ds = 0;
+        }
+    }
     // Row loads are issued by every lane, unconditionally (lanes without a column or past the last hash read a valid
     // word and are masked when the rows are consumed): with the loads inside an exec-masked region the compiler
     // cannot know how many are outstanding behind the set it waits for and falls back to s_waitcnt vmcnt(0) -- which
     // turned the double buffer into "issue two iterations, wait for both, consume both".
     const uint32_t wi_ld = col_act ? wi : 0u; // a word that exists in every row
+    auto load_row = [&](uint32_t row, auto& R, int i) {
+        const uint64_t* ptr = p.rows + ((uint64_t)row * p.W + wi_ld);
+        if constexpr (LW == 2)
+        {
+            typedef uint32_t gn_u32x4 __attribute__((ext_vector_type(4)));
+            const gn_u32x4* p4 = reinterpret_cast<const gn_u32x4*>(ptr);
+            const gn_u32x4  v  = *p4;
+            R.m[i][0] = v.x;
+            R.m[i][1] = v.y;
+            R.m[i][2] = v.z;
+            R.m[i][3] = v.w;
+        }
+        else
+        {
+            const uint2 v = *reinterpret_cast<const uint2*>(ptr);
+            R.m[i][0] = v.x;
+            R.m[i][1] = v.y;
+        }
+    };
+    // scr (wave-uniform; SCR instances, where a wave is one hash group): the two-row screen is running and an iteration means
+    // the hashes 2 it and 2 it + 1, rows 0 and 1 of each -- the same four loads into the same set, the same wait counts
+    bool scr = SCR && ds != 0;
     auto issue = [&](uint32_t it, GnRowRegs<HF, LW>& R) {
         uint32_t q = it * H + hsub;
         q          = q < n ? q : n - 1;
         uint32_t row[HF];
 #pragma unroll
         for (int i = 0; i < HF; ++i)
-            row[i] = rowtab[q * HFP + i];
+        {
+            uint32_t idx = q * HFP + (uint32_t)i;
+            if constexpr (SCR)
+            {
+                // (the second hash of an odd screen's last iteration is its first again: the same two lines, masked below)
+                const uint32_t qs = 2 * it + (uint32_t)(i >> 1) < ds ? 2 * it + (uint32_t)(i >> 1) : 2 * it;
+                idx               = scr ? qs * HFP + (uint32_t)(i & 1) : idx;
+            }
+            row[i] = rowtab[idx];
+        }
 #pragma unroll
         for (int i = 0; i < HF; ++i)
-        {
-            const uint64_t* ptr = p.rows + ((uint64_t)row[i] * p.W + wi_ld);
-            if constexpr (LW == 2)
-            {
-                typedef uint32_t gn_u32x4 __attribute__((ext_vector_type(4)));
-                const gn_u32x4* p4 = reinterpret_cast<const gn_u32x4*>(ptr);
-                const gn_u32x4  v  = *p4;
-                R.m[i][0] = v.x;
-                R.m[i][1] = v.y;
-                R.m[i][2] = v.z;
-                R.m[i][3] = v.w;
-            }
-            else
-            {
-                const uint2 v = *reinterpret_cast<const uint2*>(ptr);
-                R.m[i][0] = v.x;
-                R.m[i][1] = v.y;
-            }
-        }
+            load_row(row[i], R, i);
     };
     auto consume = [&](const GnRowRegs<HF, LW>& R, uint32_t it) {
+        if (SCR && scr)
+        {
+            const uint32_t on = col_act ? 0xFFFFFFFFu : 0u, on2 = 2 * it + 1 < ds ? on : 0u;
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+            {
+                const uint32_t a = R.m[0][d] & R.m[1][d] & on, b = R.m[2 % HF][d] & R.m[3 % HF][d] & on2;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    nib[d][j] += ((a >> j) & 0x11111111u) + ((b >> j) & 0x11111111u);
+            }
+            acc_n += 2;
+            if (acc_n >= 14) // (two more would pass 15)
+            {
+                spill_nibbles();
+                acc_n = 0;
+            }
+            return;
+        }
         const uint32_t on = (col_act && it * H + hsub < n) ? 0xFFFFFFFFu : 0u;
 #pragma unroll
         for (int d = 0; d < ND; ++d)
@@ -1327,16 +1413,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     bool     dead    = false; // no bin can reach T any more: nothing to report
     bool     narrow  = false; // a handful of bins can: the remaining hashes only look at those (below)
     uint32_t fetched = iters; // iterations whose full rows were requested
+    // Screened flow (exact; reads the table gives a screen length ds).  The first ds hashes fetch rows 0 and 1 only -- the loop
+    // below with two hashes an iteration (issue, consume) -- and count c2 = hashes whose rows 0 and 1 both have the bin's bit.
+    // Nothing is checked on the way and no hash beyond ds is touched.
+    // One survey at ds with the bound of the exit, T - (n - ds):
+    //   no bin left        the read is dead after 2 ds row fetches;
+    //   1 .. GN_NARROW_MAX the finish below fetches, word by word, the exact count of each over all n hashes;
+    //   more               (dense rows: the screen did not thin the field) the counters are zeroed and the read runs the
+    //                      unscreened flow from hash 0, its own exit and narrow mode included -- at most once a read.
+    // Why the result is what every row would give:
+    //   (a) c2 >= c4 (the count over all h rows) bin by bin, so a bin that can still reach T by c4 passes the survey;
+    //   (b) a bin that did not pass keeps its c2 < T - (n - ds) <= T, which the epilogue's compare never reports;
+    //   (c) a bin that passed gets c4 in place of c2 before the epilogue: c2 >= T > c4 vanishes, c4 >= T reports c4;
+    //   (d) c2 <= ds <= n and c4 <= n <= 127: the byte counters and the carry-free compare hold in either flow.
+    bool     finish   = false; // the bins in sm[] get their exact counts (below)
+    bool     aborted  = false;
+    uint32_t scr_rows = 0;     // rows a screen requested
+    for (;;) // (a second pass only after an aborted screen)
     {
         // Two row-register sets (A, Bq), two iterations per trip, straight-line: while set X is consumed the other
         // set's four loads stay in flight (s_waitcnt vmcnt(HF)).  Invariant at the top of a trip and after the loop:
         // A holds iteration `it`, in flight.  The survey sits after the second half (check points are even when a
         // wave is one hash group, and only those instances check).
         GnRowRegs<HF, LW> A, Bq;
+        const uint32_t    its     = SCR && scr ? (ds + 1) >> 1 : iters;        // a screen: ds hashes, two an iteration, ...
+        const uint32_t    c1      = SCR && scr ? 0xFFFFFFFFu : chk1, c2 = chk2; // ... no check on the way
         uint32_t          it      = 0;
         bool              drained = false; // a check on an odd iteration consumed everything that was in flight
         issue(0, A);
-        for (; it + 2 < iters; it += 2)
+        for (; it + 2 < its; it += 2)
         {
             if (EE && narrow)
                 break;
@@ -1345,7 +1450,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             if constexpr (EE)
             {
                 const uint32_t done = it + 1; // odd check points: Bq (iteration `done`) is in flight
-                if (done >= chk1 && done <= chk2)
+                if (done >= c1 && done <= c2)
                 {
                     const uint32_t left = survey(done);
                     if (left == 0)
@@ -1357,7 +1462,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                     // At the very first check a stray bin that happens to be ahead is cheaper to wait out for one
                     // more iteration than to follow for the rest of the read: narrow there only when every survivor
                     // has been hit by (nearly) every hash so far, as a true match has.
-                    if (left <= GN_NARROW_MAX && (done > chk1 || (done > 2 && survivors(done - 1) == left)))
+                    if (left <= GN_NARROW_MAX && (done > c1 || (done > 2 && survivors(done - 1) == left)))
                     {
                         consume(Bq, it + 1);
                         narrow  = true;
@@ -1372,7 +1477,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             if constexpr (EE)
             {
                 const uint32_t done = it + 2;
-                if (done >= chk1 && done <= chk2)
+                if (done >= c1 && done <= c2)
                 {
                     const uint32_t left = survey(done);
                     if (left == 0)
@@ -1388,7 +1493,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
         }
         if (!dead && !drained)
         {
-            const bool two = !(EE && narrow) && it + 1 < iters; // the last one or two iterations
+            const bool two = !(EE && narrow) && it + 1 < its; // the last one or two iterations
             if (two)
                 issue(it + 1, Bq);
             consume(A, it);
@@ -1397,13 +1502,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             if (EE && narrow)
                 fetched = it + 1;
         }
+        if (!(SCR && scr))
+            break;
+        // the screen's one survey, with the bound of the exit
+        scr                 = false;
+        scr_rows            = 2 * ds;
+        const uint32_t left = survey(ds);
+        if (left == 0)
+            dead = true;
+        else if (left <= GN_NARROW_MAX)
+            finish = true;
+        if (dead || finish)
+            break;
+        aborted = true;
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+            {
+                byt[d][j][0] = 0;
+                byt[d][j][1] = 0;
+            }
     }
     // Narrow mode (exact): the bins that lost the race keep their stale counts (< t <= T, never reported); for each
     // of the few that are left, the remaining hashes fetch only the 8-byte word that holds the bin -- lane l looks at
     // (hash l / HF, row l % HF), a ballot collects the bits, the HF rows of a hash are AND-ed with shifts of the
     // ballot -- and the hits are added to the owner lane's byte counter before the normal epilogue runs.
+    // The screened flow's finish is the same pass from hash 0: the exact count replaces the bin's byte (it held c2).  A bin that
+    // every screened hash hit (c2 = ds, an error-free read of its genome) needs no second look at rows 0 and 1 of those hashes.
+    // Any other bin is first probed on the rows 2 .. of the screened hashes alone (2 ds words): a stray bin, ahead on rows 0 and
+    // 1 by chance, falls below the bound there and gets 0; what is left is read in full.
     uint32_t narrow_loads = 0;
-    if (EE && narrow)
+    if (EE && (narrow || (SCR && finish)))
     {
         constexpr uint32_t QPC = GN_WAVE / HF; // hashes per pass
         uint64_t           grp = 0;            // bit q*HF for q < QPC
@@ -1411,6 +1541,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
         for (uint32_t q = 0; q < QPC; ++q)
             grp |= 1ULL << (q * HF);
         const uint32_t l_q = (uint32_t)lane / HF, l_i = (uint32_t)lane - l_q * HF;
+        const uint32_t q_from = SCR && finish ? 0u : fetched;
         uint32_t       any_sm = 0;
 #pragma unroll
         for (int d = 0; d < ND; ++d)
@@ -1432,42 +1563,107 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                     const uint32_t word = slice * 64 * LW + (uint32_t)L * LW + (tp >> 6);
                     const uint32_t sh   = tp & 63u;
                     uint32_t       add  = 0;
-                    for (uint32_t q0 = fetched; q0 < n; q0 += QPC)
+                    uint32_t       q_known = 0;     // hashes below this one are taken to have the bit in rows 0 and 1
+                    uint32_t       q_to    = n;
+                    bool           probe   = false; // a first pass over the other rows of the screened hashes only
+                    if (SCR && finish)
                     {
-                        const uint32_t q  = q0 + l_q;
-                        bool           on = false;
-                        if (l_q < QPC && q < n)
-                        {
-                            const uint32_t row = rowtab[q * HFP + l_i];
-                            on = (p.rows[(uint64_t)row * p.W + word] >> sh) & 1ULL;
-                        }
-                        const uint64_t bm  = __ballot(on);
-                        uint64_t       all = bm;
+                        uint32_t c2 = 0;
 #pragma unroll
-                        for (int i = 1; i < HF; ++i)
-                            all &= bm >> i;
-                        add += (uint32_t)__popcll(all & grp);
+                        for (int j = 0; j < 4; ++j)
+#pragma unroll
+                            for (int pp = 0; pp < 2; ++pp)
+                                if ((bit & 3u) == (uint32_t)j && ((bit >> 2) & 1u) == (uint32_t)pp)
+                                    c2 = byt[d][j][pp];
+                        c2      = ((uint32_t)__builtin_amdgcn_readlane((int)c2, L) >> (8u * (bit >> 3))) & 0xFFu;
+                        q_known = ds;
+                        if (c2 != ds) // which hashes missed is not known: the rows 2 .. of the screened hashes say whether the bin is worth it
+                        {
+                            probe = true;
+                            q_to  = ds;
+                        }
                     }
-                    narrow_loads += (n - fetched) * HF;
+                    for (;;)
+                    {
+                        add = 0;
+                        for (uint32_t q0 = q_from; q0 < q_to; q0 += QPC)
+                        {
+                            const uint32_t q  = q0 + l_q;
+                            bool           on = false;
+                            if (l_q < QPC && q < q_to)
+                            {
+                                if (SCR && l_i < 2 && q < q_known)
+                                    on = true;
+                                else
+                                {
+                                    const uint32_t row = rowtab[q * HFP + l_i];
+                                    on = (p.rows[(uint64_t)row * p.W + word] >> sh) & 1ULL;
+                                }
+                            }
+                            const uint64_t bm  = __ballot(on);
+                            uint64_t       all = bm;
+#pragma unroll
+                            for (int i = 1; i < HF; ++i)
+                                all &= bm >> i;
+                            add += (uint32_t)__popcll(all & grp);
+                        }
+                        narrow_loads += (q_to - q_from) * HF - 2 * q_known;
+                        if (!(SCR && probe))
+                            break;
+                        // add = screened hashes with the bit in rows 2 .. >= the bin's count over them: below the survey's bound the bin
+                        // cannot reach T, whatever rows 0 and 1 say hash by hash, and vanishes; else every word of every hash is read
+                        probe = false;
+                        if (add + (n - ds) < T)
+                        {
+                            add = 0;
+                            break;
+                        }
+                        q_known = 0;
+                        q_to    = n;
+                    }
                     // into byte (bit >> 3) of byt[d][bit & 3][(bit >> 2) & 1] of lane L
-                    const uint32_t inc = add << (8u * (bit >> 3));
+                    const uint32_t inc  = add << (8u * (bit >> 3));
+                    const uint32_t keep = SCR && finish ? ~(0xFFu << (8u * (bit >> 3))) : 0xFFFFFFFFu;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
 #pragma unroll
                         for (int pp = 0; pp < 2; ++pp)
                             if ((bit & 3u) == (uint32_t)j && ((bit >> 2) & 1u) == (uint32_t)pp && lane == L)
-                                byt[d][j][pp] += inc;
+                                byt[d][j][pp] = (byt[d][j][pp] & keep) + inc;
                 }
             }
         }
     }
-    if ((dead || narrow) && slice * 64 * LW < p.W)
+    // bytes this unit did not request: its algorithmic rows less the rows and the words it asked for.  A unit may have asked for
+    // more than its algorithmic bytes -- a screen that was aborted (its rows come on top), a finish or a narrow pass over a slice
+    // of few words (128 bytes a word load against 8 * wcol a row) -- so every term is added modulo 2^64, as the wave's atomic
+    // and the host's difference are: the launch's sum is exact as long as the launch as a whole requested no more than its
+    // algorithmic bytes.
+    if (slice * 64 * LW < p.W)
     {
-        const uint32_t got  = fetched < n ? fetched : n;
         const uint32_t wcol = p.W - slice * 64 * LW < 64u * LW ? p.W - slice * 64 * LW : 64u * LW; // words of this slice
-        const uint64_t full = (uint64_t)(n - got) * HF * wcol * 8ull;
-        const uint64_t part = (uint64_t)narrow_loads * 128ull; // a narrow load fills a 128-byte L2 line (FETCH_SIZE agrees)
-        skipped_bytes += full > part ? full - part : 0ull;
+        if constexpr (!SCR)
+        {
+            // the instances without the screen: the same sum in the shape it had before the screen (which keeps their register
+            // allocation what it was), wrapping like the other
+            if (dead || narrow)
+            {
+                const uint32_t got  = fetched < n ? fetched : n;
+                const uint64_t full = (uint64_t)(n - got) * HF * wcol * 8ull;
+                const uint64_t part = (uint64_t)narrow_loads * 128ull; // a narrow load fills a 128-byte L2 line (FETCH_SIZE agrees)
+                skipped_bytes += full - part;
+            }
+        }
+        else if (dead || narrow || finish)
+        {
+            const uint32_t got  = fetched < n ? fetched : n;
+            const uint32_t rows = SCR && scr_rows && !aborted ? scr_rows : got * HF;
+            const uint64_t full = (uint64_t)(n * HF - rows) * wcol * 8ull;
+            const uint64_t part = (uint64_t)narrow_loads * 128ull; // a narrow load fills a 128-byte L2 line (FETCH_SIZE agrees)
+            skipped_bytes += full - part;
+        }
+        if (SCR && aborted)
+            skipped_bytes -= (uint64_t)scr_rows * wcol * 8ull;
     }
 
     if (more) // next unit's hashes: the loads fly while this unit's epilogue runs
@@ -1777,12 +1973,30 @@ template <int HF, int LW>
 static hipError_t gn_launch_fast_one(const GnCountParams& p, hipStream_t st)
 {
     // the early-exit variant only where a wave is one hash group (no cross-lane sums in its check)
-    const bool ee = p.early_exit && p.gp_log2 == 6;
+    const bool ee = p.early_exit && p.gp_log2 == GN_FAST_EE_GP_LOG2; // (the kernel's EE instances do not read p.gp_log2)
     const uint64_t units  = (uint64_t)(p.n_reads - p.read_begin) * p.wpr;
     uint32_t       blocks = (uint32_t)((units + 3) / 4);
     if (blocks > p.max_blocks_fast)
         blocks = p.max_blocks_fast;
     const size_t   lds    = 4 * (128 * (HF <= 4 ? 4 : 8) + GN_FAST_LIST) * 4; // per wave: the row table + the epilogue's match list
+    // the screening instance only for a launch whose table gives some read a screen (gn_capi.hip fills it for the shapes that have one)
+    bool scr = false;
+    if constexpr (HF == 4)
+        for (uint32_t w : p.screen)
+            scr = scr || w != 0;
+    scr = scr && ee;
+    if constexpr (HF == 4 && LW == 2)
+        if (scr && p.W > 128)
+        {
+            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, true, true>), dim3(blocks), dim3(256), lds, st, p);
+            return hipGetLastError();
+        }
+    if constexpr (HF == 4 && LW == 1)
+        if (scr)
+        {
+            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, false, true>), dim3(blocks), dim3(256), lds, st, p);
+            return hipGetLastError();
+        }
     if (ee && LW == 2 && p.W > 128)
         hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, LW == 2>), dim3(blocks), dim3(256), lds, st, p);
     else if (ee)

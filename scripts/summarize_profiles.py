@@ -123,6 +123,7 @@ with open(os.path.join(dst, f"pmc_fetch_{wl}.json"), "w") as f:
 if "hbm_bytes_per_launch" in out:
     bench["roofline"]["traffic"] = out["hbm_bytes_per_launch"]
     bench["roofline"]["traffic_source"] = out.get("source")
+    bench["roofline"]["traffic_from"] = out.get("file")
     with open(os.path.join(dst, f"{tag}_bench_{wl}.json"), "w") as f:
         json.dump(bench, f, indent=1)
 print(json.dumps(out, indent=1))
