@@ -1048,7 +1048,14 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
 // only; switch row_screen).  Measured on the 8 GiB, 4096-bin benchmark filter (150 bp reads, half of them random, cutoff 0.75;
 // a temporary tally in a scratch build): 99.3 % of the reads are screened, 32.7 % of all reads are dead at the survey, 66.5 %
 // take the finish, 0.06 % are aborted.
-// WIDE = rows of more than 128 words (1 KiB) with 16-byte lanes: there the third wave a SIMD bought +0.3 % (128 GiB filter, 4 KiB rows) for
+// Where a wave's time went before the two changes below (the wave's clock around the three parts, summed over a launch of 2 M reads,
+// a scratch build): 45.0 % in the screen loop, 17.2 % in the survey and the finish (16.1 % in the finishes: 8 400 cycles each), 37.7 %
+// between the finish and the next unit's first row load -- of which 10.7 % between a unit's last store and its row table, where
+// the wave waited for the next unit's metadata, 9.3 % for the hashes and the row table, 6.8 % for T, ds and the counters, 11.8 % in
+// the epilogue and its stores.
+// The finish asks for two words a lane before its ballots: a pass of 32 hashes in one round trip, so every 150 bp read finishes a
+// bin in one (7 300 cycles a finish).  The screening instances ask for the next unit's metadata with the unit's first rows in flight.
+// WIDE =rows of more than 128 words (1 KiB) with 16-byte lanes: there the third wave a SIMD bought +0.3 % (128 GiB filter, 4 KiB rows) for
 // 64 bytes of scratch per lane, so those rows get the two-wave build with nothing spilled; narrower rows keep three waves (+4 .. 7 %).
 // SCRN = the instance with the screen.  It is launched only when the launch's table has an entry (gn_launch_fast_one): a launch
 // whose table is empty -- a low cutoff, row_screen ablated, h != 4 -- runs the instance without it, in which everything the screen added folds away
@@ -1084,8 +1091,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     uint32_t*      mlist  = gn_lds + (size_t)(blockDim.x >> 6) * 128 * HFP + (size_t)wave * GN_FAST_LIST; // the epilogue's match list (low cutoffs)
 
     // Persistent waves: unit = (read, column slice), handed out in chunks (below).  The metadata of the NEXT unit
-    // (status, n, hash slot) is loaded at the top of the current one and its hashes right after the current
-    // main loop, so the chain status -> n -> slot -> hashes -> rows of dependent HBM latencies that a fresh
+    // (status, n, hash slot) is loaded at the top of the current one (the screening instances: under its first rows) and its
+    // hashes right after the current main loop, so the chain status -> n -> slot -> hashes -> rows of dependent HBM latencies that a fresh
     // wave would pay before its first row load is hidden behind the previous read's work.
     const uint64_t n_units = (uint64_t)(p.n_reads - p.read_begin) * wpr;
     const uint64_t stride  = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -1138,7 +1145,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     };
     auto load_meta = [&](uint64_t u, uint32_t& rd, uint32_t& nn, uint64_t& so) {
         rd = p.read_begin + (uint32_t)(u / wpr);
-        nn = p.status[rd] == GN_READ_OK ? p.n_hashes[rd] : 0u;
+        const uint32_t nh = p.n_hashes[rd]; // (asked for beside the status, not after it: one round trip, not two)
+        nn = p.status[rd] == GN_READ_OK ? nh : 0u;
         so = p.slot_off[rd];
     };
     auto load_hashes = [&](uint32_t nn, uint64_t so, uint64_t& h0, uint64_t& h1) {
@@ -1165,7 +1173,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     for (;;)
     {
     const uint32_t slice = (uint32_t)(unit - (uint64_t)(read - p.read_begin) * wpr);
-    // prefetch the next unit's metadata (consumed after the main loop)
+    // which unit is next; its metadata is asked for here, or under this unit's first rows (META_LATE below), and consumed after the main loop
     uint64_t unit_n = unit + 1;
     if (unit_n >= chunk_end)
     {
@@ -1187,7 +1195,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     const bool more = unit_n < n_units;
     uint32_t       read_n = 0, n_n = 0;
     uint64_t       slot_n = 0, hA_n = 0, hB_n = 0;
-    if (more)
+    // The metadata loads are scalar loads, and scalar loads come back in any order: whatever waits for the row table in LDS
+    // waits for all of them too.  Asked for here, the wave stood waiting for them at the row table's barrier with nothing of its
+    // own in flight (measured: 10.7 % of the wave time between the last store of a unit and its row table).  The screening
+    // instances ask for them once the unit's first rows are in flight, so that wait is paid under those rows.  The other instances
+    // keep the old place: the three-wave build of 16-byte lanes pays for the new one with 24 bytes of scratch a lane where it has 8.
+    constexpr bool META_LATE = SCR;
+    if (!META_LATE && more)
         load_meta(unit_n, read_n, n_n, slot_n);
 
     if (n > NMAX || n == 0)
@@ -1201,6 +1215,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
         }
         if (!more)
             break;
+        if (META_LATE)
+            load_meta(unit_n, read_n, n_n, slot_n);
         load_hashes(n_n, slot_n, hA_n, hB_n);
         unit = unit_n; read = read_n; n = n_n; slot = slot_n; hA = hA_n; hB = hB_n;
         continue;
@@ -1429,18 +1445,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     bool     finish   = false; // the bins in sm[] get their exact counts (below)
     bool     aborted  = false;
     uint32_t scr_rows = 0;     // rows a screen requested
+    // Two row-register sets (A, Bq).  A pass of the loop below starts with iteration 0 in flight in A: issued here, and again
+    // at the end of an aborted screen.  With these rows in flight the screening instances ask for the next unit's metadata.
+    GnRowRegs<HF, LW> A, Bq;
+    issue(0, A);
+    if (META_LATE && more)
+        load_meta(unit_n, read_n, n_n, slot_n);
     for (;;) // (a second pass only after an aborted screen)
     {
-        // Two row-register sets (A, Bq), two iterations per trip, straight-line: while set X is consumed the other
+        // Two iterations per trip, straight-line: while set X is consumed the other
         // set's four loads stay in flight (s_waitcnt vmcnt(HF)).  Invariant at the top of a trip and after the loop:
         // A holds iteration `it`, in flight.  The survey sits after the second half (check points are even when a
         // wave is one hash group, and only those instances check).
-        GnRowRegs<HF, LW> A, Bq;
         const uint32_t    its     = SCR && scr ? (ds + 1) >> 1 : iters;        // a screen: ds hashes, two an iteration, ...
         const uint32_t    c1      = SCR && scr ? 0xFFFFFFFFu : chk1, c2 = chk2; // ... no check on the way
         uint32_t          it      = 0;
         bool              drained = false; // a check on an odd iteration consumed everything that was in flight
-        issue(0, A);
         for (; it + 2 < its; it += 2)
         {
             if (EE && narrow)
@@ -1523,11 +1543,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                 byt[d][j][0] = 0;
                 byt[d][j][1] = 0;
             }
+        issue(0, A); // (scr is off: iteration 0 of the unscreened flow)
     }
     // Narrow mode (exact): the bins that lost the race keep their stale counts (< t <= T, never reported); for each
     // of the few that are left, the remaining hashes fetch only the 8-byte word that holds the bin -- lane l looks at
-    // (hash l / HF, row l % HF), a ballot collects the bits, the HF rows of a hash are AND-ed with shifts of the
-    // ballot -- and the hits are added to the owner lane's byte counter before the normal epilogue runs.
+    // (hash l / HF, row l % HF) and at the hash 64 / HF further on, one ballot each collects the bits, the HF rows of a hash are
+    // AND-ed with shifts of the ballot -- and the hits are added to the owner lane's byte counter before the normal epilogue runs.
     // The screened flow's finish is the same pass from hash 0: the exact count replaces the bin's byte (it held c2).  A bin that
     // every screened hash hit (c2 = ds, an error-free read of its genome) needs no second look at rows 0 and 1 of those hashes.
     // Any other bin is first probed on the rows 2 .. of the screened hashes alone (2 ds words): a stray bin, ahead on rows 0 and
@@ -1586,26 +1607,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                     for (;;)
                     {
                         add = 0;
-                        for (uint32_t q0 = q_from; q0 < q_to; q0 += QPC)
+                        for (uint32_t q0 = q_from; q0 < q_to; q0 += 2 * QPC)
                         {
-                            const uint32_t q  = q0 + l_q;
-                            bool           on = false;
-                            if (l_q < QPC && q < q_to)
-                            {
-                                if (SCR && l_i < 2 && q < q_known)
-                                    on = true;
-                                else
-                                {
-                                    const uint32_t row = rowtab[q * HFP + l_i];
-                                    on = (p.rows[(uint64_t)row * p.W + word] >> sh) & 1ULL;
-                                }
-                            }
-                            const uint64_t bm  = __ballot(on);
-                            uint64_t       all = bm;
+                            // a lane takes two hash slots, l_q and l_q + QPC, and both of its word loads are requested before either
+                            // ballot waits for one: a pass covers 2 QPC hashes in one round trip (every 150 bp read in one)
+                            const uint32_t qa = q0 + l_q, qb = qa + QPC;
+                            const bool     ina = l_q < QPC && qa < q_to, inb = l_q < QPC && qb < q_to;
+                            uint64_t       wa = ~0ULL, wb = ~0ULL; // (rows 0 and 1 of a hash below q_known: taken to have the bit)
+                            if (ina && !(SCR && l_i < 2 && qa < q_known))
+                                wa = p.rows[(uint64_t)rowtab[qa * HFP + l_i] * p.W + word];
+                            if (inb && !(SCR && l_i < 2 && qb < q_known))
+                                wb = p.rows[(uint64_t)rowtab[qb * HFP + l_i] * p.W + word];
+                            const uint64_t bma = __ballot(ina && ((wa >> sh) & 1ULL)), bmb = __ballot(inb && ((wb >> sh) & 1ULL));
+                            uint64_t       alla = bma, allb = bmb;
 #pragma unroll
                             for (int i = 1; i < HF; ++i)
-                                all &= bm >> i;
-                            add += (uint32_t)__popcll(all & grp);
+                            {
+                                alla &= bma >> i;
+                                allb &= bmb >> i;
+                            }
+                            add += (uint32_t)__popcll(alla & grp) + (uint32_t)__popcll(allb & grp);
                         }
                         narrow_loads += (q_to - q_from) * HF - 2 * q_known;
                         if (!(SCR && probe))
