@@ -9,10 +9,12 @@
 //   gn_filter_bin_popcounts  set bits per technical bin of an IBF: how full each bin of an index is (towards `--update`)
 //   gn_filter_copy_ibf       an IBF into one with more bins, device to device
 //   gn_filter_copy_ibf_spans the same with runs of bins left out or moved (`--update --remove`)
+//   gn_filter_fold_ibf       groups of bins of an IBF ORed into one bin each of another one: merged bins (`--update --fold`)
 // No counterpart in the reference's own sources: `ganon build --filter-type hibf` runs `raptor build`
 // (/root/reference/src/ganon/build_update.py:411-518).  HBM-bound integer work: depth * h atomic ORs per hash, each to a row
 // of its own.
 #include "gn_bin_spans.h"
+#include "gn_fold_table.h"
 #include "gn_build_row.h"
 #include "gn_scan.h"
 #include <hipcub/hipcub.hpp>
@@ -1321,6 +1323,184 @@ extern "C" int gn_filter_copy_ibf_spans(gn_filter* dst, uint32_t dst_ibf, const 
         hipLaunchKernelGGL(gn_copy_ibf_spans_kernel<2>, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr, P);
     else
         hipLaunchKernelGGL(gn_copy_ibf_spans_kernel<1>, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr, P);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipDeviceSynchronize()); // (the table is freed behind it)
+    return GN_OK;
+}
+
+// ---- gn_filter_fold_ibf: groups of bins of an IBF ORed into one bin each of another one ---------------------------------------------------
+// The merged bin above a group of bins (`ganon-build --hibf --update --fold`): the members are turned into a table of segments per SOURCE
+// word on the host (gn_fold_table.h, where the arithmetic and its traps are described) and uploaded once.  A block owns whole rows:
+//   rows of at most 256 words   256 / stride rows lie one behind the other in the block's threads -- the flat array the popcount and the
+//                               span-copy kernels read -- and a thread keeps its word of the row, and so its segments' place in the table,
+//                               for every row it walks; GN_FOLD_K such row sets a step, their loads issued together
+//   wider rows                  one row a step, in chunks of GN_FOLD_K * 256 words along the row, all chunks by the same block
+// Every source word below W_src is read once, by neighbouring lanes; a word without a segment's bit set costs nothing more.  A segment
+// that hits ORs its group's bit into the row's hits in LDS (an LDS OR without a return).  After ONE barrier a step the destination words
+// the groups reach -- ceil(n_groups / 64) + 1 a row at most -- are composed from the hits and written by one thread each as load-OR-store,
+// a word whose groups all missed not at all.  The hits are three buffers taken in turn, so that the step's second half also clears the
+// buffer of the step after next: what it clears was last read before this step's barrier and is next written behind the next step's.
+// No global atomic, no scratch.
+struct GnFoldParams
+{
+    uint64_t*        dst;
+    const uint64_t*  src;
+    const uint32_t*  seg_off;
+    const GnFoldSeg* segs;
+    uint64_t         S;
+    uint32_t         Ws_dst, Ws_src, W_src;
+    uint32_t         rpb;       // whole source rows 256 threads cover; 0: rows of more than 256 words
+    uint32_t         hw;        // hit words a row
+    uint32_t         dw0, ndw;  // the destination words the groups reach: the first, and how many
+    uint32_t         dst_first;
+};
+
+constexpr uint32_t GN_FOLD_K = 4;
+
+__global__ __launch_bounds__(256) void gn_fold_ibf_kernel(const GnFoldParams P)
+{
+    extern __shared__ uint32_t gn_fold_hits[]; // 3 buffers of (rows a step) * hw words
+    const uint32_t tid       = threadIdx.x;
+    const uint32_t rows_step = P.rpb ? P.rpb * GN_FOLD_K : 1u;
+    const uint32_t buf_words = rows_step * P.hw;
+    for (uint32_t i = tid; i < 2u * buf_words; i += 256u)
+        gn_fold_hits[i] = 0;
+    __syncthreads();
+    uint32_t rr = 0, u = tid, first = 0, n = 0; // rows of at most 256 words: the thread's row of the set, its word, its segments
+    if (P.rpb)
+    {
+        rr = tid / P.Ws_src, u = tid % P.Ws_src;
+        if (rr < P.rpb && u < P.W_src) // (the words from W_src to the stride are not trusted, and have no segment)
+        {
+            first = P.seg_off[u];
+            n     = P.seg_off[u + 1] - first;
+        }
+    }
+    uint32_t cur = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * rows_step; r0 < P.S; r0 += (uint64_t)gridDim.x * rows_step) // (the same trips in every thread)
+    {
+        uint32_t* hits = gn_fold_hits + cur * buf_words;
+        if (P.rpb)
+        {
+            if (n)
+            {
+                uint64_t x[GN_FOLD_K];
+#pragma unroll
+                for (uint32_t k = 0; k < GN_FOLD_K; ++k)
+                {
+                    const uint64_t row = r0 + k * P.rpb + rr; // (64-bit: row * stride passes 2^32 words in a large IBF)
+                    x[k]               = row < P.S ? P.src[row * P.Ws_src + u] : 0ull;
+                }
+                for (uint32_t s = 0; s < n; ++s)
+                {
+                    const GnFoldSeg seg = P.segs[first + s];
+#pragma unroll
+                    for (uint32_t k = 0; k < GN_FOLD_K; ++k)
+                        if (x[k] & seg.mask)
+                            atomicOr(&hits[(k * P.rpb + rr) * P.hw + (seg.group >> 5)], 1u << (seg.group & 31u));
+                }
+            }
+        }
+        else
+        {
+            const uint64_t* row = P.src + r0 * P.Ws_src;
+            for (uint32_t c = 0; c < P.W_src; c += GN_FOLD_K * 256u)
+            {
+                uint64_t x[GN_FOLD_K];
+#pragma unroll
+                for (uint32_t k = 0; k < GN_FOLD_K; ++k)
+                {
+                    const uint32_t w = c + k * 256u + tid;
+                    x[k]             = w < P.W_src ? row[w] : 0ull;
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < GN_FOLD_K; ++k)
+                {
+                    if (!x[k])
+                        continue;
+                    const uint32_t w = c + k * 256u + tid;
+                    for (uint32_t s = P.seg_off[w], end = P.seg_off[w + 1]; s < end; ++s)
+                    {
+                        const GnFoldSeg seg = P.segs[s];
+                        if (x[k] & seg.mask)
+                            atomicOr(&hits[seg.group >> 5], 1u << (seg.group & 31u));
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        uint32_t* clear = gn_fold_hits + (cur + 2u) % 3u * buf_words;
+        for (uint32_t i = tid; i < buf_words; i += 256u)
+            clear[i] = 0;
+        for (uint32_t i = tid; i < rows_step * P.ndw; i += 256u)
+        {
+            const uint32_t slot = i / P.ndw, k = i % P.ndw;
+            const uint64_t row  = r0 + slot;
+            if (row >= P.S)
+                continue;
+            const uint64_t v = gn_fold_word(hits + slot * P.hw, P.hw, P.dw0 + k, P.dst_first);
+            if (v)
+            {
+                uint64_t* at = P.dst + row * P.Ws_dst + P.dw0 + k;
+                *at |= v;
+            }
+        }
+        cur = (cur + 1u) % 3u;
+    }
+}
+
+extern "C" int gn_filter_fold_ibf(gn_filter* dst, uint32_t dst_ibf, uint32_t dst_first, uint32_t n_groups, const gn_filter* src, uint32_t src_ibf,
+                                  const gn_fold_member* members, uint32_t n_members)
+{
+    if (!dst || !src || (n_members && !members))
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: null argument");
+    if (!dst->is_hibf || !src->is_hibf)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf needs two HIBF filters");
+    if (dst->device != src->device)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: the filters are on devices %d and %d", dst->device, src->device);
+    if (dst_ibf >= dst->ibfs.size() || src_ibf >= src->ibfs.size())
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: ibf %u of %zu into ibf %u of %zu", src_ibf, src->ibfs.size(), dst_ibf, dst->ibfs.size());
+    GnIbfHost&       d = dst->ibfs[dst_ibf];
+    const GnIbfHost& s = src->ibfs[src_ibf];
+    if (!d.d_rows || !s.d_rows || d.d_rows.get() == s.d_rows.get())
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: an IBF onto itself");
+    if (d.S != s.S || d.h != s.h)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: %llu rows and %u hash functions into %llu rows and %u", (unsigned long long)s.S, s.h,
+                       (unsigned long long)d.S, d.h);
+    uint32_t    at  = 0;
+    const char* why = gn_fold_check(members, n_members, n_groups, dst_first, s.B, d.B, &at);
+    if (why && at < n_members)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: member %u {source %u, %u bins, group %u} of %u: %s (source %llu bins, %u groups)", at, members[at].src_first,
+                       members[at].n_bins, members[at].group, n_members, why, (unsigned long long)s.B, n_groups);
+    if (why)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: %u groups from bin %u on, %u members: %s (destination %llu bins)", n_groups, dst_first, n_members, why,
+                       (unsigned long long)d.B);
+    if (d.Ws * 64 < d.B || s.W * 64 < s.B || s.Ws < s.W || d.Ws > 0xFFFFFFFFull || s.Ws > 0xFFFFFFFFull)
+        return gn_fail(GN_EINVAL, "gn_filter_fold_ibf: rows of %llu and %llu words for %llu and %llu bins", (unsigned long long)s.Ws, (unsigned long long)d.Ws,
+                       (unsigned long long)s.B, (unsigned long long)d.B);
+    if (n_groups == 0 || d.S == 0)
+        return GN_OK;
+    GnFoldParams P{};
+    P.dst = d.d_rows.get(), P.src = s.d_rows.get();
+    P.S = d.S, P.Ws_dst = (uint32_t)d.Ws, P.Ws_src = (uint32_t)s.Ws, P.W_src = (uint32_t)s.W;
+    P.rpb = s.Ws <= 256 ? (uint32_t)(256 / s.Ws) : 0u;
+    P.hw  = gn_fold_hit_words(n_groups);
+    P.dw0 = dst_first >> 6, P.ndw = ((dst_first + n_groups - 1) >> 6) - P.dw0 + 1, P.dst_first = dst_first;
+    const uint64_t rows_step = P.rpb ? (uint64_t)P.rpb * GN_FOLD_K : 1;
+    const uint64_t lds       = 3 * rows_step * P.hw * sizeof(uint32_t);
+    if (lds > 65536)
+        return gn_fail(GN_ERANGE, "gn_filter_fold_ibf: %u groups in one call (%llu bytes of LDS, at most 65536)", n_groups, (unsigned long long)lds);
+    std::vector<uint32_t>  seg_off;
+    std::vector<GnFoldSeg> segs;
+    gn_fold_table(members, n_members, s.W, seg_off, segs);
+    GN_HIP(hipSetDevice(dst->device));
+    GnDev<uint32_t>  d_off;
+    GnDev<GnFoldSeg> d_segs;
+    GN_HIP(d_off.upload(seg_off.data(), seg_off.size()));
+    GN_HIP(d_segs.upload(segs.data(), segs.size()));
+    P.seg_off = d_off.get(), P.segs = d_segs.get();
+    const uint64_t blocks = std::min<uint64_t>((d.S + rows_step - 1) / rows_step, (uint64_t)std::max(dst->n_cu, 1) * 8);
+    hipLaunchKernelGGL(gn_fold_ibf_kernel, dim3((uint32_t)blocks), dim3(256), (uint32_t)lds, nullptr, P);
     GN_HIP(hipGetLastError());
     GN_HIP(hipDeviceSynchronize()); // (the table is freed behind it)
     return GN_OK;

@@ -33,7 +33,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_inflate_cuts_lines", "gn_inflate_cut_at_lines", "gn_stream_upload_text_pair_device", "gn_stream_fetch_letters",
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
-               "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_extend_path",
+               "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_fold_ibf", "gn_filter_extend_path",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
 
 
@@ -168,6 +168,7 @@ def load_library():
     L.gn_filter_bin_popcounts.argtypes = [vp, u32, vp]
     L.gn_filter_copy_ibf.argtypes = [vp, u32, vp, u32]
     L.gn_filter_copy_ibf_spans.argtypes = [vp, u32, vp, u32, vp, u32]
+    L.gn_filter_fold_ibf.argtypes = [vp, u32, u32, u32, vp, u32, vp, u32]
     L.gn_filter_extend_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp]
     L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
     L.gn_sketches_free.argtypes = [vp]
@@ -677,6 +678,16 @@ class HipFilter:
         table = np.zeros((len(spans), 4), dtype=np.uint32)  # gn_bin_span: src_first, dst_first, n_bins, reserved
         table[:, :3] = spans
         _check(load_library().gn_filter_copy_ibf_spans(self._h, dst_ibf, src._h, src_ibf, _p(table) if len(table) else None, len(table)))
+
+    def fold_ibf(self, dst_ibf: int, dst_first: int, n_groups: int, src: "HipFilter", src_ibf: int, members) -> None:
+        """gn_filter_fold_ibf: bin dst_first + g of this HIBF's IBF dst_ibf is ORed, row by row, with the OR of bins [src_first, src_first +
+        n_bins) of IBF src_ibf of the HIBF `src` over the members (src_first, n_bins, group) of group g; nothing else changes"""
+        members = np.asarray(members, dtype=np.int64).reshape(-1, 3)
+        if ((members < 0) | (members > 0xFFFFFFFF)).any():
+            raise ValueError("a member does not fit 32 bits")
+        table = np.zeros((len(members), 4), dtype=np.uint32)  # gn_fold_member: src_first, n_bins, group, reserved
+        table[:, :3] = members
+        _check(load_library().gn_filter_fold_ibf(self._h, dst_ibf, dst_first, n_groups, src._h, src_ibf, _p(table) if len(table) else None, len(table)))
 
     def probe(self, hashes: np.ndarray, bins: np.ndarray) -> Tuple[int, int, int]:
         """gn_filter_probe -> (hits summed over the bins, hashes in none of the bins, index of the first such hash or -1)"""

@@ -101,6 +101,12 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--extend needs --update (it adds the inputs' sequences to targets of the index --update names)");
     if (c.remove_given && !c.update_given)
         return say("--remove needs --update (it takes targets out of the index --update names)");
+    if (c.fold_given && c.verify_given)
+        return say("--fold cannot be used with --verify-index (fold first, then check the file written)");
+    if (c.fold_given && !c.update_given)
+        return say("--fold needs --update (it holds the IBFs of the index --update names to a number of bins)");
+    if (c.fold_given && c.fold < 2)
+        return say("--fold has to be >= 2");
     if (c.update_given)
     {
         if (!c.hibf)
@@ -151,7 +157,7 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         if (!(c.max_fp > 0 && c.max_fp < 1))
             return say("--max-fp has to be above 0 and below 1 with --hibf");
     }
-    const bool remove_only = c.remove_given && c.input_file.empty(); // (the one case without inputs: targets leave, none comes)
+    const bool remove_only = (c.remove_given || c.fold_given) && c.input_file.empty(); // (without inputs: targets leave or move, none comes)
     if (c.input_file.empty() && !remove_only)
         return say("--input-file is mandatory");
     if (!remove_only && !fs::exists(c.input_file))
@@ -206,6 +212,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--extend            " << c.extend << '\n';
     if (c.remove_given)
         std::cerr << "--remove            " << c.remove << '\n';
+    if (c.fold_given)
+        std::cerr << "--fold              " << c.fold << '\n';
     std::cerr << sep << '\n';
 }
 
@@ -262,6 +270,13 @@ const char* kHelp =
     "                               name the index does not hold, or the removal of every target, ends the command with nothing\n"
     "                               written.  Merged bins above a removed target keep its hashes (`stale` lines of the report say\n"
     "                               how many, estimated); rows never shrink\n"
+    "      --fold arg               [--update] hold every IBF of the updated index to `arg` bins (>= 2) without the genomes: runs of\n"
+    "                               user bins of a wider IBF, the emptiest first, move into new IBFs one level down, and one merged\n"
+    "                               bin per group -- the OR of the group's columns -- stays behind.  User bins, names and columns are\n"
+    "                               unchanged; a folded target is found one level deeper.  Merged bins are not folded, a new IBF has\n"
+    "                               its parent's rows, and one level is added per command: an IBF that cannot reach `arg` this way\n"
+    "                               ends the command with nothing written (rebuild or give a larger --fold).  --input-file may\n"
+    "                               then be left out.  Not with --verify-index\n"
     "      --verbose                Verbose output mode\n"
     "      --quiet                  Quiet output mode\n"
     "  -h, --help                   Show help commands\n"
@@ -311,7 +326,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update", "--remove" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -372,6 +387,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.update = vals["--update"], c.update_given = true;
         if (vals.count("--remove"))
             c.remove = vals["--remove"], c.remove_given = true;
+        if (vals.count("--fold"))
+            c.fold = u("--fold", 0xFFFFFFFFull), c.fold_given = true;
         if (vals.count("--max-fp"))
             c.max_fp = d("--max-fp"), c.max_fp_given = true;
         if (vals.count("--filter-size"))
@@ -535,7 +552,7 @@ bool run(Config c)
         return fail("--device " + std::to_string(c.device) + " does not exist (" + std::to_string(n_dev) + " visible)");
 
     Totals              totals;
-    const bool          remove_only = c.remove_given && c.input_file.empty();
+    const bool          remove_only = (c.remove_given || c.fold_given) && c.input_file.empty();
     std::vector<Target> targets;
     if (!remove_only)
         targets = read_input_file(c, totals);

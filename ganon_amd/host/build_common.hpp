@@ -46,6 +46,8 @@ struct Config // Config.hpp:10-27
     bool        extend = false;  // (--update only: a target the index holds gains the inputs' sequences)
     std::string remove;          // (--update only: a file of target names, one per line, that leave the index)
     bool        remove_given = false;
+    uint64_t    fold = 0;        // (--update only: hold every IBF of the updated index to this many bins by folding runs of user bins)
+    bool        fold_given = false;
     bool        verify_given = false, kmer_given = false, window_given = false, hashes_given = false, output_given = false;
 };
 

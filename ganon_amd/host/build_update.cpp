@@ -5,7 +5,11 @@
 // With `--remove NAMES` targets leave on the way: the tables after the removal (hibf_remove.hpp) are what the placement works on, B is
 // created without the dropped bins and IBFs, and the move compacts the columns (gn_filter_copy_ibf_spans) -- every row is read and
 // written once either way.  A name in both NAMES and the inputs is replaced: the old user bin goes, the inputs enter as a new one.
+// With `--fold N` the IBFs of the result are held to N bins (hibf_fold.hpp): the plan runs last, on the tables and fills the others leave,
+// B is created with the new IBFs, every surviving and every new IBF takes its columns from A (gn_filter_copy_ibf_spans), the new merged
+// bins are the OR of their groups' columns (gn_filter_fold_ibf), and the inserts go along the rewritten paths.
 #include "build_common.hpp"
+#include "hibf_fold.hpp"
 #include "hibf_pool.hpp"
 #include "hibf_remove.hpp"
 #include "hibf_update.hpp"
@@ -37,7 +41,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             return fail(gn_last_error());
         fresh_target.push_back(t);
     }
-    if (fresh_target.empty() && !(c.remove_given && c.input_file.empty())) // (without inputs only where targets leave and none comes)
+    if (fresh_target.empty() && !((c.remove_given || c.fold_given) && c.input_file.empty())) // (without inputs only where targets leave or move and none comes)
         return fail("No valid sequences to build");
     const double hash_s = counting.seconds() + since(t0);
     std::vector<uint64_t>    remove_user;  // --remove: the user bins that leave, ascending, and the name each of them carries
@@ -213,20 +217,63 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         }
         const gnhibf::UpdatePlan plan =
             gnhibf::plan_update(bins, rows, meta.next_ibf_id, meta.bin_to_user, n_base, h, fpr, pop, fresh_counts, ext_target.empty() ? nullptr : &ex.fills);
-        const uint32_t depth  = plan.paths.depth;
+        // --fold: the rule runs last, on the tables the plans above leave and on a fill per bin: the bit count A shows (or the extension's
+        // prediction), the prediction for a merged bin the new user bins touch, and for a bin of a new run what its share of hashes sets
+        const bool        folding = c.fold_given;
+        gnhibf::FoldPlan  fold;
+        gnhibf::Paths     new_paths = plan.paths; // of the new user bins, along the tables written
+        if (folding)
+        {
+            std::vector<std::vector<double>> fills(n_ibf_b);
+            for (uint64_t i = 0; i < n_ibf_b; ++i)
+            {
+                if (!ext_target.empty())
+                    fills[i] = ex.fills[i];
+                else
+                    fills[i].assign(pop[i].begin(), pop[i].begin() + bins[i]);
+                fills[i].resize(plan.bins[i], 0.0);
+            }
+            for (const gnhibf::UpdateTouched& t : plan.touched)
+                fills[t.ibf][t.bin] = t.bits_predicted;
+            for (size_t j = 0; j < fresh_target.size(); ++j)
+            {
+                const gn_path_entry& run = plan.paths.entries[j * plan.paths.depth];
+                for (uint32_t b = run.first_bin; b < run.first_bin + run.n_bins; ++b)
+                    fills[run.ibf][b] = gnhibf::update_predict(0.0, run.hashes_per_bin, rows[run.ibf], h); // (ceil(count / bins of the run))
+            }
+            try
+            {
+                fold = gnhibf::plan_fold(plan.bins, rows, plan.next_ibf_id, plan.bin_to_user, plan.n_user_bins, h, fpr, fills, c.fold);
+            }
+            catch (const gnhibf::FoldUnreachable& e)
+            {
+                return fail(std::string("--fold: ") + e.what() + "; nothing written");
+            }
+            new_paths = gnhibf::fold_paths(plan.paths, fold);
+            if (!ext_target.empty())
+                old_paths = gnhibf::fold_paths(old_paths, fold);
+        }
+        const std::vector<uint64_t>&             final_bins = folding ? fold.bins : plan.bins;
+        const std::vector<uint64_t>&             final_rows = folding ? fold.rows : rows;
+        const std::vector<std::vector<int64_t>>& final_nx   = folding ? fold.next_ibf_id : plan.next_ibf_id;
+        const std::vector<std::vector<int64_t>>& final_bu   = folding ? fold.bin_to_user : plan.bin_to_user;
+        const uint64_t n_final = final_bins.size();
+        const uint32_t depth   = folding ? fold.depth : plan.paths.depth;
+        // where a bin of the tables the plans worked on is in the file written
+        auto now = [&](uint32_t i, uint32_t b) { return folding ? std::pair<uint32_t, uint32_t>(fold.where[i][b].ibf, fold.where[i][b].bin) : std::pair<uint32_t, uint32_t>(i, b); };
         const double   plan_s = since(t0) - probe_s;
 
         // filter B: the same rows, the new bins.  A and B are on the device together until every IBF is moved
         t0 = std::chrono::steady_clock::now();
-        std::vector<HibfShape> ibfs(n_ibf_b);
+        std::vector<HibfShape> ibfs(n_final);
         uint64_t               a_bytes = 0, b_bytes = 0;
         for (uint64_t i = 0; i < n_ibf; ++i)
             a_bytes += meta.shapes[i].bin_size * gn_hibf_row_stride_words((bins_a[i] + 63) >> 6) * 8;
-        for (uint64_t i = 0; i < n_ibf_b; ++i)
+        for (uint64_t i = 0; i < n_final; ++i)
         {
-            ibfs[i].bins = plan.bins[i], ibfs[i].rows = rows[i];
-            ibfs[i].next_ibf_id = plan.next_ibf_id[i], ibfs[i].bin_to_user = plan.bin_to_user[i];
-            b_bytes += rows[i] * gn_hibf_row_stride_words((plan.bins[i] + 63) >> 6) * 8;
+            ibfs[i].bins = final_bins[i], ibfs[i].rows = final_rows[i];
+            ibfs[i].next_ibf_id = final_nx[i], ibfs[i].bin_to_user = final_bu[i];
+            b_bytes += final_rows[i] * gn_hibf_row_stride_words((final_bins[i] + 63) >> 6) * 8;
         }
         {
             uint64_t free_b = 0, total_b = 0;
@@ -245,12 +292,84 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         gnhost::OwnedFilter b_flt = descs.upload(c.device, plan.n_user_bins);
         if (!b_flt)
             throw std::runtime_error(gn_last_error());
-        for (uint64_t i = 0; i < n_ibf_b; ++i)
-            if ((removing ? gn_filter_copy_ibf_spans(b_flt.get(), (uint32_t)i, sink->filter(), gone.old_ibf[i], gone.spans[i].data(), (uint32_t)gone.spans[i].size())
-                          : gn_filter_copy_ibf(b_flt.get(), (uint32_t)i, sink->filter(), (uint32_t)i)) != GN_OK)
-                throw std::runtime_error(gn_last_error());
+        double fold_s = 0;
+        if (!folding)
+        {
+            for (uint64_t i = 0; i < n_ibf_b; ++i)
+                if ((removing ? gn_filter_copy_ibf_spans(b_flt.get(), (uint32_t)i, sink->filter(), gone.old_ibf[i], gone.spans[i].data(), (uint32_t)gone.spans[i].size())
+                              : gn_filter_copy_ibf(b_flt.get(), (uint32_t)i, sink->filter(), (uint32_t)i)) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+        }
+        else
+        {
+            // the bin of A that holds the column of bin b of IBF i of the tables the fold worked on, or -1: a bin this command adds
+            std::vector<std::vector<int64_t>> a_bin(n_ibf_b);
+            for (uint64_t i = 0; i < n_ibf_b; ++i)
+            {
+                a_bin[i].assign(plan.bins[i], -1);
+                if (!removing)
+                    std::iota(a_bin[i].begin(), a_bin[i].begin() + bins[i], int64_t(0));
+                else
+                    for (const gn_bin_span& s : gone.spans[i])
+                        std::iota(a_bin[i].begin() + s.dst_first, a_bin[i].begin() + s.dst_first + s.n_bins, (int64_t)s.src_first);
+            }
+            auto a_ibf = [&](uint32_t i) { return removing ? gone.old_ibf[i] : i; };
+            // every surviving IBF and every child: its columns out of A, one span per maximal run that is one in A too
+            for (uint64_t f = 0; f < n_final; ++f)
+            {
+                const uint32_t           si = fold.src_ibf[f];
+                std::vector<gn_bin_span> spans;
+                for (const gn_bin_span& s : fold.spans[f])
+                    for (uint32_t j = 0; j < s.n_bins; ++j)
+                    {
+                        const int64_t from = a_bin[si][s.src_first + j];
+                        if (from < 0)
+                            continue;
+                        if (!spans.empty() && spans.back().src_first + spans.back().n_bins == (uint64_t)from && spans.back().dst_first + spans.back().n_bins == s.dst_first + j)
+                            ++spans.back().n_bins;
+                        else
+                            spans.push_back(gn_bin_span{ (uint32_t)from, s.dst_first + j, 1, 0 });
+                    }
+                if (gn_filter_copy_ibf_spans(b_flt.get(), (uint32_t)f, sink->filter(), a_ibf(si), spans.data(), (uint32_t)spans.size()) != GN_OK)
+                    throw std::runtime_error(gn_last_error());
+            }
+            // the new merged bins: per folded parent the OR of every group's columns of A.  A group of new user bins alone has no column
+            // there yet (the inserts below fill its merged bin); the groups on either side of it go in calls of their own
+            const auto t_fold = std::chrono::steady_clock::now();
+            for (size_t g0 = 0; g0 < fold.groups.size();)
+            {
+                const uint32_t              parent = fold.groups[g0].parent;
+                std::vector<gn_fold_member> members;
+                size_t                      g = g0;
+                for (; g < fold.groups.size() && fold.groups[g].parent == parent; ++g)
+                {
+                    const size_t had = members.size();
+                    for (size_t k = 0; k < fold.groups[g].run_first.size(); ++k)
+                        for (uint32_t b = fold.groups[g].run_first[k]; b < fold.groups[g].run_first[k] + fold.groups[g].run_bins[k]; ++b)
+                            if (a_bin[parent][b] >= 0)
+                                members.push_back(gn_fold_member{ (uint32_t)a_bin[parent][b], 1, (uint32_t)(g - g0), 0 });
+                    if (members.size() == had)
+                        break;
+                }
+                if (!members.empty())
+                {
+                    std::sort(members.begin(), members.end(), [](const gn_fold_member& x, const gn_fold_member& y) { return x.src_first < y.src_first; });
+                    std::vector<gn_fold_member> joined; // neighbouring bins of one group are one member
+                    for (const gn_fold_member& m : members)
+                        if (!joined.empty() && joined.back().group == m.group && joined.back().src_first + joined.back().n_bins == m.src_first)
+                            ++joined.back().n_bins;
+                        else
+                            joined.push_back(m);
+                    if (gn_filter_fold_ibf(b_flt.get(), parent, fold.groups[g0].merged_bin, (uint32_t)(g - g0), sink->filter(), a_ibf(parent), joined.data(),
+                                           (uint32_t)joined.size()) != GN_OK)
+                        throw std::runtime_error(gn_last_error());
+                }
+                g0 = g > g0 ? g : g0 + 1; // (g == g0: the group at g0 has no column in A)
+            }
+            fold_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_fold).count();
+        }
         sink.reset(); // (frees A)
-        const double copy_s = since(t0);
+        const double copy_s = since(t0) - fold_s;
 
         // the new sets along their paths, pooled as run_hibf pools them; before them the extensions, by their quotas
         // (the pooler may cut the extensions into several calls.  A later call takes presence against B after the earlier ORs, not against A,
@@ -272,7 +391,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         gnhibf::for_each_pooled(
             fresh_target.size(),
             [&](size_t j) { return hash_set(targets[fresh_target[j]]); },
-            [&](size_t j) { return &plan.paths.entries[j * depth]; }, depth,
+            [&](size_t j) { return &new_paths.entries[j * depth]; }, depth,
             [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>&) {
                 if (gn_filter_emplace_path(b_flt.get(), hashes, off, (uint32_t)n, p, depth) != GN_OK)
                     throw std::runtime_error(gn_last_error());
@@ -281,22 +400,26 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
 
         // B's bit counts, for the IBFs the report speaks of: those that gained bins or lie on a new path
         t0 = std::chrono::steady_clock::now();
-        std::vector<bool> shown(n_ibf_b, false);
+        std::vector<bool> shown(n_final, false);
         for (uint64_t i = 0; i < n_ibf_b; ++i)
-            shown[i] = plan.bins[i] != bins[i] || (removing && bins[i] != bins_a[gone.old_ibf[i]]);
+            shown[i] = final_bins[i] != bins[i] || (removing && bins[i] != bins_a[gone.old_ibf[i]]);
+        for (uint64_t i = n_ibf_b; i < n_final; ++i) // (--fold: the IBFs it creates)
+            shown[i] = true;
+        for (const uint32_t i : fold.folded)
+            shown[i] = true;
         for (const gnhibf::RemoveStale& st : gone.stale)
             shown[st.ibf] = true;
-        for (const gn_path_entry& e : plan.paths.entries)
+        for (const gn_path_entry& e : new_paths.entries)
             if (e.n_bins)
                 shown[e.ibf] = true;
         for (const uint64_t u : ext_user_b)
             for (uint32_t d = 0; d < depth && old_paths.entries[(size_t)u * depth + d].n_bins; ++d)
                 shown[old_paths.entries[(size_t)u * depth + d].ibf] = true;
-        std::vector<std::vector<uint64_t>> pop_b(n_ibf_b);
-        for (uint64_t i = 0; i < n_ibf_b; ++i)
+        std::vector<std::vector<uint64_t>> pop_b(n_final);
+        for (uint64_t i = 0; i < n_final; ++i)
             if (shown[i])
             {
-                pop_b[i].assign(plan.bins[i], 0);
+                pop_b[i].assign(final_bins[i], 0);
                 if (gn_filter_bin_popcounts(b_flt.get(), (uint32_t)i, pop_b[i].data()) != GN_OK)
                     throw std::runtime_error(gn_last_error());
             }
@@ -336,14 +459,14 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         const double bound_fill = std::pow(fpr, 1.0 / h);
         std::cout << "index\t" << c.update << "\t->\t" << c.output_file << "\tk=" << unsigned(c.kmer_size) << " w=" << c.window_size << " h=" << unsigned(h)
                   << " ibfs=" << n_ibf;
-        if (removing)
-            std::cout << "->" << n_ibf_b;
+        if (removing || folding)
+            std::cout << "->" << n_final;
         std::cout << " levels=" << depth << " user_bins=" << n_old << "->" << plan.n_user_bins << " fpr=" << fpr << "\n";
         std::cout << "#target\tuser_bin\tdistinct_hashes\tleaf_ibf\tfirst_bin\tbins\tdepth\tpath\n";
         uint64_t bins_added = 0;
         for (size_t j = 0; j < fresh_target.size(); ++j)
         {
-            const gn_path_entry* p    = &plan.paths.entries[j * depth];
+            const gn_path_entry* p    = &new_paths.entries[j * depth];
             uint32_t             used = 0;
             while (used < depth && p[used].n_bins)
                 ++used;
@@ -378,7 +501,10 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
                 std::cout << "dropped\t" << d.ibf << "\t" << d.parent_ibf << "\t" << d.parent_bin << "\n";
             std::cout << "#stale\tibf\tbin\tbits\testimated_stale_hashes\n";
             for (const gnhibf::RemoveStale& st : gone.stale)
-                std::cout << "stale\t" << st.ibf << "\t" << st.bin << "\t" << pop_b[st.ibf][st.bin] << "\t" << estimate(st.hashes, st.full) << "\n";
+            {
+                const auto [i, b] = now(st.ibf, st.bin);
+                std::cout << "stale\t" << i << "\t" << b << "\t" << pop_b[i][b] << "\t" << estimate(st.hashes, st.full) << "\n";
+            }
         }
         if (c.extend)
         {
@@ -399,15 +525,21 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
             }
             std::cout << "#run\tibf\tbin\tdealt\tbits_before\tbits_predicted\tbits_after\n";
             for (const gnhibf::ExtendRunBin& r : ex.run)
-                std::cout << "run\t" << r.ibf << "\t" << r.bin << "\t" << r.dealt << "\t" << r.bits_before << "\t" << std::fixed << std::setprecision(1) << r.bits_predicted << "\t"
-                          << pop_b[r.ibf][r.bin] << "\n";
+            {
+                const auto [i, b] = now(r.ibf, r.bin);
+                std::cout << "run\t" << i << "\t" << b << "\t" << r.dealt << "\t" << r.bits_before << "\t" << std::fixed << std::setprecision(1) << r.bits_predicted << "\t"
+                          << pop_b[i][b] << "\n";
+            }
         }
         std::cout << "#ibf\trows\tbins_before\tbins_after\tmax_fill_before\tmax_fill_after\n" << std::fixed << std::setprecision(6);
         for (uint64_t i = 0; i < n_ibf_b; ++i)
             if (shown[i])
-                std::cout << "ibf\t" << i << "\t" << rows[i] << "\t" << (removing ? bins_a[gone.old_ibf[i]] : bins[i]) << "\t" << plan.bins[i] << "\t"
+                std::cout << "ibf\t" << i << "\t" << rows[i] << "\t" << (removing ? bins_a[gone.old_ibf[i]] : bins[i]) << "\t" << final_bins[i] << "\t"
                           << *std::max_element(pop[i].begin(), pop[i].end()) / (double)rows[i] << "\t"
                           << *std::max_element(pop_b[i].begin(), pop_b[i].end()) / (double)rows[i] << "\n";
+        for (uint64_t i = n_ibf_b; i < n_final; ++i) // (--fold: an IBF it creates had no bin before)
+            std::cout << "ibf\t" << i << "\t" << final_rows[i] << "\t0\t" << final_bins[i] << "\t" << 0.0 << "\t"
+                      << *std::max_element(pop_b[i].begin(), pop_b[i].end()) / (double)final_rows[i] << "\n";
         std::cout << "#merged\tibf\tbin\tbits_before\tbits_predicted\tbits_after\n";
         uint64_t fullest = 0, fullest_rows = 1;
         bool     any_touched = false;
@@ -422,17 +554,31 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         }
         for (const gnhibf::UpdateTouched& t : touched)
         {
-            const uint64_t after = pop_b[t.ibf][t.bin];
-            std::cout << "merged\t" << t.ibf << "\t" << t.bin << "\t" << t.bits_before << "\t" << std::setprecision(1) << t.bits_predicted << std::setprecision(6) << "\t"
+            const auto [ti, tb]  = now(t.ibf, t.bin); // (a merged bin stays in its IBF; a fold may move it to the left)
+            const uint64_t after = pop_b[ti][tb];
+            std::cout << "merged\t" << ti << "\t" << tb << "\t" << t.bits_before << "\t" << std::setprecision(1) << t.bits_predicted << std::setprecision(6) << "\t"
                       << after << (after > bound_fill * rows[t.ibf] ? "\tWARN fill" : "") << "\n";
             if (!any_touched || after * (double)fullest_rows > fullest * (double)rows[t.ibf])
                 fullest = after, fullest_rows = rows[t.ibf];
             any_touched = true;
         }
+        if (folding)
+        {
+            // (a merged bin that holds new user bins was predicted with their fills; one an extension passes through may end above it)
+            std::cout << "#folded\tparent_ibf\tmerged_bin\tnew_ibf\truns\tbins\tbits_predicted\tbits_found\n";
+            for (const gnhibf::FoldGroup& g : fold.groups)
+            {
+                const uint64_t found = pop_b[g.parent][g.merged_bin];
+                std::cout << "folded\t" << g.parent << "\t" << g.merged_bin << "\t" << g.new_ibf << "\t" << g.runs << "\t" << g.bins << "\t" << std::setprecision(1) << g.bits_predicted
+                          << std::setprecision(6) << "\t" << found << (found > bound_fill * final_rows[g.parent] ? "\tWARN fill" : "") << "\n";
+            }
+        }
         std::error_code ec;
         std::cout << "result\tok\t";
         if (removing)
             std::cout << gone.removed.size() << " user bin(s) removed, " << gone.dropped.size() << " IBF(s) dropped, ";
+        if (folding)
+            std::cout << fold.groups.size() << " IBF(s) created under " << fold.folded.size() << " folded, ";
         if (c.extend)
             std::cout << ext_target.size() << " user bin(s) extended, ";
         std::cout << fresh_target.size() << " user bin(s) added, " << bins_added << " bin(s) added, " << fs::file_size(c.update, ec) << " -> "
@@ -447,7 +593,7 @@ bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counti
         std::cout << std::endl;
         if (c.verbose && !c.quiet)
             std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " count " << count_s + count_b_s + probe_s << " plan " << plan_s << " copy " << copy_s
-                      << " emplace " << emplace_s << " write " << write_s << std::endl;
+                      << (folding ? " fold " + std::to_string(fold_s) : std::string()) << " emplace " << emplace_s << " write " << write_s << std::endl;
         return true;
     }
     catch (const std::exception& e)

@@ -17,8 +17,8 @@
 // to the next, so that two of them do not claim the same room.
 // Doubles occur in predict, in the eligibility bound, and inside hibf_run_bits; everything else is integers, and the same input gives
 // the same plan.
-// Stated limits: tmax does not bound an updated IBF, and no subtree is grafted -- a user bin that fits no merged bin of the root widens
-// the root.  Refused (std::runtime_error): malformed tables (derive_paths is called first), inconsistent sizes, a count of 0 or
+// Stated limits: this plan creates no IBF and grafts no subtree -- a user bin that fits no merged bin of the root widens the root; what
+// holds an updated IBF to a number of bins is plan_fold (hibf_fold.hpp, `--fold`), which runs on the tables this plan leaves.  Refused (std::runtime_error): malformed tables (derive_paths is called first), inconsistent sizes, a count of 0 or
 // above 2^48, and a run that would need more than 65536 bins.
 //
 // `--update --extend` adds hashes to user bins the index holds already (plan_extend; it comes first, since an extension has no choice of

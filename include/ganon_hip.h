@@ -500,6 +500,24 @@ typedef struct
 int gn_filter_copy_ibf_spans(gn_filter* dst, uint32_t dst_ibf, const gn_filter* src, uint32_t src_ibf, const gn_bin_span* spans,
                              uint32_t n_spans);
 
+/* `ganon-build --hibf --update --fold`: the merged bins above groups of bins of an IBF (no counterpart in the reference).
+ * gn_filter_fold_ibf: for every row, bit dst_first + g of IBF dst_ibf of `dst` is ORed with the OR of bits src_first .. src_first +
+ *   n_bins - 1 of the row of IBF src_ibf of `src`, over all members of group g, for every g < n_groups; no other bit of the destination
+ *   changes, and what the destination held stays (the call is an OR).  A hash's row depends on the hash, the seed and the IBF's row count
+ *   only, so with equal rows this is, bit for bit, the merged bin a build would have put above the group.  The members ascend and are
+ *   disjoint in the source; their groups are free in order, and a group may have several members.  n_groups == 0 does nothing.
+ *   GN_EINVAL, with everything checked before anything is launched (a refused call writes nothing): a null argument; a filter that is
+ *   not an HIBF, or two filters on different devices; an IBF out of range, or an IBF onto itself; differing rows or hash functions; a
+ *   member of 0 bins or beyond the source's bins; members that overlap or do not ascend; a group >= n_groups, or a group without a
+ *   member; dst_first + n_groups beyond the destination's bins.  GN_ERANGE for more groups than one call holds (above 170 000).
+ *   Returns when the fold is complete. */
+typedef struct
+{
+    uint32_t src_first, n_bins, group, reserved;
+} gn_fold_member;
+int gn_filter_fold_ibf(gn_filter* dst, uint32_t dst_ibf, uint32_t dst_first, uint32_t n_groups, const gn_filter* src, uint32_t src_ibf,
+                       const gn_fold_member* members, uint32_t n_members);
+
 /* `ganon-build --hibf --layout sketch | similarity`: HyperLogLog sketches of hash sets and the estimated cardinality of unions of neighbouring
  * sketches -- what a layout search asks n * width times (raptor gets its tree from chopper's sketches through `raptor layout`,
  * /root/reference/src/ganon/build_update.py:411-518).  The estimates choose the tree only: the IBFs are sized from gn_hashes_union.

@@ -25,6 +25,8 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --remove N      [--update M] the update also takes the first N targets of the index out (`--remove`): its laps beside copy_s of the
                   same update without --remove (the plain move against the compacting one), the file checked over the files that are
                   left, beside a rebuild from those.  Not with --extend
+  --fold N        [--update M] the update also holds every IBF to N bins (`--fold N`): its `fold` lap beside its `copy` lap, the `folded`
+                  lines, the IBFs before and after, the file checked like any updated one
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
@@ -40,7 +42,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -179,6 +181,7 @@ def update_run(layout, m):
            "--verbose"] + (["--extend"] if extend else [])
     n_remove = int(opts["--remove"] or 0)
     lap = r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)"
+    lap_keys = ("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s")
     if extend:  # one warm-up, then the runs: the update's own seconds and the process's wall time
         emplace, total = [], []
         for r in range(int(opts["--runs"]) + 1):
@@ -198,15 +201,21 @@ def update_run(layout, m):
         open(os.path.join(d, "remove.txt"), "w").writelines(ln.rstrip("\n").split("\t")[1] + "\n" for ln in lines[:n_remove])
         open(os.path.join(d, "in.tsv"), "w").writelines(lines[n_remove:])  # what the check and the rebuild read
         cmd += ["--remove", os.path.join(d, "remove.txt")]
+    if opts["--fold"]:  # (behind the runs above: their laps are those of the update without it)
+        cmd += ["--fold", opts["--fold"]]
+        lap, lap_keys = lap.replace(" emplace ", " fold ([0-9.eE+-]+) emplace "), lap_keys[:5] + ("fold_s",) + lap_keys[5:]
     t0 = time.time()
     p = subprocess.run(cmd, capture_output=True, text=True)
     upd = {"rc": p.returncode, "wall_s": round(time.time() - t0, 2)}
+    if opts["--fold"]:
+        upd["fold"], upd["index_line"] = int(opts["--fold"]), p.stdout.split("\n", 1)[0]
+        upd["folded_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith("folded\t")][:12]
     if n_remove:
         upd["removed"], upd["copy_s_without_remove"] = n_remove, plain_copy_s
         upd["removed_lines"] = [ln for ln in p.stdout.splitlines() if ln.startswith(("removed\t", "dropped\t", "stale\t"))][:12]
     mm = re.search(lap, p.stderr)
     if mm:
-        for key, x in zip(("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s"), mm.groups()):
+        for key, x in zip(lap_keys, mm.groups()):
             upd[key] = float(x)
     mm = re.search(r"^result\t.*", p.stdout, re.M)
     upd["result"] = mm.group(0) if mm else (p.stderr or p.stdout)[-300:]
