@@ -186,6 +186,18 @@ __global__ void gn_clear_padding_kernel(uint64_t* rows, uint64_t S, uint64_t W, 
         rows[r * Ws + (W - 1)] &= mask;
 }
 
+// The same for an IBF some of whose bins are absent (a part of a subtree-partitioned HIBF: the root's bins that other parts own arrive
+// with the streamed rows all the same): the words of a row that hold absent bins -- the part's boundary words -- are ANDed with the mask
+// of the bins that are present, uploaded once.  blockIdx.y picks the word, the threads of a row of blocks the rows.
+__global__ __launch_bounds__(256) void gn_clear_absent_kernel(uint64_t* rows, uint64_t S, uint64_t Ws, const uint32_t* __restrict__ col,
+                                                             const uint64_t* __restrict__ keep)
+{
+    const uint64_t j = col[blockIdx.y], m = keep[blockIdx.y];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < S; r += stride)
+        rows[r * Ws + j] &= m;
+}
+
 extern "C" uint64_t gn_hibf_row_stride_words(uint64_t bin_words)
 {
     return gn_sw().hibf_dense_rows ? bin_words : gn_pad_row_words(bin_words);
@@ -447,6 +459,8 @@ extern "C" int gn_filter_upload_ibf(int device, const gn_ibf_desc* ibf, const ui
 int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const int64_t* const* next_ibf_id,
                   const int64_t* const* bin2userbin, uint64_t n_user_bins); // gn_hibf.hip
 
+static int gn_clear_padding(gn_filter* f, GnIbfHost* ib, hipStream_t st);
+
 extern "C" int gn_filter_upload_hibf(int device, uint32_t n_ibf, const gn_ibf_desc* ibfs, const int64_t* const* next_ibf_id,
                                      const int64_t* const* bin2userbin, uint64_t n_user_bins, gn_filter** out)
 {
@@ -475,6 +489,16 @@ extern "C" int gn_filter_upload_hibf(int device, uint32_t n_ibf, const gn_ibf_de
         }
     }
     rc = gn_hibf_build(f, n_ibf, ibfs, next_ibf_id, bin2userbin, n_user_bins);
+    // (rows that came with the call: the bits of absent bins go now; streamed rows are cleared by gn_filter_finalize)
+    bool cleared = false;
+    for (uint32_t i = 0; i < n_ibf && rc == GN_OK; ++i)
+        if (ibfs[i].rows && f->ibfs[i].n_keep)
+        {
+            rc      = gn_clear_padding(f, &f->ibfs[i], nullptr);
+            cleared = true;
+        }
+    if (rc == GN_OK && cleared && hipDeviceSynchronize() != hipSuccess)
+        rc = gn_fail(GN_ENODEV, "gn_filter_upload_hibf: clearing absent bins failed");
     if (rc)
     {
         gn_filter_free(f);
@@ -752,7 +776,13 @@ extern "C" int gn_filter_write_sync(gn_filter* f)
 
 static int gn_clear_padding(gn_filter* f, GnIbfHost* ib, hipStream_t st)
 {
-    if (ib->B & 63)
+    if (ib->n_keep)
+    {
+        hipLaunchKernelGGL(gn_clear_absent_kernel, dim3((unsigned)std::min<uint64_t>((ib->S + 255) / 256, 65536), ib->n_keep), dim3(256), 0, st,
+                           ib->d_rows, ib->S, ib->Ws, ib->d_keep_col, ib->d_keep);
+        GN_HIP(hipGetLastError());
+    }
+    else if (ib->B & 63)
     {
         hipLaunchKernelGGL(gn_clear_padding_kernel, dim3((unsigned)((ib->S + 255) / 256)), dim3(256), 0, st, ib->d_rows, ib->S,
                            ib->W, ib->Ws, (1ull << (ib->B & 63)) - 1ull);

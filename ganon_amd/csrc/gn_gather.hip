@@ -45,6 +45,7 @@ struct gn_gather
     uint64_t  n_matches = 0;
     uint64_t  peer_bytes = 0; // bytes that crossed devices in the last run
     bool      ran = false;
+    bool      merged = false; // gn_gather_create_merged: a read's records are merged by translated id, not put part after part
 };
 
 struct GnGatherParams
@@ -113,6 +114,114 @@ __global__ __launch_bounds__(256) void gn_gather_parts_kernel(GnGatherParams p)
                 p.out[w + j] = m;
             }
             w += cs;
+        }
+    }
+}
+
+// ---- the merging gather: the subtree parts of an HIBF (host/hibf_partition.hpp) --------------------------------------------------------
+// A part of an HIBF owns root bins with their whole subtrees, and its user bins are numbered part-locally in ascending GLOBAL
+// user-bin id: a part's segment of a read (sorted by local id, gn_hibf.hip's radix sort) ascends in global id, but the parts' ids
+// interleave (the layout sorts user bins by size, not by file position).  The unpartitioned filter's result is sorted by
+// (read, user bin): the parts' segments are merged.  No serial k-way loop: an element's place is
+//     moff[r] + its index in its own segment + sum over the OTHER parts of (records there with a smaller translated id),
+// the last term a binary search per other part.  Ties (which disjoint parts never produce) go lower part first: against a lower
+// part the search counts "<=", against a higher one "<".
+
+__device__ __forceinline__ uint32_t gn_gm_key(const gn_match* in, const uint32_t* map, uint64_t j)
+{
+    const uint32_t t = in[j].target;
+    return map ? map[t] : t;
+}
+
+// records of in[b, b + n) whose translated id is < key (or <= key with `incl`); the segment ascends in translated id
+__device__ __forceinline__ uint32_t gn_gm_rank(const gn_match* in, const uint32_t* map, uint64_t b, uint32_t n, uint32_t key, bool incl)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint32_t k   = gn_gm_key(in, map, b + mid);
+        if (k < key || (incl && k == key))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// place of a record with translated id `key` of part i among the read's records of all parts but i
+__device__ __forceinline__ uint32_t gn_gm_others(const GnGatherParams& p, uint64_t r, uint32_t i, uint32_t key)
+{
+    uint32_t before = 0;
+    for (uint32_t i2 = 0; i2 < p.k; ++i2)
+    {
+        if (i2 == i)
+            continue;
+        const uint64_t b2 = p.off[i2][r] - p.off[i2][0];
+        const uint32_t n2 = (uint32_t)(p.off[i2][r + 1] - p.off[i2][r]);
+        if (n2)
+            before += gn_gm_rank(p.in[i2], p.map[i2], b2, n2, key, i2 < i);
+    }
+    return before;
+}
+
+__global__ __launch_bounds__(256) void gn_gather_merge_kernel(GnGatherParams p)
+{
+    const uint64_t r     = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane  = threadIdx.x & 63u;
+    const bool     valid = r < p.n_reads;
+    uint64_t       o = 0;
+    uint32_t       c = 0, np = 0; // records of the read, parts that hold some
+    if (r <= p.n_reads)
+    {
+        for (uint32_t i = 0; i < p.k; ++i)
+            o += p.off[i][r] - p.off[i][0];
+        p.moff[r] = o;
+    }
+    if (valid)
+        for (uint32_t i = 0; i < p.k; ++i)
+        {
+            const uint32_t cs = (uint32_t)(p.off[i][r + 1] - p.off[i][r]);
+            c += cs;
+            np += cs != 0;
+        }
+    // light reads, a lane each: every record looks its place up among the (at most GN_GATHER_LIGHT - 1) others
+    if (valid && c != 0 && c <= GN_GATHER_LIGHT)
+        for (uint32_t i = 0; i < p.k; ++i)
+        {
+            const uint64_t base = p.off[i][0], b = p.off[i][r] - base, e = p.off[i][r + 1] - base;
+            for (uint64_t j = b; j < e; ++j)
+            {
+                gn_match m = p.in[i][j];
+                if (p.map[i])
+                    m.target = p.map[i][m.target];
+                const uint32_t pos = (uint32_t)(j - b) + (np > 1 ? gn_gm_others(p, r, i, m.target) : 0u);
+                p.out[o + pos]     = m;
+            }
+        }
+    // heavy reads, the wave each: lanes stride over a part's segment, a binary search per other part
+    uint64_t heavy = __ballot(valid && c > GN_GATHER_LIGHT);
+    while (heavy)
+    {
+        const uint32_t L = (uint32_t)__builtin_ctzll(heavy);
+        heavy &= heavy - 1;
+        const uint64_t rr = r - lane + L;
+        const uint64_t w  = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(o >> 32), (int)L) << 32) |
+                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)o, (int)L);
+        const bool     alone = (uint32_t)__builtin_amdgcn_readlane((int)np, (int)L) <= 1u;
+        for (uint32_t i = 0; i < p.k; ++i)
+        {
+            const uint64_t  b   = p.off[i][rr] - p.off[i][0];
+            const uint32_t  cs  = (uint32_t)(p.off[i][rr + 1] - p.off[i][rr]);
+            const uint32_t* map = p.map[i];
+            for (uint32_t j = lane; j < cs; j += 64)
+            {
+                gn_match m = p.in[i][b + j];
+                if (map)
+                    m.target = map[m.target];
+                const uint32_t pos = j + (alone ? 0u : gn_gm_others(p, rr, i, m.target));
+                p.out[w + pos]     = m;
+            }
         }
     }
 }
@@ -226,10 +335,10 @@ extern "C" int gn_gather_destroy(gn_gather* g)
     return GN_OK;
 }
 
-extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, gn_gather** out)
+static int gn_gather_make(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, bool merged, gn_gather** out)
 {
     if (!out || n_parts == 0 || n_parts > GN_GATHER_MAX_PARTS)
-        return gn_fail(GN_EINVAL, "gn_gather_create: 1..%d parts", GN_GATHER_MAX_PARTS);
+        return gn_fail(GN_EINVAL, "%s: 1..%d parts", merged ? "gn_gather_create_merged" : "gn_gather_create", GN_GATHER_MAX_PARTS);
     *out = nullptr;
     int c = 0;
     if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
@@ -242,6 +351,7 @@ extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* co
         return gn_fail(GN_ENOMEM, "out of host memory");
     g->device  = device;
     g->n_parts = n_parts;
+    g->merged  = merged;
     g->d_map.resize(n_parts);
     g->n_map.assign(n_parts, 0);
     g->d_off.resize(n_parts);
@@ -263,6 +373,27 @@ extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* co
     return GN_OK;
 }
 
+extern "C" int gn_gather_create(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, gn_gather** out)
+{
+    return gn_gather_make(device, n_parts, target_map, n_map, false, out);
+}
+
+// every target_map[i] strictly increasing, every part's segment of a read ascending in part-local id, translated ids of
+// different parts disjoint: per read the union of the parts' records in ascending translated id
+extern "C" int gn_gather_create_merged(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, gn_gather** out)
+{
+    return gn_gather_make(device, n_parts, target_map, n_map, true, out);
+}
+
+static void gn_gather_launch(gn_gather* g, const GnGatherParams& p)
+{
+    const dim3 grid((unsigned)(((uint64_t)p.n_reads + 1 + 255) / 256));
+    if (g->merged)
+        hipLaunchKernelGGL(gn_gather_merge_kernel, grid, dim3(256), 0, g->st, p);
+    else
+        hipLaunchKernelGGL(gn_gather_parts_kernel, grid, dim3(256), 0, g->st, p);
+}
+
 template <typename T>
 static hipError_t gn_gather_reserve(GnDev<T>& b, uint64_t need)
 {
@@ -280,7 +411,7 @@ extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n
     for (uint32_t i = 0; i < n_streams; ++i)
     {
         gn_stream* s = streams[i];
-        if (!s || s->f->is_hibf)
+        if (!s || (s->f->is_hibf && !g->merged))
             return gn_fail(GN_EINVAL, "gn_gather_run: part %u is not a stream on a flat IBF", i);
         if (s->pf_on && s->pf_joint && !s->pf_joint_done)
             return gn_fail(GN_EINVAL, "gn_gather_run: part %u waits for gn_streams_postfilter_joint", i);
@@ -300,7 +431,7 @@ extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n
     for (uint32_t i = 0; i < n_streams; ++i)
     {
         gn_stream*      s   = streams[i];
-        const uint32_t  wpr = s->f->geom.wpr;
+        const uint32_t  wpr = s->f->is_hibf ? 1u : (uint32_t)s->f->geom.wpr;
         const uint64_t* src_off;
         GN_HIP(hipSetDevice(s->device));
         if (s->pf_on)
@@ -347,7 +478,7 @@ extern "C" int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n
     GN_HIP(gn_gather_reserve(g->d_out, total));
     p.moff = g->d_moff;
     p.out  = g->d_out;
-    hipLaunchKernelGGL(gn_gather_parts_kernel, dim3((unsigned)(((uint64_t)n + 1 + 255) / 256)), dim3(256), 0, g->st, p);
+    gn_gather_launch(g, p);
     GN_HIP(hipGetLastError());
     g->n_reads   = n;
     g->n_matches = total;
@@ -383,7 +514,7 @@ extern "C" int gn_gather_run_buffers(gn_gather* g, const uint64_t* const* d_off,
     GN_HIP(gn_gather_reserve(g->d_out, total));
     p.moff = g->d_moff;
     p.out  = g->d_out;
-    hipLaunchKernelGGL(gn_gather_parts_kernel, dim3((unsigned)(((uint64_t)n_reads + 1 + 255) / 256)), dim3(256), 0, g->st, p);
+    gn_gather_launch(g, p);
     GN_HIP(hipGetLastError());
     g->n_reads    = n_reads;
     g->n_matches  = total;

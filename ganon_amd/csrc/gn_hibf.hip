@@ -1408,6 +1408,7 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
     {
         const uint64_t B = ibfs[i].bins;
         std::vector<uint4>    runs, mruns;
+        std::vector<uint64_t> absent; // per word of a row: the bins that are present (empty: all of them)
         std::vector<uint32_t> tab((size_t)f->ibfs[i].Ws * 64, 0xFFFFFFFFu); // (the kernels see the padded row: its extra bins lead nowhere)
         uint64_t b = 0;
         while (b < B)
@@ -1415,7 +1416,16 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
             const int64_t u = bin2userbin[i][b];
             if (u >= (int64_t)n_user_bins)
                 return gn_fail(GN_EINVAL, "ibf %u bin %llu: user bin %lld out of range", i, (unsigned long long)b, (long long)u);
-            if (u < 0)
+            if (u == -1 && next_ibf_id[i][b] == -1)
+            {
+                // absent: a bin of the root that another part of a subtree-partitioned HIBF owns (host/hibf_partition.hpp).  No run, the
+                // table says "leads nowhere" as for padding, and gn_filter_finalize clears its bits in every row
+                if (absent.empty())
+                    absent.assign((size_t)f->ibfs[i].W, ~0ull);
+                absent[b >> 6] &= ~(1ull << (b & 63));
+                ++b;
+            }
+            else if (u < 0)
             {
                 const int64_t c = next_ibf_id[i][b];
                 if (c < 0 || c >= (int64_t)n_ibf || c == (int64_t)i)
@@ -1444,6 +1454,22 @@ int gn_hibf_build(gn_filter* f, uint32_t n_ibf, const gn_ibf_desc* ibfs, const i
         GN_HIP(d_runs.upload(runs.data(), runs.size()));
         GN_HIP(d_mruns.upload(mruns.data(), mruns.size()));
         GN_HIP(d_tab.upload(tab.data(), tab.size()));
+        if (!absent.empty())
+        {
+            if (B & 63)
+                absent.back() &= (1ull << (B & 63)) - 1ull;
+            std::vector<uint32_t> col;
+            std::vector<uint64_t> keep;
+            for (size_t j = 0; j < absent.size(); ++j)
+                if (absent[j] != ~0ull)
+                {
+                    col.push_back((uint32_t)j);
+                    keep.push_back(absent[j]);
+                }
+            GN_HIP(f->ibfs[i].d_keep_col.upload(col.data(), col.size()));
+            GN_HIP(f->ibfs[i].d_keep.upload(keep.data(), keep.size()));
+            f->ibfs[i].n_keep = (uint32_t)col.size();
+        }
         dev[i].rows    = f->ibfs[i].d_rows;
         dev[i].S       = f->ibfs[i].S;
         dev[i].W       = (uint32_t)f->ibfs[i].Ws; // width = stride on the device: the words a row is padded with are zero

@@ -242,6 +242,11 @@ struct GnIbfHost
     uint64_t  Ws = 0; // words from one row to the next on the device: W, or -- the IBFs of an HIBF -- W padded so that no row straddles a 128-byte
                       // line (gn_pad_row_words); the words beyond W are zero.  Everything the C ABI takes or returns is W words a row.
     uint32_t  h = 0, shift = 0;
+    // an IBF of an HIBF part with absent bins (gn_hibf_build): the words of a row that hold absent bins (the boundary words of a part's
+    // root) and the bins present in each; gn_filter_finalize ANDs these words of every row (the padding of the last word included)
+    GnDev<uint32_t> d_keep_col;
+    GnDev<uint64_t> d_keep;
+    uint32_t        n_keep = 0;
 };
 
 // Row stride of an HIBF's IBF.  raptor lays an IBF out with ceil(bins / 64) words a row: 3, 5, 9 ... 15 words for most lower IBFs, and a row

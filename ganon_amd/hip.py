@@ -23,7 +23,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_stream_upload_reads", "gn_stream_minimisers", "gn_stream_classify", "gn_submit_batch", "gn_stream_sync", "gn_fetch_batch", "gn_stream_set_postfilter",
                "gn_fetch_postfilter", "gn_streams_postfilter_joint", "gn_stream_set_long_reads", "gn_stream_device_matches",
                "gn_stream_distinct_hashes", "gn_filter_emplace_split", "gn_stream_fetch_hashes", "gn_stream_dense_counts",
-               "gn_stream_timings", "gn_gather_create", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
+               "gn_stream_timings", "gn_gather_create", "gn_gather_create_merged", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
                "gn_gather_destroy", "gn_device_memory", "gn_hibf_row_stride_words", "gn_gather_run_buffers", "gn_stream_device_offsets", "gn_stream_hibf_levels", "gn_stream_hibf_level_lines", "gn_stream_classify_shared",
                "gn_stream_upload_fastq", "gn_stream_fastq_index", "gn_stream_fastq_keep", "gn_stream_fastq_records",
                "gn_peer_stats", "gn_stream_upload_text", "gn_stream_upload_text_pair", "gn_stream_text_pair_index", "gn_stream_text_pair_records2",
@@ -178,6 +178,7 @@ def load_library():
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
+    L.gn_gather_create_merged.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
     L.gn_gather_run.argtypes = [vp, C.POINTER(vp), u32]
     L.gn_gather_fetch.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.gn_gather_device_matches.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
@@ -434,16 +435,18 @@ class HipReassign:
 
 
 class HipGather:
-    """gn_gather: the column parts of a bin-range partitioned flat IBF put back together on the batch's owner device."""
+    """gn_gather: the column parts of a bin-range partitioned flat IBF put back together on the batch's owner device;
+    merged=True: the subtree parts of an HIBF, a read's segments merged by translated id (gn_gather_create_merged)."""
 
-    def __init__(self, device: int, target_maps: Sequence[Optional[np.ndarray]]):
+    def __init__(self, device: int, target_maps: Sequence[Optional[np.ndarray]], merged: bool = False):
         self._maps = [None if m is None else np.ascontiguousarray(m, dtype=np.uint32) for m in target_maps]
         n = len(self._maps)
         ptrs = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in self._maps])
         sizes = np.array([0 if m is None else len(m) for m in self._maps], dtype=np.uint32)
         self._h = C.c_void_p()
         self.n_reads = 0
-        _check(load_library().gn_gather_create(device, n, ptrs, _p(sizes), C.byref(self._h)))
+        L = load_library()
+        _check((L.gn_gather_create_merged if merged else L.gn_gather_create)(device, n, ptrs, _p(sizes), C.byref(self._h)))
 
     def run(self, streams: Sequence["HipStream"]) -> None:
         arr = (C.c_void_p * len(streams))(*[st._h for st in streams])

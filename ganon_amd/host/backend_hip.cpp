@@ -375,10 +375,12 @@ public:
                     std::vector<uint32_t>        sizes;
                     for (auto& part : lf.parts)
                     {
-                        maps.push_back(part.dp->to_target.empty() ? nullptr : part.dp->to_target.data());
-                        sizes.push_back((uint32_t)part.dp->to_target.size());
+                        // (subtree parts of an HIBF: their ids interleave -- merged by the file's user bin, which the host then translates)
+                        auto const& map = lf.is_hibf ? part.dp->user_global : part.dp->to_target;
+                        maps.push_back(map.empty() ? nullptr : map.data());
+                        sizes.push_back((uint32_t)map.size());
                     }
-                    if (gn_gather_create(device_, (uint32_t)lf.parts.size(), maps.data(), sizes.data(), &lf.gather) != GN_OK)
+                    if ((lf.is_hibf ? gn_gather_create_merged : gn_gather_create)(device_, (uint32_t)lf.parts.size(), maps.data(), sizes.data(), &lf.gather) != GN_OK)
                     {
                         err = gn_last_error();
                         return false;
@@ -402,6 +404,8 @@ public:
                 }
                 fr.matches.resize(need);
                 fr.flag_in_count = pf_active_; // (the gather rewrote part-local target ids on the device)
+                if (lf.is_hibf && translate(fr.matches, lf.user_to_target)) // user bin -> target, where the unpartitioned HIBF's path does it
+                    drop_unassigned(n, fr);
                 uint64_t moved = 0;
                 if (gn_gather_device_matches(lf.gather, nullptr, nullptr, nullptr, &moved) == GN_OK)
                     gathered_bytes_ += moved;
@@ -686,6 +690,7 @@ private:
         std::vector<Part> parts;  // one, or the column parts of a wide / partitioned flat filter
         size_t            home = 0; // a part on this worker's device (n_hashes / status are fetched from its stream)
         gn_gather*        gather = nullptr;
+        const std::vector<uint32_t>* user_to_target = nullptr; // a spread HIBF's (SharedFilter::user_to_target)
     };
 
     bool make_stream(Part& part, uint64_t reads, uint64_t bases, std::string& err)
@@ -723,6 +728,7 @@ private:
         {
             Logical lf;
             lf.is_hibf = sf.is_hibf;
+            lf.user_to_target = sf.is_hibf && sf.spread ? &sf.user_to_target : nullptr;
             auto const& copy = sf.spread ? sf.copies.at(0) : sf.copies.at(set_->unique_index(device_));
             for (size_t g = 0; g < copy.size(); ++g)
             {

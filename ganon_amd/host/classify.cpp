@@ -237,6 +237,13 @@ static bool ganon_classify(Config config)
             catch (std::exception const& e)
             {
                 std::cerr << "ERROR: loading ibf or tax files: " << e.what() << std::endl;
+                if (first_level) // (a filter that is refused before a read was looked at: the run leaves no empty .rep / .unc behind)
+                    for (auto* files : { &out_rep, &out_unc })
+                        for (auto& [prefix, file] : *files)
+                        {
+                            file.close();
+                            std::remove((config.output_prefix + prefix + "." + (files == &out_rep ? "rep" : "unc")).c_str());
+                        }
                 return false;
             }
         }

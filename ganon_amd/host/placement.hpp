@@ -3,6 +3,7 @@
 #pragma once
 
 #include "backend.hpp"
+#include "hibf_partition.hpp"
 #include "pinned_pool.hpp"
 
 namespace gnhost
@@ -23,7 +24,9 @@ constexpr uint64_t kPartWords = 512; // 32 768 bins: four wave slices of 16-byte
 // filter, from the filter's size and what the devices have left:
 //   * REPLICATED: a copy on every GPU in use (read-sharded classification, SURVEY 8e first bullet) -- entries of --device
 //     that name the same GPU share its copy;
-//   * PARTITIONED (flat IBF only): the reference loads a filter of any size (GanonClassify.cpp:949-986,1007-1039); one that
+//   * PARTITIONED BY SUBTREE (HIBF): one that does not fit is dealt to the devices root bin by root bin, each with its whole subtree
+//     (hibf_partition.hpp); every part is an HIBF of its own, and a read's matches are merged by user bin (gn_gather_create_merged);
+//   * PARTITIONED (flat IBF): the reference loads a filter of any size (GanonClassify.cpp:949-986,1007-1039); one that
 //     does not fit beside what a device already holds is cut by technical-bin range at target boundaries and its column
 //     parts are placed on different devices (SURVEY 8e second bullet, BASELINE config 5).  Every part is at most kPartWords
 //     wide, so a device may hold several.
@@ -37,6 +40,10 @@ struct DevPart
     int                   vdev   = 0;
     uint64_t              word_lo = 0, words = 0;
     std::vector<uint32_t> to_target; // device target id -> index into FilterMeta::targets (empty: the same)
+    // a subtree part of a spread HIBF (hibf_partition.hpp): the file's IBF -> the part's (-1: another part holds it; empty: the same),
+    // and the part's user bin -> the file's (strictly increasing: the key the merging gather sorts by)
+    std::vector<int32_t>  ibf_local;
+    std::vector<uint32_t> user_global;
 };
 
 struct SharedFilter
@@ -46,6 +53,7 @@ struct SharedFilter
     std::vector<uint64_t>             row_words;       // bin_words of every IBF as stored in the file
     // replicated: copies[u] = the filter's parts on unique device u; partitioned: copies[0] = all parts, in column order
     std::vector<std::vector<DevPart>> copies;
+    std::vector<uint32_t>             user_to_target; // spread HIBF: the file's user bin -> target index (applied after the merging gather)
 };
 
 inline uint64_t parse_bytes(const char* v)
@@ -142,14 +150,63 @@ public:
         note << "filter " << filters_.size() << " (" << (f.is_hibf ? "HIBF, " : "IBF, ") << bytes / double(1ull << 30) << " GiB): ";
         if (f.is_hibf)
         {
+            sf.is_hibf = true;
             if (!fits)
             {
-                err = "the HIBF (" + std::to_string(bytes >> 20) + " MiB) does not fit into the memory of one device beside the filters "
-                      "loaded before it; an HIBF cannot be partitioned by bin range (its levels are data dependent)";
-                return false;
+                // bin ranges of the whole tree cannot be cut (its levels are data dependent), but the root's bins with their subtrees can
+                std::vector<uint64_t> room;
+                for (auto const& v : vdev_)
+                    room.push_back(v.budget > v.used ? v.budget - v.used : 0);
+                HibfPlan plan = plan_hibf_partition(f, room, gn_hibf_row_stride_words);
+                if (plan.refusal.empty() && plan.parts.size() > 64) // GN_GATHER_MAX_PARTS
+                    plan.refusal = "the HIBF does not fit one device and cannot be partitioned into " + std::to_string(plan.parts.size()) + " parts (at most 64)";
+                if (!plan.refusal.empty())
+                {
+                    err = plan.refusal;
+                    return false;
+                }
+                sf.spread = true;
+                sf.user_to_target.assign(f.n_user_bins, 0xFFFFFFFFu);
+                for (size_t t = 0; t < f.targets.size(); ++t)
+                    sf.user_to_target[f.target_bins[t][0]] = (uint32_t)t;
+                sf.copies.push_back({});
+                note << "partitioned by subtree:";
+                for (auto& pp : plan.parts)
+                {
+                    std::vector<gn_ibf_desc>    descs;
+                    std::vector<const int64_t*> nx, bu;
+                    for (size_t i = 0; i < pp.shapes.size(); ++i)
+                    {
+                        auto& m = pp.shapes[i];
+                        descs.push_back(gn_ibf_desc{ nullptr, m.bin_size, m.bin_words, m.bins, (uint32_t)m.hash_funs, (uint32_t)m.hash_shift });
+                        nx.push_back(pp.next_ibf_id[i].data());
+                        bu.push_back(pp.bin_to_user[i].data());
+                    }
+                    DevPart part;
+                    part.device  = vdev_[pp.slot].device;
+                    part.vdev    = (int)pp.slot;
+                    part.word_lo = pp.word_lo;
+                    part.words   = pp.word_hi - pp.word_lo;
+                    if (gn_filter_upload_hibf(part.device, (uint32_t)descs.size(), descs.data(), nx.data(), bu.data(),
+                                              std::max<uint64_t>(pp.user_global.size(), 1), &part.f) != GN_OK)
+                    {
+                        err = gn_last_error();
+                        free_parts(sf);
+                        return false;
+                    }
+                    part.ibf_local.assign(f.shapes.size(), -1);
+                    for (size_t l = 0; l < pp.ibf_global.size(); ++l)
+                        part.ibf_local[pp.ibf_global[l]] = (int32_t)l;
+                    part.user_global = pp.user_global;
+                    for (uint32_t u : pp.user_global)
+                        part.to_target.push_back(sf.user_to_target[u]);
+                    vdev_[pp.slot].used += pp.bytes;
+                    note << " [root bins " << pp.bin_lo << "-" << pp.bin_hi - 1 << ", " << pp.ibf_global.size() << " IBFs, "
+                         << pp.bytes / double(1u << 20) << " MiB -> device " << part.device << "]";
+                    sf.copies[0].push_back(std::move(part));
+                }
             }
-            sf.is_hibf = true;
-            for (int d : uniq_)
+            for (int d : fits ? uniq_ : std::vector<int>())
             {
                 std::vector<gn_ibf_desc>    descs;
                 std::vector<const int64_t*> nx, bu;
@@ -175,9 +232,12 @@ public:
                 sf.copies.push_back({});
                 sf.copies.back().push_back(std::move(part));
             }
-            for (auto& v : vdev_)
-                v.used += bytes;
-            note << "replicated on " << uniq_.size() << " device(s)";
+            if (fits)
+            {
+                for (auto& v : vdev_)
+                    v.used += bytes;
+                note << "replicated on " << uniq_.size() << " device(s)";
+            }
         }
         else
         {
@@ -383,11 +443,21 @@ public:
         }
         for (auto& copy : sf.copies)
             for (auto& part : copy)
-                if (gn_filter_write_rows(part.f, sf.is_hibf ? ibf : 0, row_begin, n_rows, src, sf.row_words[ibf], part.word_lo) != GN_OK)
+            {
+                // a subtree part of an HIBF takes the rows of the IBFs it owns, and its words of the root's rows
+                uint32_t at = sf.is_hibf ? ibf : 0;
+                if (!part.ibf_local.empty())
+                {
+                    if (part.ibf_local[ibf] < 0)
+                        continue;
+                    at = (uint32_t)part.ibf_local[ibf];
+                }
+                if (gn_filter_write_rows(part.f, at, row_begin, n_rows, src, sf.row_words[ibf], ibf == 0 ? part.word_lo : 0) != GN_OK)
                 {
                     err = gn_last_error();
                     return false;
                 }
+            }
         return true;
     }
 

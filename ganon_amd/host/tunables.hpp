@@ -88,7 +88,7 @@ inline const KnobInfo& knob_info(Knob k)
         { "GANON_HOST_INFLATE_THREADS", "threads of the host's parallel inflater (default: twice the parser threads)" },
         { "GANON_HOST_INFLATE_CHUNK", "compressed bytes per chunk of the host's parallel inflater" },
         { "GANON_PARTITION_WORKERS", "workers that drive a level with a partitioned filter (default 2)" },
-        { "GANON_DEVICE_BUDGET", "bytes every --device entry may hold (tests: forces a partition on one GPU; e.g. 6G)" },
+        { "GANON_DEVICE_BUDGET", "bytes every --device entry may hold (tests: forces a partition on one GPU -- a flat IBF by bin range, an HIBF by subtree; e.g. 6G)" },
         { "GANON_DEVICE", "default for --device" },
         { "GANON_HIP_ABLATE", "the library's switch list (include/ganon_hip.h); the host adds sync=block when it names no sync mode" },
         { "GANON_HOST_FULL_TEARDOWN", "return from main normally (destructors, atexit handlers) instead of _Exit after the outputs are closed" },

@@ -103,7 +103,11 @@ int gn_filter_upload_ibf(int device, const gn_ibf_desc* ibf, const uint32_t* bin
 
 /* HIBF (raptor 3.0.1 layout, hierarchical_interleaved_bloom_filter.hpp:124-136,188):
  * next_ibf_id[i][b] and bin2userbin[i][b] (-1 = merged bin) for every bin b < ibfs[i].bins.
- * Reported target id = user bin index (ibf_bin_to_filename_position). */
+ * Reported target id = user bin index (ibf_bin_to_filename_position).
+ * A bin with bin2userbin == -1 AND next_ibf_id == -1 is ABSENT: it belongs to another part of an HIBF that is spread over
+ * several devices by subtree (below: gn_gather_create_merged).  It is never reported and never descended into, and
+ * gn_filter_finalize clears its bits in every row, so that rows streamed in with gn_filter_write_rows(word_lo) may carry
+ * the neighbours' bins of a boundary word.  (The reference has no such bins: it holds the whole tree in host memory.) */
 int gn_filter_upload_hibf(int device, uint32_t n_ibf, const gn_ibf_desc* ibfs, const int64_t* const* next_ibf_id,
                           const int64_t* const* bin2userbin, uint64_t n_user_bins, gn_filter** out);
 
@@ -316,6 +320,18 @@ int gn_stream_device_matches(gn_stream* s, const gn_match** d_matches, uint64_t*
  * first: then only survivors travel.  The result is what gn_fetch_batch would return for the unpartitioned filter. */
 typedef struct gn_gather gn_gather;
 int gn_gather_create(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, gn_gather** out);
+/* The same for an HIBF that does not fit one device and is spread BY SUBTREE: the reference's counting agent walks one tree in
+ * host memory (hierarchical_interleaved_bloom_filter.hpp:432-460) and select_matches(THIBF) reads the counts by user bin
+ * (GanonClassify.cpp:543-577).  A technical bin of the root is reported or descended into on its own count alone and everything
+ * below a merged bin is reached through it only, so the root's bins -- each with its whole subtree -- are dealt to the devices;
+ * every part is an HIBF of its own (gn_filter_upload_hibf with absent bins, a root of words [word_lo, word_hi) of the root's
+ * rows, user bins renumbered densely in ascending global id).  User bins are numbered by file position and laid out by size,
+ * so the parts' ids interleave: this gather MERGES a read's segments by translated id instead of putting them behind each
+ * other.  Preconditions: every target_map[i] is strictly increasing (NULL = the identity), every part's segment of a read
+ * ascends in part-local id (gn_fetch_batch order), translated ids of different parts are disjoint (equal ids: lower part
+ * first).  Result, per read: the union of the parts' records in ascending translated id -- for an HIBF what gn_fetch_batch
+ * of the unpartitioned filter gives.  gn_gather_run accepts streams on HIBFs only from a gather created here. */
+int gn_gather_create_merged(int device, uint32_t n_parts, const uint32_t* const* target_map, const uint32_t* n_map, gn_gather** out);
 /* streams[i] = part i's stream, all holding the same submitted batch (gn_submit_batch / gn_stream_classify) */
 int gn_gather_run(gn_gather* g, gn_stream* const* streams, uint32_t n_streams);
 /* The same over parts that are plain DEVICE buffers on the gather's device -- the receive buffers of a multi-process job
