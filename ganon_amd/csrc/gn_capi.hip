@@ -47,7 +47,7 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
     {
         const char* name;
         bool GnSwitches::* flag;
-    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"cand_select", &GnSwitches::cand_select},
+    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"lean_screen", &GnSwitches::lean_screen},     {"cand_select", &GnSwitches::cand_select},
                               {"csr_identity", &GnSwitches::csr_identity},   {"uniform_select", &GnSwitches::uniform_select},
                               {"run_select", &GnSwitches::run_select},       {"max_first", &GnSwitches::max_first},
                               {"const_nb", &GnSwitches::const_nb},           {"split_kernel", &GnSwitches::split_kernel},
@@ -965,6 +965,9 @@ extern "C" int gn_stream_create(gn_filter* f, uint32_t max_reads, uint64_t max_b
     ok(s->d_seg_off.alloc(nseg + 1));
     ok(s->d_deferred.alloc(max_reads));
     ok(s->d_mdeferred.alloc(max_reads));
+    // the screen-only fast kernel's list: every unit of a batch may land on it (a dense filter); unit numbers are 32 bits wide
+    if (!f->is_hibf && f->identity && f->ibf.h == 4 && f->geom.lw == 1 && (uint64_t)nseg <= 0xFFFFFFFFull)
+        ok(s->d_unit_list.alloc(nseg ? nseg : 1));
     size_t tmp1 = 0, tmp2 = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, s->d_slot_cnt.get(), s->d_slot_off.get(), (int)(max_reads + 1), s->st);
     gn_scan_counts(nullptr, tmp2, s->d_seg_count, s->d_seg_off, (int)(nseg + 1), s->st);
@@ -1279,6 +1282,8 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     p.max_blocks = (uint32_t)f->n_cu * 16u;
     // persistent grid = a whole number of resident rounds: 8-byte-lane variant holds 4 blocks per CU, 16-byte one 3
     p.max_blocks_fast = (uint32_t)f->n_cu * (f->geom.lw == 1 ? 8u : 6u);
+    p.max_blocks_lean = (uint32_t)f->n_cu * 10u; // (the screen-only kernel holds 5 blocks per CU)
+    p.max_blocks_list = p.max_blocks_fast;
     p.emit_probe = gn_sw().emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
     p.early_exit = gn_sw().early_exit ? 0u : 1u; // (bench.py's every-row measurement and the parity tests of the exit)
     p.skip_ctr   = s->d_ctr + 7;
@@ -1340,7 +1345,19 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
             GN_HIP(hipMemsetAsync(s->d_ctr + 72, 0, sizeof(unsigned long long), s->st));
             p.grab = s->d_ctr + 72;
         }
+        // the screen-only kernel where the screening instance <4,1,true,false,true> would run (gn_launch_fast_one; switch lean_screen):
+        // what it leaves goes to d_unit_list and is run by the launch that follows it
+        if (s->d_unit_list && !gn_sw().lean_screen)
+        {
+            GN_HIP(hipMemsetAsync(s->d_ctr + 73, 0, sizeof(unsigned long long), s->st));
+            p.unit_list_out  = s->d_unit_list;
+            p.unit_count_out = s->d_ctr + 73;
+            if (s->prev_unit_deferred != ~0ull && lo == 0 && hi == s->n_reads && !gn_sw().deferred_grids)
+                // a grid for twice the last batch's list (four units a block)
+                p.max_blocks_list = (uint32_t)std::min<uint64_t>(p.max_blocks_list, std::max<uint64_t>((uint64_t)f->n_cu, s->prev_unit_deferred / 2 + 1));
+        }
         GN_HIP(gn_launch_count_fast(p, f->geom, f->ibf.h, s->st));
+        p.unit_list_out = nullptr;
         p.grab       = nullptr; // (the generic kernel that takes the deferred reads hands out its rounds as before)
         p.work_list  = s->d_deferred;
         p.work_count = s->d_ctr + 4;
@@ -1683,6 +1700,7 @@ static int gn_finish(gn_stream* s)
             if (!s->f->is_hibf)
             {
                 s->prev_count_deferred = s->h_ctr[4];
+                s->prev_unit_deferred  = s->h_ctr[73];
                 if (!s->src)
                     s->prev_min_deferred = s->h_ctr[5];
             }
@@ -1966,5 +1984,16 @@ extern "C" int gn_stream_timings(gn_stream* s, gn_timings* t)
     if (s->cmp_timed && hipEventSynchronize(s->ev_cmp[1]) == hipSuccess)
         hipEventElapsedTime(&tm.ms_compact, s->ev_cmp[0], s->ev_cmp[1]);
     *t = tm;
+    return GN_OK;
+}
+
+extern "C" int gn_stream_screen_deferred(gn_stream* s, uint64_t* units)
+{
+    if (!s || !units)
+        return gn_fail(GN_EINVAL, "null argument");
+    int rc = gn_finish(s);
+    if (rc)
+        return rc;
+    *units = s->f->is_hibf ? 0ull : (uint64_t)s->h_ctr[73]; // (the batch's last count range)
     return GN_OK;
 }

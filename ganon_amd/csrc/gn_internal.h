@@ -19,8 +19,8 @@
 #define GN_PF_MAX_JOINT 16   // filters of one hierarchy level in a joint filter_matches pre-pass, per device
 #define GN_PF_MAX_DEVICES 16 // devices a joint pass spans (column parts of a bin-range partitioned filter)
 #define GN_LONG_BLOCKS 128u // workgroups (and uint32 count slabs) of the long-read kernel
-#define GN_NCTR 73 // device counters: [0] match cursor [2] algo bytes [3] hibf work [4] count-deferred [5] minimiser-deferred
-                   // [6] exact match total [8..71] total-hashes shards [72] unit cursor of the fast count kernel
+#define GN_NCTR 74 // device counters: [0] match cursor [2] algo bytes [3] hibf work [4] count-deferred [5] minimiser-deferred
+                   // [6] exact match total [8..71] total-hashes shards [72] unit cursor of the fast count kernel [73] units the screen-only fast kernel left to its list
 
 // ---- switches ---------------------------------------------------------------------------------
 // The ONE place the library reads its environment: $GANON_HIP_ABLATE, a comma list of the names below, parsed once when
@@ -32,6 +32,7 @@ struct GnSwitches
     // count + select (flat IBF)
     bool early_exit = false;      // fast kernel: fetch every row (no exact early exit)
     bool row_screen = false;      // fast kernel: no two-row screen in front of the exit (every read takes the unscreened flow)
+    bool lean_screen = false;     // fast kernel: no screen-only kernel + launch over its list (the screening instance takes every unit, one launch)
     bool cand_select = false;     // generic kernel: scan every target instead of the candidate-driven select
     bool csr_identity = false;    // split-bin kernel family: treat an ordered CSR map as a general one
     bool uniform_select = false;  // ... no packed select for equal bins-per-target
@@ -136,6 +137,14 @@ struct GnCountParams
     const unsigned long long* work_count;
     uint32_t*                 work_list_out;
     unsigned long long*       work_count_out;
+    // unit list (unit = read * wpr + slice, counted from read_begin): what the screen-only fast kernel leaves to the instance <4,1,true>
+    // (its output; that instance's input, nullptr = every unit of the range)
+    const uint32_t*           unit_list;
+    const unsigned long long* unit_count;
+    uint32_t*                 unit_list_out;
+    unsigned long long*       unit_count_out;
+    uint32_t                  max_blocks_lean; // screen-only fast kernel: persistent grid size (five blocks a CU)
+    uint32_t                  max_blocks_list; // ... and the grid of the launch over its list
     uint32_t                  max_blocks; // generic kernel: persistent grid size
     uint32_t                  max_blocks_fast; // fast kernel: persistent grid size
     uint32_t                  emit_probe;      // fast kernel: GnSwitches::emit_probe (0 in the product)
@@ -429,6 +438,7 @@ struct gn_stream
     GnDev<uint32_t>     d_seg_count;
     GnDev<uint64_t>     d_seg_off;   // n*wpr+1 exclusive scan of seg_count
     GnDev<uint32_t>     d_deferred;  // reads the fast count kernel left to the generic one
+    GnDev<uint32_t>     d_unit_list; // units (read * wpr + slice) the screen-only fast kernel left to the instance without a screen; empty: that kernel is not for this filter
     GnDev<uint32_t>     d_mdeferred; // reads the lane-per-read minimiser kernel left to the wave-per-read one
     GnDev<uint8_t>      d_scan_tmp;
     size_t              scan_tmp_bytes = 0;
@@ -479,7 +489,7 @@ struct gn_stream
     bool     ctr_copied = false; // the batch's counters are on their way to h_ctr / pf.h_ctr (queued behind its last kernel)
     // reads the previous batch left to the deferred launches (count stage, minimiser stage): their lists are usually empty and a
     // chip-filling persistent grid that finds nothing costs 0.1-0.2 ms per launch; ~0: unknown
-    uint64_t prev_count_deferred = ~0ull, prev_min_deferred = ~0ull;
+    uint64_t prev_count_deferred = ~0ull, prev_min_deferred = ~0ull, prev_unit_deferred = ~0ull;
     uint32_t k = 0, w = 0;
     double   rel_cutoff = 0;
     uint64_t n_matches = 0;

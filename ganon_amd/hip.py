@@ -23,7 +23,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_stream_upload_reads", "gn_stream_minimisers", "gn_stream_classify", "gn_submit_batch", "gn_stream_sync", "gn_fetch_batch", "gn_stream_set_postfilter",
                "gn_fetch_postfilter", "gn_streams_postfilter_joint", "gn_stream_set_long_reads", "gn_stream_device_matches",
                "gn_stream_distinct_hashes", "gn_filter_emplace_split", "gn_stream_fetch_hashes", "gn_stream_dense_counts",
-               "gn_stream_timings", "gn_gather_create", "gn_gather_create_merged", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
+               "gn_stream_timings", "gn_stream_screen_deferred", "gn_gather_create", "gn_gather_create_merged", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
                "gn_gather_destroy", "gn_device_memory", "gn_hibf_row_stride_words", "gn_gather_run_buffers", "gn_stream_device_offsets", "gn_stream_hibf_levels", "gn_stream_hibf_level_lines", "gn_stream_classify_shared",
                "gn_stream_upload_fastq", "gn_stream_fastq_index", "gn_stream_fastq_keep", "gn_stream_fastq_records",
                "gn_peer_stats", "gn_stream_upload_text", "gn_stream_upload_text_pair", "gn_stream_text_pair_index", "gn_stream_text_pair_records2",
@@ -177,6 +177,7 @@ def load_library():
     L.gn_sketches_pair_table.argtypes = [vp, vp, u32, vp]
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
+    L.gn_stream_screen_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
     L.gn_gather_create_merged.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
     L.gn_gather_run.argtypes = [vp, C.POINTER(vp), u32]
@@ -950,6 +951,12 @@ class HipStream:
         return dict(ms_minimiser=t.ms_minimiser, ms_count=t.ms_count, ms_total=t.ms_total, n_hashes=t.n_hashes,
                     algo_bytes=t.algo_bytes, n_matches=t.n_matches, n_count_launches=t.n_count_launches,
                     fetched_bytes=t.fetched_bytes, ms_compact=t.ms_compact)
+
+    def screen_deferred(self) -> int:
+        """units of the last batch the fast count kernel's screen-only launch left to the launch after it (gn_stream_screen_deferred)"""
+        n = C.c_uint64(0)
+        _check(load_library().gn_stream_screen_deferred(self._h, C.byref(n)))
+        return int(n.value)
 
     def hibf_levels(self):
         """per tree level of the last HIBF batch: [dict(ms, algo_bytes, table_bytes, row_bytes, line_bytes)] (gn_stream_hibf_levels / _level_lines)"""
