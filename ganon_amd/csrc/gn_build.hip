@@ -4,11 +4,18 @@
 //   gn_filter_emplace_split    insert a target's hashes into its run of technical bins, equal shares per bin
 //                              (create_bin_map_hash :619-653 + build :655-698: hash i of the target goes to bin
 //                              first_bin + i / hashes_per_bin)
+//   gn_filter_emplace_runs_window  the same rule for many runs in one call, into a filter that stands for a window of the rows of a
+//                              larger one: one launch per staging chunk, uploads under the kernels (a flat filter built in row slabs)
 // HBM-bound integer work: a radix sort (hipCUB) over the hash array, a unique pass, an atomic-OR scatter.
 #include "gn_internal.h"
 #include <hipcub/hipcub.hpp>
 
 #include "gn_build_row.h" // gn_build_row: seqan3::interleaved_bloom_filter's hash_and_fit
+#include "gn_emplace_window.h"
+
+#include <algorithm>
+#include <string.h>
+#include <vector>
 
 // hashes live in per-read slots (one slot per window, gn_slot_count_kernel); read r used the first nh[r] of them
 __global__ void gn_pack_hashes_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ slot_off,
@@ -161,6 +168,165 @@ extern "C" int gn_filter_emplace_split(gn_filter* f, const uint64_t* hashes, uin
         GN_HIP(hipGetLastError());
         GN_HIP(hipStreamSynchronize(f->load_st)); // (the staging buffer is reused, and `hashes` may be pageable)
     }
+    return GN_OK;
+}
+
+// ---- gn_filter_emplace_runs_window: many runs into a slab of rows ------------------------------------------------------------------
+// The filter stands for rows [row_begin, row_begin + S) of a filter of total_rows rows (`ganon-build --device-memory`, `--device a,b`:
+// build_slabs.cpp).  A hash's rows depend on the hash and on the WHOLE filter's row count alone, so every slab is filled from the same
+// hash sets and takes the bits of the rows it holds.
+typedef __attribute__((address_space(1))) unsigned long long GnGlobalWord;
+
+// One wave per item, as gn_emplace_path_kernel (gn_build_hibf.hip): the item index goes through readfirstlane so that item and run are
+// read with scalar loads into SGPRs; the lane's hashes are loaded first, from then on the wave only issues no-return atomic ORs.  The
+// item's first bin is divided out once for the wave (gn_window_item_bin); a row outside the window costs its hash and one compare.
+__global__ __launch_bounds__(256) void gn_emplace_window_kernel(uint64_t* rows, uint64_t S_total, uint32_t shift, uint32_t W, uint32_t h, uint32_t row_begin,
+                                                                uint32_t n_rows, const uint64_t* __restrict__ stage, const GnRunItem* __restrict__ items,
+                                                                uint32_t n_items, const GnRunDev* __restrict__ runs)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t  lane = threadIdx.x & 63u;
+    const GnRunItem it   = items[item];
+    const GnRunDev  run  = runs[it.run];
+    uint64_t        v[GN_WIN_PER_LANE];
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+    }
+    const uint64_t b0   = it.begin / run.per_bin; // (wave-uniform: once per item)
+    const uint64_t r0   = it.begin - b0 * run.per_bin;
+    const uint32_t bin0 = run.first_bin + (uint32_t)b0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        if (q >= it.cnt)
+            continue;
+        const uint32_t bin  = gn_window_item_bin(bin0, r0, q, run.per_bin);
+        GnGlobalWord*  word = (GnGlobalWord*)rows + (bin >> 6);
+        const uint64_t bit  = 1ULL << (bin & 63);
+        for (uint32_t i = 0; i < h; ++i)
+        {
+            uint32_t local;
+            if (gn_window_local(gn_build_row(v[j], i, shift, S_total), row_begin, n_rows, &local))
+                (void)__hip_atomic_fetch_or(word + (uint64_t)local * W, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// Hashes of a staging chunk when the caller names none: 8 MiB, two of them page-locked and two on the device.  Page-locking is paid per
+// call: one insert of 287 M hashes into a quarter of a filter's rows took 0.118 s with chunks of 4 Mi hashes, 0.080 s with 1 Mi, 0.098 s
+// with 256 Ki and 0.155 s with 64 Ki (launches and waits take over).
+#define GN_WIN_CHUNK (1ull << 20)
+namespace
+{
+struct GnStreamPair
+{
+    hipStream_t st[2] = { nullptr, nullptr };
+    ~GnStreamPair()
+    {
+        for (hipStream_t s : st)
+            if (s)
+                (void)hipStreamDestroy(s);
+    }
+};
+struct GnWindowStage // everything a call holds; freed when the call returns
+{
+    GnStreamPair        streams;
+    GnPinned<uint64_t>  h_stage[2];
+    GnPinned<GnRunItem> h_items[2];
+    GnDev<uint64_t>     d_stage[2];
+    GnDev<GnRunItem>    d_items[2];
+    GnDev<GnRunDev>     d_runs;
+};
+} // namespace
+
+// Chunk c goes through buffer and stream c & 1: its hashes are gathered into the page-locked buffer, copied and inserted on that
+// stream, while chunk c - 1 is still on the other one -- the upload of a chunk runs under the kernel of the one before.  A buffer is
+// written again only after its stream has been waited for.
+static int gn_runs_window_rounds(gn_filter* f, GnWindowStage& g, const uint64_t* const* runs, const uint64_t* run_sizes, uint32_t n_runs, uint64_t total_rows,
+                                 uint64_t row_begin, uint64_t chunk, uint64_t cap_items)
+{
+    const GnIbfHost&       ib = f->ibf;
+    std::vector<GnRunItem> items;
+    GnRunCursor            cur;
+    for (uint32_t c = 0;; ++c)
+    {
+        const uint32_t b = c & 1u;
+        GN_HIP(hipStreamSynchronize(g.streams.st[b]));
+        const uint64_t taken = gn_window_next_chunk(run_sizes, n_runs, cur, chunk, cap_items, items);
+        if (taken == 0)
+            return GN_OK;
+        // (one thread gathers: with chunks of 4 Mi hashes four of them made a pass over a slab 5 % shorter, within the spread of the runs)
+        for (const GnRunItem& it : items)
+            memcpy(g.h_stage[b] + it.stage_at, runs[it.run] + it.begin, (size_t)it.cnt * 8);
+        memcpy(g.h_items[b].get(), items.data(), items.size() * sizeof(GnRunItem));
+        GN_HIP(hipMemcpyAsync(g.d_stage[b], g.h_stage[b], taken * 8, hipMemcpyHostToDevice, g.streams.st[b]));
+        GN_HIP(hipMemcpyAsync(g.d_items[b], g.h_items[b], items.size() * sizeof(GnRunItem), hipMemcpyHostToDevice, g.streams.st[b]));
+        const uint32_t n_items = (uint32_t)items.size();
+        hipLaunchKernelGGL(gn_emplace_window_kernel, dim3((n_items + 3) / 4), dim3(256), 0, g.streams.st[b], ib.d_rows.get(), total_rows,
+                           (uint32_t)__builtin_clzll(total_rows), (uint32_t)ib.Ws, ib.h, (uint32_t)row_begin, (uint32_t)ib.S, (const uint64_t*)g.d_stage[b],
+                           (const GnRunItem*)g.d_items[b], n_items, (const GnRunDev*)g.d_runs);
+        GN_HIP(hipGetLastError());
+    }
+}
+
+extern "C" int gn_filter_emplace_runs_window(gn_filter* f, const uint64_t* const* runs, const uint64_t* run_sizes, const uint32_t* first_bin,
+                                             const uint64_t* hashes_per_bin, uint32_t n_runs, uint64_t total_rows, uint64_t row_begin, uint64_t chunk_hashes)
+{
+    static const char* const who = "gn_filter_emplace_runs_window";
+    if (!f || f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs a flat IBF filter", who);
+    const GnIbfHost& ib = f->ibf;
+    if (total_rows == 0 || total_rows > 0xFFFFFFFFull)
+        return gn_fail(GN_ERANGE, "%s: a filter of %llu rows, 1 .. 2^32 - 1 are supported", who, (unsigned long long)total_rows);
+    if (row_begin > total_rows || ib.S > total_rows - row_begin)
+        return gn_fail(GN_EINVAL, "%s: rows %llu .. %llu of a filter of %llu rows", who, (unsigned long long)row_begin, (unsigned long long)(row_begin + ib.S),
+                       (unsigned long long)total_rows);
+    if (n_runs == 0)
+        return GN_OK;
+    if (!runs || !run_sizes || !first_bin || !hashes_per_bin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    // every bin a hash can reach is checked before anything is launched (the local row is below S by the window test)
+    std::vector<GnRunDev> dev(n_runs);
+    uint64_t              total = 0;
+    for (uint32_t r = 0; r < n_runs; ++r)
+    {
+        dev[r] = GnRunDev{ hashes_per_bin[r] ? hashes_per_bin[r] : 1, first_bin[r], 0 };
+        if (run_sizes[r] == 0)
+            continue;
+        if (!runs[r] || hashes_per_bin[r] == 0)
+            return gn_fail(GN_EINVAL, "%s: run %u: bad argument", who, r);
+        if ((uint64_t)first_bin[r] + (run_sizes[r] - 1) / hashes_per_bin[r] >= ib.B)
+            return gn_fail(GN_EINVAL, "%s: run %u: bins %u.. exceed the filter's %llu bins", who, r, first_bin[r], (unsigned long long)ib.B);
+        total += run_sizes[r];
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    const uint64_t chunk     = std::min<uint64_t>(chunk_hashes ? chunk_hashes : GN_WIN_CHUNK, total);
+    const uint64_t cap_items = chunk / 64 + 16; // (a chunk of many short runs closes at this many items instead of at `chunk` hashes)
+    GnWindowStage  g;
+    for (int b = 0; b < 2; ++b)
+    {
+        GN_HIP(hipStreamCreateWithFlags(&g.streams.st[b], hipStreamNonBlocking));
+        GN_HIP(g.h_stage[b].alloc(chunk));
+        GN_HIP(g.h_items[b].alloc(cap_items));
+        GN_HIP(g.d_stage[b].alloc(chunk));
+        GN_HIP(g.d_items[b].alloc(cap_items));
+    }
+    GN_HIP(g.d_runs.upload(dev.data(), dev.size()));
+    const int rc = gn_runs_window_rounds(f, g, runs, run_sizes, n_runs, total_rows, row_begin, chunk, cap_items);
+    // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
+    const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
+    if (rc != GN_OK)
+        return rc;
+    GN_HIP(e0);
+    GN_HIP(e1);
     return GN_OK;
 }
 

@@ -34,7 +34,8 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_ibf_hash_constants", "gn_inflate_set_turns", "gn_inflate_handoff",
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
                "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_fold_ibf", "gn_filter_extend_path",
-               "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table"]
+               "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table",
+               "gn_filter_emplace_runs_window"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -161,6 +162,7 @@ def load_library():
     L.gn_stream_fetch_hashes.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.gn_stream_distinct_hashes.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_split.argtypes = [vp, vp, u64, u32, u64]
+    L.gn_filter_emplace_runs_window.argtypes = [vp, vp, vp, vp, vp, u32, u64, u64, u64]
     L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
     L.gn_filter_probe_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
@@ -600,6 +602,31 @@ class HipFilter:
         bins = np.ascontiguousarray(bins, dtype=np.uint32)
         assert len(hashes) == len(bins)
         _check(load_library().gn_filter_emplace_ibf(self._h, ibf_idx, _p(hashes), _p(bins), len(hashes)))
+
+    @classmethod
+    def ibf_storage(cls, bins: int, bin_size: int, hash_funs: int, device: int = 0) -> "HipFilter":
+        """an empty storage-only flat filter (no bin map, as `ganon-build` creates it): bits can be inserted and read back"""
+        d = _desc(None, bins, bin_size, hash_funs)
+        h = C.c_void_p()
+        _check(load_library().gn_filter_upload_ibf(device, C.byref(d), None, 0, C.byref(h)))
+        return cls(h, bins=[bins])
+
+    def emplace_split(self, hashes: np.ndarray, first_bin: int, hashes_per_bin: int) -> None:
+        """gn_filter_emplace_split: hash i into bin first_bin + i // hashes_per_bin"""
+        hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+        _check(load_library().gn_filter_emplace_split(self._h, _p(hashes), len(hashes), first_bin, hashes_per_bin))
+
+    def emplace_runs_window(self, runs: Sequence[np.ndarray], first_bins, hashes_per_bin, total_rows: int, row_begin: int,
+                            chunk_hashes: int = 0) -> None:
+        """gn_filter_emplace_runs_window: this filter stands for rows [row_begin, row_begin + its rows) of a filter of total_rows rows;
+        hash i of runs[r] belongs to bin first_bins[r] + i // hashes_per_bin[r] and sets the bits of its rows inside that window"""
+        runs = [np.ascontiguousarray(a, dtype=np.uint64) for a in runs]
+        ptrs = (C.c_void_p * max(len(runs), 1))(*[a.ctypes.data for a in runs])
+        sizes = np.array([len(a) for a in runs], dtype=np.uint64)
+        first = np.ascontiguousarray(first_bins, dtype=np.uint32)
+        per = np.ascontiguousarray(hashes_per_bin, dtype=np.uint64)
+        assert len(first) == len(per) == len(runs)
+        _check(load_library().gn_filter_emplace_runs_window(self._h, ptrs, _p(sizes), _p(first), _p(per), len(runs), total_rows, row_begin, chunk_hashes))
 
     def emplace_path(self, sets: Sequence[np.ndarray], paths: np.ndarray) -> None:
         """gn_filter_emplace_path: sets[s] (ascending uint64) along paths[s] (PATH_DTYPE, shape [len(sets), depth]) of an HIBF"""

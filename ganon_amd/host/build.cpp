@@ -10,7 +10,8 @@
 // The device does what is data-parallel: sequences are cut into overlapping pieces (every window of a sequence lies in one
 // piece), the classify-side minimiser kernels hash them, a radix sort + unique gives the file's hash SET
 // (gn_stream_distinct_hashes), the filter is created empty in HBM, filled by an atomic-OR scatter
-// (gn_filter_emplace_split) and streamed to the file.  The host parses FASTA, keeps the hash sets (RAM, not `.min` files:
+// (gn_filter_emplace_runs_window) and streamed to the file -- whole when it fits what a device may hold, otherwise in slabs of rows
+// over the entries of --device (build_slabs.cpp).  The host parses FASTA, keeps the hash sets (RAM, not `.min` files:
 // --tmp-output-folder is accepted and validated, nothing is written there) and does the sizing arithmetic.
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
 //
@@ -91,6 +92,16 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
             std::cerr << m << std::endl;
         return false;
     };
+    // a build in row slabs or over several devices is the flat build's: refused here, before any device call
+    for (const auto& [on, mode] : { std::pair<bool, const char*>{ c.update_given, "--update" }, { c.verify_given, "--verify-index" }, { c.hibf, "--hibf" } })
+    {
+        if (on && c.device_memory_given)
+            return say(std::string("--device-memory cannot be used with ") + mode + " (only a flat .ibf is built in row slabs)");
+        if (on && c.devices.size() > 1)
+            return say(std::string("--device takes one device with ") + mode + " (only a flat .ibf is built over a device list)");
+    }
+    if (c.device_memory_given && c.device_memory == 0)
+        return say("--device-memory has to be > 0");
     if (c.tmax_given && !c.hibf)
         return say("--tmax needs --hibf");
     if (c.layout_given && !c.hibf)
@@ -200,6 +211,15 @@ void print_config(const Config& c) // Config.hpp:110-133
               << "--threads           " << c.threads << '\n'
               << "--verbose           " << c.verbose << '\n'
               << "--quiet             " << c.quiet << '\n';
+    if (c.devices.size() > 1)
+    {
+        std::cerr << "--device            ";
+        for (size_t i = 0; i < c.devices.size(); ++i)
+            std::cerr << (i ? "," : "") << c.devices[i];
+        std::cerr << '\n';
+    }
+    if (c.device_memory_given)
+        std::cerr << "--device-memory     " << c.device_memory << '\n';
     if (c.hibf)
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
     if (c.layout_given)
@@ -233,7 +253,12 @@ const char* kHelp =
     "  -y, --min-length arg         min. sequence length (bp) to keep. 0 to keep all. Default: 0\n"
     "  -m, --tmp-output-folder arg  Folder to write temporary files (accepted; this build keeps the hashes in memory)\n"
     "  -t, --threads arg            Number of threads (parser threads, one device stream each)\n"
-    "      --device arg             HIP device index. Default: 0\n"
+    "      --device arg             HIP device index. Default: 0.  A list a,b,... (an index may repeat) deals the row slabs of a flat\n"
+    "                               filter to its entries, one worker each, and the hashing threads to the devices; not with --hibf\n"
+    "      --device-memory arg      most bytes of filter rows held on an entry of --device at one time.  A flat filter larger than\n"
+    "                               that is filled in slabs of rows, each one more pass over the hash sets (which stay in host\n"
+    "                               memory), and written slab by slab: the same file.  Default: what the device has free when\n"
+    "                               filling starts, less staging and a reserve, shared among the entries that name it; not with --hibf\n"
     "      --hibf                   Write a hierarchical filter (raptor 3.0.1 index, one user bin per target) sized from\n"
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
@@ -326,7 +351,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -406,8 +431,26 @@ int parse_args(int argc, char** argv, Config& c)
             c.tmp_output_folder = vals["--tmp-output-folder"];
         if (vals.count("--threads"))
             c.threads = (uint16_t)u("--threads", 65535);
-        if (vals.count("--device"))
-            c.device = (int)u("--device", 1 << 20);
+        if (vals.count("--device")) // one index, or a list a,b,...
+        {
+            c.devices.clear();
+            std::istringstream list(vals["--device"]);
+            for (std::string e; std::getline(list, e, ',');)
+            {
+                size_t pos = 0;
+                if (e.empty() || e[0] == '-' || e[0] == '+')
+                    throw std::invalid_argument("--device");
+                const uint64_t x = std::stoull(e, &pos);
+                if (pos != e.size() || x > (1u << 20))
+                    throw std::invalid_argument("--device");
+                c.devices.push_back((int)x);
+            }
+            if (c.devices.empty() || vals["--device"].back() == ',')
+                throw std::invalid_argument("--device");
+            c.device = c.devices[0];
+        }
+        if (vals.count("--device-memory"))
+            c.device_memory = u("--device-memory", ~0ull), c.device_memory_given = true;
         c.verbose = vals.count("--verbose") && vals["--verbose"] != "false";
         c.quiet   = vals.count("--quiet") && vals["--quiet"] != "false";
         c.extend  = vals.count("--extend") && vals["--extend"] != "false";
@@ -469,12 +512,12 @@ std::vector<Target> read_input_file(const Config& c, Totals& totals)
 }
 
 // count_hashes (:184-249) for the targets this thread draws from the shared cursor
-void hash_targets(const Config& c, std::vector<Target>& targets, std::atomic<size_t>& next, Totals& totals, std::string& fatal,
+void hash_targets(const Config& c, int device, std::vector<Target>& targets, std::atomic<size_t>& next, Totals& totals, std::string& fatal,
                   std::mutex& log_mutex)
 {
     try
     {
-        gnhost::Hasher    hasher(c.device, c.kmer_size, c.window_size);
+        gnhost::Hasher    hasher(device, c.kmer_size, c.window_size);
         std::string       ids;
         gnhost::ByteBuf   seq;
         for (;;)
@@ -548,8 +591,9 @@ bool run(Config c)
     int n_dev = 0;
     if (gn_device_count(&n_dev) != GN_OK || n_dev <= 0)
         return fail(std::string("no usable MI355X/HIP device (") + gn_last_error() + "); ganon-build has no CPU fallback");
-    if (c.device >= n_dev)
-        return fail("--device " + std::to_string(c.device) + " does not exist (" + std::to_string(n_dev) + " visible)");
+    for (int d : c.devices)
+        if (d >= n_dev)
+            return fail("--device " + std::to_string(d) + " does not exist (" + std::to_string(n_dev) + " visible)");
 
     Totals              totals;
     const bool          remove_only = (c.remove_given || c.fold_given) && c.input_file.empty();
@@ -571,7 +615,7 @@ bool run(Config c)
         std::string              fatal;
         std::mutex               log_mutex;
         for (unsigned i = 0; i < nt; ++i)
-            th.emplace_back(hash_targets, std::cref(c), std::ref(targets), std::ref(next), std::ref(per[i]), std::ref(fatal),
+            th.emplace_back(hash_targets, std::cref(c), c.devices[i % c.devices.size()], std::ref(targets), std::ref(next), std::ref(per[i]), std::ref(fatal),
                             std::ref(log_mutex));
         for (auto& t : th)
             t.join();
@@ -638,31 +682,8 @@ bool run(Config c)
                   << " hash function(s): --filter-size / --max-fp do not fit " << targets.size() << " target(s)" << std::endl;
         return false;
     }
-    filling.start();
-    gnhost::OwnedFilter flt = gnhost::upload_ibf(c.device, p.n_bins, p.bin_size_bits, p.hash_functions, nullptr, 0); // storage only: no bin map
-    if (!flt)
-        return fail(gn_last_error());
-    {
-        uint32_t first_bin = 0;
-        for (size_t t = 0; t < targets.size(); ++t)
-        {
-            const uint64_t n = targets[t].hashes.size();
-            if (n == 0)
-                continue;
-            if (gn_filter_emplace_split(flt.get(), targets[t].hashes.data(), n, first_bin, shares[t]) != GN_OK)
-                return fail(gn_last_error());
-            first_bin += (uint32_t)((n + shares[t] - 1) / shares[t]);
-        }
-    }
-    filling.stop();
-
-    writing.start();
-    std::string err;
-    const bool  saved = save_filter(c, flt.get(), p, targets, bins, err);
-    flt.reset();
-    if (!saved)
-        return fail(err);
-    writing.stop();
+    if (!fill_and_save_flat(FlatFill{ c, p, targets, bins, shares }, filling, writing))
+        return false;
     whole.stop();
 
     if (!c.quiet)

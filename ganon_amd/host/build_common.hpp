@@ -33,7 +33,10 @@ struct Config // Config.hpp:10-27
     uint64_t    min_length = 0;
     uint16_t    threads = 1;
     bool        verbose = false, quiet = false;
-    int         device = 0; // (not in the reference: which GPU)
+    int         device = 0; // (not in the reference: which GPU; the first entry of `devices`)
+    std::vector<int> devices = { 0 }; // (--device a,b,...: the flat build deals row slabs to the entries; an entry may repeat)
+    uint64_t    device_memory = 0;    // (--device-memory: most bytes of filter rows on a list entry at one time; 0 = from what is free)
+    bool        device_memory_given = false;
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
     bool        tmax_given = false, filter_size_given = false;
@@ -191,6 +194,22 @@ bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std:
                  std::string& err);
 bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions,
                const std::vector<std::vector<std::string>>& bin_path, const std::vector<std::string>& user_files, std::string& err);
+// the flat .ibf in pieces, for a build in row slabs: the header and a file of full size, whose descriptor (>= 0; the caller closes it) and
+// payload offset come back; then rows [0, n_rows) of a slab filter to byte `at` of the file
+int  open_filter(const Config& c, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins, uint64_t& payload_at,
+                 std::string& err);
+bool save_slab(int fd, gn_filter* flt, uint64_t n_rows, uint64_t row_bytes, uint64_t at, gnhost::PinnedBlock& stage, std::string& err);
+
+// build_slabs.cpp: the bit matrix of a flat filter, filled slab by slab over c.devices and written as it goes
+struct FlatFill
+{
+    const Config&               c;
+    const IbfParams&            p;
+    const std::vector<Target>&  targets;
+    const std::vector<BinSpan>& bins;
+    const std::vector<uint64_t>& shares; // hashes per bin of each target (lay_out_bins)
+};
+bool fill_and_save_flat(const FlatFill& w, Lap& filling, Lap& writing);
 
 // the modes, after the inputs are hashed (build.cpp: run)
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting);   // build_hibf.cpp

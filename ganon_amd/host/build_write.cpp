@@ -109,11 +109,9 @@ bool write_rows(int fd, gn_filter* flt, uint32_t ibf, uint64_t n_rows, uint64_t 
 
 } // namespace
 
-// save_filter (:251-288): header from the host, the bit matrix streamed out of HBM
-bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins,
-                 std::string& err)
+// the flat file's header: IBFConfig, hashes_count_std, bin_map, then the IBF's own fields up to the bit vector's size
+static void filter_header(Writer& w, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins)
 {
-    Writer w;
     for (int v : kVersionTuple)
         w.raw<int32_t>(v);
     w.raw<uint64_t>(p.n_bins);
@@ -138,6 +136,14 @@ bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std:
         w.str(targets[bins[b].target].name);
     }
     ibf_header(w, p.n_bins, p.bin_size_bits, p.hash_functions);
+}
+
+// save_filter (:251-288): header from the host, the bit matrix streamed out of HBM
+bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins,
+                 std::string& err)
+{
+    Writer w;
+    filter_header(w, p, targets, bins);
     const int fd = ::open(c.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0)
     {
@@ -161,6 +167,46 @@ bool save_filter(const Config& c, gn_filter* flt, const IbfParams& p, const std:
     }
     ::close(fd);
     return ok;
+}
+
+// The same file for a build in row slabs: the header, and the file extended to its full size so that every slab's rows have their
+// place (payload_at + row_begin * row_bytes) whichever slab is written first.  -1: `err` says why.
+int open_filter(const Config& c, const IbfParams& p, const std::vector<Target>& targets, const std::vector<BinSpan>& bins, uint64_t& payload_at,
+                std::string& err)
+{
+    Writer w;
+    filter_header(w, p, targets, bins);
+    payload_at   = w.buf.size();
+    const int fd = ::open(c.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0)
+    {
+        err = "cannot write " + c.output_file;
+        return -1;
+    }
+    if (!pwrite_all(fd, w.buf.data(), w.buf.size(), 0) || ::ftruncate(fd, (off_t)(payload_at + p.bin_size_bits * row_bytes_of(p.n_bins))) != 0)
+    {
+        err = "write error on " + c.output_file;
+        ::close(fd);
+        return -1;
+    }
+    return fd;
+}
+
+// rows [0, n_rows) of a slab's filter to byte `at` of the file; `stage` is the caller's (one per worker) and grows to a chunk
+bool save_slab(int fd, gn_filter* flt, uint64_t n_rows, uint64_t row_bytes, uint64_t at, PinnedBlock& stage, std::string& err)
+{
+    if (!stage.reserve(chunk_rows(n_rows, row_bytes) * row_bytes))
+    {
+        err = gnhost::hip_error();
+        return false;
+    }
+    if (!write_rows(fd, flt, 0, n_rows, row_bytes, at, stage.get(), 8, err))
+    {
+        if (err.empty())
+            err = "write error on the output file";
+        return false;
+    }
+    return true;
 }
 
 // The raptor 3.0.1 index (reader: GanonClassify.cpp:875-938 with hibf.hpp:163-169,293-298), field for field what

@@ -408,6 +408,17 @@ int gn_reassign_free(gn_reassign* g);
  * run of bins with equal shares, create_bin_map_hash (:619-653) + build (:655-698). */
 int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t cap, uint64_t* n_distinct);
 int gn_filter_emplace_split(gn_filter* f, const uint64_t* hashes, uint64_t n, uint32_t first_bin, uint64_t hashes_per_bin);
+/* gn_filter_emplace_runs_window: the insert of build (/root/reference/src/ganon-build/GanonBuild.cpp:655-698) for a filter that is
+ * built in slabs of rows.  `f` is a storage-only flat filter of n rows that stands for rows [row_begin, row_begin + n) of a filter of
+ * total_rows rows (1 .. 2^32 - 1).  Run r is runs[r][0 .. run_sizes[r]) in host memory; hash i of it belongs to bin
+ * first_bin[r] + i / hashes_per_bin[r], the rule of gn_filter_emplace_split.  For each of the filter's hash functions the row is that of
+ * the WHOLE filter -- hash_and_fit with total_rows and countl_zero(total_rows), not with f's own -- and the bit is set at row
+ * row - row_begin of f only when the row lies in the window; nothing else is touched.  With row_begin = 0 and total_rows = n the call
+ * sets exactly the bits a loop of gn_filter_emplace_split over the runs sets.  All runs of a call go through two page-locked staging
+ * chunks of chunk_hashes hashes (0: 1 Mi hashes, 8 MiB each; a run may be longer than a chunk), the upload of one under the kernel
+ * of the one before, one launch per chunk; every bin a run can reach is checked before anything is launched. */
+int gn_filter_emplace_runs_window(gn_filter* f, const uint64_t* const* runs, const uint64_t* run_sizes, const uint32_t* first_bin,
+                                  const uint64_t* hashes_per_bin, uint32_t n_runs, uint64_t total_rows, uint64_t row_begin, uint64_t chunk_hashes);
 /* The membership check of the reference's build test (validate_elements, /root/reference/tests/ganon-build/GanonBuild.test.cpp:53-98:
  * hash a sequence, bulk_count, add up the counts of its target's bins, compare with the number of hashes) for a flat IBF on the
  * device: *hits = sum over the n hashes (host memory) of the number of `bins` that contain the hash, *missing = hashes no bin

@@ -30,7 +30,10 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --families F:D  F families in place of independent genomes: one random ancestor of `len` bases per family; file i is member
                   i // F of family i % F, the ancestor with every base substituted with probability D and a random 0 .. 10 % cut
                   from its end, so that the lengths of the families interleave
-  --lognormal S   file i has len * exp(S * z_i) bases, z_i standard normal (seeded): `len` is the median, not every file's length"""
+  --lognormal S   file i has len * exp(S * z_i) bases, z_i standard normal (seeded): `len` is the median, not every file's length
+  --device LIST   passed on as `--device LIST` to every build; a list a,b,... only to the flat build (the hierarchical modes take one)
+  --device-memory BYTES  passed on to the flat build: the filter is filled in row slabs when it is larger; the run reports "slabs",
+                  "passes", "hash_bytes_uploaded" and per slab its fill and write seconds"""
 import json
 import math
 import os
@@ -42,7 +45,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -101,14 +104,21 @@ if n_families:
 if opts["--lognormal"]:
     out["lognormal_sigma"], out["largest_file"], out["smallest_file"] = float(opts["--lognormal"]), max(lengths), min(lengths)
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
+device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["--device-memory", opts["--device-memory"]] if opts["--device-memory"] else [])
+device_hibf = ["--device", opts["--device"]] if opts["--device"] else []
 
 
 def flat_run(max_fp="0.05", extra=()):
     res = {}
     t0 = time.time()
-    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", max_fp] + list(extra),
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", max_fp] + list(extra) + device_flat,
                        capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    m = re.search(r"filled in (\d+) pass(?:es)? over the hash sets, (\d+) hash bytes uploaded", p.stderr)
+    if m:
+        res["passes"], res["hash_bytes_uploaded"] = int(m.group(1)), int(m.group(2))
+        res["slabs"] = [ln for ln in p.stderr.splitlines() if re.match(r"slab \d+: rows ", ln)][:64]
+        res["slab_fill_write_s"] = [(float(a), float(b)) for a, b in re.findall(r"^slab \d+: filled in ([0-9.eE+-]+) s, written in ([0-9.eE+-]+) s$", p.stderr, re.M)][:64]
     for key, pat in (("count_hashes_s", r"Count/save hashes start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
                      ("sizing_s", r"Estimate params   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
                      ("fill_s", r"Building filter   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
@@ -134,7 +144,7 @@ def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     res = {}
     t0 = time.time()
     cmd = [exe, "-i", os.path.join(d, tsv), "-o", os.path.join(d, db), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
-           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else [])
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf
     p = subprocess.run(cmd, capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
     m = re.search(r" - seconds: hash ([0-9.eE+-]+) union ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
