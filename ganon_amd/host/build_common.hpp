@@ -1,5 +1,6 @@
 // build_common.hpp -- what the modes of `ganon-build` share: build.cpp (arguments, hashing, the flat .ibf), build_hibf.cpp (--hibf),
-// build_verify.cpp (--hibf --verify-index), build_update.cpp (--hibf --update) and build_write.cpp (the two file writers).
+// build_verify.cpp (--hibf --verify-index), build_update.cpp (--hibf --update; its report is build_update_report.cpp, what the two share
+// build_update.hpp) and build_write.cpp (the two file writers).
 #pragma once
 
 #include "build_params.hpp"
