@@ -218,22 +218,11 @@ __global__ __launch_bounds__(256) void gn_emplace_window_kernel(uint64_t* rows, 
     }
 }
 
-// Hashes of a staging chunk when the caller names none: 8 MiB, two of them page-locked and two on the device.  Page-locking is paid per
-// call: one insert of 287 M hashes into a quarter of a filter's rows took 0.118 s with chunks of 4 Mi hashes, 0.080 s with 1 Mi, 0.098 s
-// with 256 Ki and 0.155 s with 64 Ki (launches and waits take over).
-#define GN_WIN_CHUNK (1ull << 20)
+// Hashes of a staging chunk when the caller names none (GN_WIN_CHUNK, gn_emplace_window.h): 8 MiB, two of them page-locked and two on the
+// device.  Page-locking is paid per call: one insert of 287 M hashes into a quarter of a filter's rows took 0.118 s with chunks of 4 Mi
+// hashes, 0.080 s with 1 Mi, 0.098 s with 256 Ki and 0.155 s with 64 Ki (launches and waits take over).
 namespace
 {
-struct GnStreamPair
-{
-    hipStream_t st[2] = { nullptr, nullptr };
-    ~GnStreamPair()
-    {
-        for (hipStream_t s : st)
-            if (s)
-                (void)hipStreamDestroy(s);
-    }
-};
 struct GnWindowStage // everything a call holds; freed when the call returns
 {
     GnStreamPair        streams;

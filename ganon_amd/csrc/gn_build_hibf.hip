@@ -6,6 +6,7 @@
 //                            and ORed into h rows of EVERY IBF on its path (the user bin's own run of bins in its leaf IBF, one
 //                            merged bin in each IBF above).  Inserting every member's set into a merged bin sets the bits the
 //                            union of the sets would: the unions are never materialised.
+//   gn_filter_emplace_path_window  the same into a filter whose IBFs are pieces of rows of the tree's IBFs: a tree built in parts
 //   gn_filter_bin_popcounts  set bits per technical bin of an IBF: how full each bin of an index is (towards `--update`)
 //   gn_filter_copy_ibf       an IBF into one with more bins, device to device
 //   gn_filter_copy_ibf_spans the same with runs of bins left out or moved (`--update --remove`)
@@ -16,8 +17,10 @@
 #include "gn_bin_spans.h"
 #include "gn_fold_table.h"
 #include "gn_build_row.h"
+#include "gn_path_window.h"
 #include "gn_scan.h"
 #include <hipcub/hipcub.hpp>
+#include <cstring>
 #include <vector>
 
 extern "C" int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* sizes, uint32_t n_sets, uint64_t* out, uint64_t cap,
@@ -270,6 +273,166 @@ extern "C" int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, cons
                                                  depth, f->ibfs[0].h);
                               return hipSuccess;
                           });
+}
+
+// ---- gn_filter_emplace_path_window: the same insert into pieces of IBFs ------------------------------------------------------------
+// IBF j of the filter stands for rows [row_begin[j], row_begin[j] + S_j) of an IBF of total_rows[j] rows (`ganon-build --hibf
+// --hibf-memory`, `--hibf-devices`: build_hibf_parts.cpp).  A hash's rows in an IBF depend on the hash and on the WHOLE IBF's row count
+// alone, so every piece is filled from the same hash sets and takes the bits of the rows it holds.
+//
+// One wave per item, as gn_emplace_path_kernel: item and path entries depend on the wave alone, the index goes through readfirstlane so
+// that they are read with scalar loads.  The lane's 8 hashes are loaded first; from then on the wave only issues no-return atomic ORs and
+// waits for nothing.  Per entry the item's first bin and the remainder are divided out once for the wave (gn_path_window_start): no
+// 64-bit division per hash, which gn_emplace_path_kernel pays.  A row outside the piece costs its hash and one compare.
+__global__ __launch_bounds__(256) void gn_emplace_path_window_kernel(const uint64_t* __restrict__ stage, const GnRunItem* __restrict__ items, uint32_t n_items,
+                                                                     const GnPathWinDev* __restrict__ paths, uint32_t depth, uint32_t h)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t  lane = threadIdx.x & 63u;
+    const GnRunItem it   = items[item];
+    uint64_t        v[GN_WIN_PER_LANE];
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+    }
+    const GnPathWinDev* __restrict__ p = paths + (uint64_t)it.run * depth;
+    for (uint32_t d = 0; d < depth; ++d)
+    {
+        const GnPathWinDev e = p[d];
+        if (e.n_bins == 0)
+            break;
+        uint32_t bin0;
+        uint64_t r0;
+        gn_path_window_start(e.first_bin, e.n_bins, e.per_bin, it.begin, &bin0, &r0); // (wave-uniform: once per item and entry)
+#pragma unroll
+        for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+        {
+            const uint32_t q = j * 64u + lane;
+            if (q >= it.cnt)
+                continue;
+            const uint32_t bin  = gn_path_window_bin(bin0, r0, q, e.n_bins, e.per_bin);
+            // (a pointer read from memory is generic to the compiler: say that it is global, as gn_emplace_path_kernel does)
+            GnGlobalWord*  word = (GnGlobalWord*)e.rows + (bin >> 6);
+            const uint64_t bit  = 1ULL << (bin & 63);
+            for (uint32_t i = 0; i < h; ++i)
+            {
+                uint32_t local;
+                if (gn_window_local(gn_build_row(v[j], i, e.shift, e.S_total), e.row_begin, e.n_rows, &local))
+                    (void)__hip_atomic_fetch_or(word + (uint64_t)local * e.Ws, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+namespace
+{
+struct GnPathWindowStage // everything a call holds; freed when the call returns
+{
+    GnStreamPair        streams;
+    GnPinned<uint64_t>  h_stage[2];
+    GnPinned<GnRunItem> h_items[2];
+    GnDev<uint64_t>     d_stage[2];
+    GnDev<GnRunItem>    d_items[2];
+    GnDev<GnPathWinDev> d_paths;
+};
+} // namespace
+
+// Chunk c goes through buffer and stream c & 1, as gn_runs_window_rounds (gn_build.hip) sends it: gathered into the page-locked buffer,
+// copied and inserted on that stream while chunk c - 1 is still on the other one.  A buffer is written again only after its stream has
+// been waited for.
+static int gn_path_window_rounds(GnPathWindowStage& g, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, uint32_t depth, uint32_t h,
+                                 uint64_t chunk, uint64_t cap_items)
+{
+    std::vector<GnRunItem> items;
+    GnRunCursor            cur;
+    for (uint32_t c = 0;; ++c)
+    {
+        const uint32_t b = c & 1u;
+        GN_HIP(hipStreamSynchronize(g.streams.st[b]));
+        const uint64_t taken = gn_window_next_chunk(set_sizes, n_sets, cur, chunk, cap_items, items);
+        if (taken == 0)
+            return GN_OK;
+        for (const GnRunItem& it : items)
+            memcpy(g.h_stage[b] + it.stage_at, sets[it.run] + it.begin, (size_t)it.cnt * 8);
+        memcpy(g.h_items[b].get(), items.data(), items.size() * sizeof(GnRunItem));
+        GN_HIP(hipMemcpyAsync(g.d_stage[b], g.h_stage[b], taken * 8, hipMemcpyHostToDevice, g.streams.st[b]));
+        GN_HIP(hipMemcpyAsync(g.d_items[b], g.h_items[b], items.size() * sizeof(GnRunItem), hipMemcpyHostToDevice, g.streams.st[b]));
+        const uint32_t n_items = (uint32_t)items.size();
+        hipLaunchKernelGGL(gn_emplace_path_window_kernel, dim3((n_items + 3) / 4), dim3(256), 0, g.streams.st[b], (const uint64_t*)g.d_stage[b],
+                           (const GnRunItem*)g.d_items[b], n_items, (const GnPathWinDev*)g.d_paths, depth, h);
+        GN_HIP(hipGetLastError());
+    }
+}
+
+extern "C" int gn_filter_emplace_path_window(gn_filter* f, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, const gn_path_entry* paths,
+                                             uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t chunk_hashes)
+{
+    static const char* const who = "gn_filter_emplace_path_window";
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs an HIBF filter", who);
+    if (!total_rows || !row_begin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    for (size_t j = 0; j < f->ibfs.size(); ++j)
+    {
+        if (total_rows[j] == 0 || total_rows[j] > 0xFFFFFFFFull)
+            return gn_fail(GN_ERANGE, "%s: ibf %zu: an IBF of %llu rows, 1 .. 2^32 - 1 are supported", who, j, (unsigned long long)total_rows[j]);
+        if (row_begin[j] > total_rows[j] || f->ibfs[j].S > total_rows[j] - row_begin[j])
+            return gn_fail(GN_EINVAL, "%s: ibf %zu: rows %llu .. %llu of an IBF of %llu rows", who, j, (unsigned long long)row_begin[j],
+                           (unsigned long long)(row_begin[j] + f->ibfs[j].S), (unsigned long long)total_rows[j]);
+    }
+    if (n_sets == 0)
+        return GN_OK;
+    if (!sets || !set_sizes || !paths || depth == 0)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    const uint32_t h = f->ibfs[0].h;
+    // every bin a hash can reach is checked before anything is launched (the local row is below the piece's rows by the window test)
+    std::vector<GnPathWinDev> dev((size_t)n_sets * depth, GnPathWinDev{ nullptr, 1, 1, 1, 0, 0, 0, 0, 0 });
+    uint64_t                  total = 0;
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        if (set_sizes[s] && !sets[s])
+            return gn_fail(GN_EINVAL, "%s: set %u is null", who, s);
+        total += set_sizes[s];
+        for (uint32_t d = 0; d < depth && paths[(size_t)s * depth + d].n_bins != 0; ++d)
+        {
+            GnPathDev           o;
+            const gn_path_entry& e = paths[(size_t)s * depth + d];
+            if (const int rc = gn_path_resolve(who, f, e, s, d, true, set_sizes[s], o))
+                return rc;
+            const GnIbfHost& ib = f->ibfs[e.ibf];
+            if (ib.h != h)
+                return gn_fail(GN_EINVAL, "%s: ibf %u has %u hash functions, ibf 0 has %u", who, e.ibf, ib.h, h);
+            dev[(size_t)s * depth + d] = GnPathWinDev{ o.rows, total_rows[e.ibf], o.per_bin, o.Ws, (uint32_t)__builtin_clzll(total_rows[e.ibf]),
+                                                       o.first_bin, o.n_bins, (uint32_t)row_begin[e.ibf], (uint32_t)ib.S };
+        }
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    const uint64_t    chunk     = std::min<uint64_t>(chunk_hashes ? chunk_hashes : GN_WIN_CHUNK, total);
+    const uint64_t    cap_items = chunk / 64 + 16; // (a chunk of many short sets closes at this many items instead of at `chunk` hashes)
+    GnPathWindowStage g;
+    for (int b = 0; b < 2; ++b)
+    {
+        GN_HIP(hipStreamCreateWithFlags(&g.streams.st[b], hipStreamNonBlocking));
+        GN_HIP(g.h_stage[b].alloc(chunk));
+        GN_HIP(g.h_items[b].alloc(cap_items));
+        GN_HIP(g.d_stage[b].alloc(chunk));
+        GN_HIP(g.d_items[b].alloc(cap_items));
+    }
+    GN_HIP(g.d_paths.upload(dev.data(), dev.size()));
+    const int rc = gn_path_window_rounds(g, sets, set_sizes, n_sets, depth, h, chunk, cap_items);
+    // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
+    const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
+    if (rc != GN_OK)
+        return rc;
+    GN_HIP(e0);
+    GN_HIP(e1);
+    return GN_OK;
 }
 
 // ---- gn_filter_probe_path / gn_filter_probe_paths_shared: the insert read back ---------------------------------------------------

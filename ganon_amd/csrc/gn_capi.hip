@@ -508,6 +508,40 @@ extern "C" int gn_filter_upload_hibf(int device, uint32_t n_ibf, const gn_ibf_de
     return GN_OK;
 }
 
+// A zero-filled HIBF without tables: the builder's storage for a part of a tree (build_hibf_parts.cpp).  gn_filter_upload_hibf with
+// every bin absent does not serve: gn_hibf_build takes a tree whose IBFs hang together and a part is any set of IBFs or pieces of
+// them, and a stream would be created on the result.  The rows are padded as gn_filter_upload_hibf pads them.
+extern "C" int gn_filter_create_hibf_storage(int device, uint32_t n_ibf, const gn_ibf_desc* ibfs, gn_filter** out)
+{
+    if (!out || !ibfs || n_ibf == 0)
+        return gn_fail(GN_EINVAL, "gn_filter_create_hibf_storage: null/empty argument");
+    *out = nullptr;
+    for (uint32_t i = 0; i < n_ibf; ++i)
+        if (ibfs[i].rows)
+            return gn_fail(GN_EINVAL, "gn_filter_create_hibf_storage: ibf %u comes with rows (a storage filter starts zero-filled)", i);
+    int rc = gn_set_device(device);
+    if (rc)
+        return rc;
+    gn_filter* f = new (std::nothrow) gn_filter();
+    if (!f)
+        return gn_fail(GN_ENOMEM, "out of host memory");
+    f->device       = device;
+    f->is_hibf      = true;
+    f->storage_only = true;
+    f->ibfs.resize(n_ibf);
+    for (uint32_t i = 0; i < n_ibf; ++i)
+    {
+        rc = gn_upload_ibf_rows(&ibfs[i], &f->ibfs[i], &f->device_bytes, gn_hibf_row_stride_words(ibfs[i].bin_words) != ibfs[i].bin_words);
+        if (rc)
+        {
+            gn_filter_free(f);
+            return rc;
+        }
+    }
+    *out = f;
+    return GN_OK;
+}
+
 extern "C" int gn_filter_free(gn_filter* f)
 {
     if (!f)

@@ -106,5 +106,21 @@ public:
     operator T*() const { return p_; }
 };
 
+// the two streams of an insert that uploads one staging chunk under the kernel of the one before (gn_filter_emplace_runs_window,
+// gn_filter_emplace_path_window); destroyed with the call
+struct GnStreamPair
+{
+    hipStream_t st[2] = { nullptr, nullptr };
+    GnStreamPair() = default;
+    GnStreamPair(const GnStreamPair&) = delete;
+    GnStreamPair& operator=(const GnStreamPair&) = delete;
+    ~GnStreamPair()
+    {
+        for (hipStream_t s : st)
+            if (s)
+                (void)hipStreamDestroy(s);
+    }
+};
+
 static_assert(!std::is_copy_constructible<GnDev<int>>::value && !std::is_copy_assignable<GnDev<int>>::value, "GnDev owns its allocation");
 static_assert(!std::is_copy_constructible<GnPinned<int>>::value && !std::is_copy_assignable<GnPinned<int>>::value, "GnPinned owns its allocation");

@@ -21,6 +21,7 @@
 
 #define GN_WIN_PER_LANE 8u                    // hashes a lane holds in registers
 #define GN_WIN_ITEM (64u * GN_WIN_PER_LANE)   // ... and a wave's item: 512 hashes
+#define GN_WIN_CHUNK (1ull << 20)             // hashes of a staging chunk when the caller names none (measured: gn_build.hip)
 
 // A wave's piece of work: `cnt` consecutive hashes of run `run`, the first of them hash number `begin` of the run and word `stage_at`
 // of the staging chunk.

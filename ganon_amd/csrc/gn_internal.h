@@ -278,7 +278,7 @@ struct gn_filter
     int      device  = 0;
     int      n_cu    = 256;
     bool     is_hibf = false;
-    bool     storage_only = false; // flat, created without a bin map: no streams (gn_filter_upload_ibf)
+    bool     storage_only = false; // created without a bin map (gn_filter_upload_ibf) or without tables (gn_filter_create_hibf_storage): no streams
     uint64_t device_bytes = 0;
     hipStream_t load_st = nullptr; // streaming upload (gn_filter_write_rows), created on first use
     GnDev<uint64_t> d_emplace_stage; // gn_filter_emplace_split's staging buffer (cap(): its capacity in hashes)

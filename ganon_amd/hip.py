@@ -35,7 +35,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
                "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_fold_ibf", "gn_filter_extend_path",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table",
-               "gn_filter_emplace_runs_window"]
+               "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -165,7 +165,9 @@ def load_library():
     L.gn_filter_emplace_runs_window.argtypes = [vp, vp, vp, vp, vp, u32, u64, u64, u64]
     L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
-    L.gn_filter_probe_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
+    L.gn_filter_create_hibf_storage.argtypes = [i32, u32, C.POINTER(IbfDesc), C.POINTER(vp)]
+    L.gn_filter_emplace_path_window.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, u64]
+    L.gn_filter_probe_path.argtypes =[vp, vp, vp, u32, vp, u32, vp, vp, vp]
     L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
     L.gn_filter_bin_popcounts.argtypes = [vp, u32, vp]
     L.gn_filter_copy_ibf.argtypes = [vp, u32, vp, u32]
@@ -637,6 +639,33 @@ class HipFilter:
         hashes = np.concatenate([np.asarray(a, dtype=np.uint64) for a in sets]) if len(sets) else np.zeros(0, np.uint64)
         hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
         _check(load_library().gn_filter_emplace_path(self._h, _p(hashes), _p(off), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1]))
+
+    @classmethod
+    def hibf_storage(cls, shapes: Sequence[Tuple[int, int, int]], device: int = 0) -> "HipFilter":
+        """gn_filter_create_hibf_storage: an empty storage-only HIBF without tables, as `ganon-build --hibf` creates one per part of a
+        tree built in parts.  shapes: (bins, rows, hash_funs) per IBF; the 4-tuples of `hibf` with rows None are taken too"""
+        assert all(len(s) == 3 or (len(s) == 4 and s[0] is None) for s in shapes), "a storage filter starts zero-filled"
+        shapes = [tuple(s[-3:]) for s in shapes]
+        n = len(shapes)
+        descs = (IbfDesc * max(n, 1))(*[_desc(None, b, r, hf) for b, r, hf in shapes])
+        h = C.c_void_p()
+        _check(load_library().gn_filter_create_hibf_storage(device, n, descs, C.byref(h)))
+        return cls(h, bins=[b for b, _, _ in shapes])
+
+    def emplace_path_window(self, sets: Sequence[np.ndarray], paths: np.ndarray, total_rows, row_begin, chunk_hashes: int = 0) -> None:
+        """gn_filter_emplace_path_window: IBF j of this filter stands for rows [row_begin[j], row_begin[j] + its rows) of an IBF of
+        total_rows[j] rows; sets[s] (ascending uint64) goes along paths[s] (PATH_DTYPE, [len(sets), depth], `ibf` numbering this filter's
+        IBFs) and sets the bits of its rows inside those pieces"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(sets)
+        sets = [np.ascontiguousarray(a, dtype=np.uint64) for a in sets]
+        ptrs = (C.c_void_p * max(len(sets), 1))(*[a.ctypes.data for a in sets])
+        sizes = np.array([len(a) for a in sets], dtype=np.uint64)
+        total = np.ascontiguousarray(total_rows, dtype=np.uint64)
+        begin = np.ascontiguousarray(row_begin, dtype=np.uint64)
+        assert len(total) == len(begin) == len(self._bins)
+        _check(load_library().gn_filter_emplace_path_window(self._h, ptrs, _p(sizes), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1],
+                                                            _p(total), _p(begin), chunk_hashes))
 
     def extend_path(self, sets: Sequence[np.ndarray], paths: np.ndarray, quotas: Sequence[np.ndarray]) -> None:
         """gn_filter_extend_path: sets[s] (strictly ascending uint64) along paths[s] (PATH_DTYPE, [len(sets), depth]) of an HIBF that holds

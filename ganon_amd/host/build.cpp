@@ -102,6 +102,18 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
     }
     if (c.device_memory_given && c.device_memory == 0)
         return say("--device-memory has to be > 0");
+    // the hierarchical build in parts has switches of its own (a tree is cut by IBF and by padded device rows, not by file rows)
+    for (const auto& [given, name] : { std::pair<bool, const char*>{ c.hibf_memory_given, "--hibf-memory" }, { c.hibf_devices_given, "--hibf-devices" } })
+    {
+        if (given && !c.hibf)
+            return say(std::string(name) + " needs --hibf (a flat .ibf is built in row slabs with --device-memory and a --device list)");
+        if (given && c.update_given)
+            return say(std::string(name) + " cannot be used with --update (an index is updated on one device)");
+        if (given && c.verify_given)
+            return say(std::string(name) + " cannot be used with --verify-index (an index is checked on one device)");
+    }
+    if (c.hibf_memory_given && c.hibf_memory == 0)
+        return say("--hibf-memory has to be > 0");
     if (c.tmax_given && !c.hibf)
         return say("--tmax needs --hibf");
     if (c.layout_given && !c.hibf)
@@ -222,6 +234,15 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--device-memory     " << c.device_memory << '\n';
     if (c.hibf)
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
+    if (c.hibf_memory_given)
+        std::cerr << "--hibf-memory       " << c.hibf_memory << '\n';
+    if (c.hibf_devices_given)
+    {
+        std::cerr << "--hibf-devices      ";
+        for (size_t i = 0; i < c.hibf_devices.size(); ++i)
+            std::cerr << (i ? "," : "") << c.hibf_devices[i];
+        std::cerr << '\n';
+    }
     if (c.layout_given)
         std::cerr << "--layout            " << c.layout << '\n';
     if (c.verify_given)
@@ -263,6 +284,16 @@ const char* kHelp =
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
     "                               Default: ceil(sqrt(targets) / 64) * 64\n"
+    "      --hibf-memory arg        [--hibf] most device bytes of IBF rows held on an entry of --hibf-devices at one time (rows as the\n"
+    "                               device pads them, not as the file holds them).  A tree larger than that is filled in parts --\n"
+    "                               whole IBFs grouped in file order, an IBF over the budget in slabs of rows -- each from the\n"
+    "                               hash sets that reach it (which stay in host memory), and written part by part: the same file.\n"
+    "                               Default: what the device has free when filling starts, less staging and a reserve, shared\n"
+    "                               among the entries that name it.  Not with --update or --verify-index\n"
+    "      --hibf-devices arg       [--hibf] a list a,b,... (an index may repeat): the parts are dealt to its entries, one worker\n"
+    "                               each.  Default: the single --device, where hashing, unions and sketches stay.  Two families of\n"
+    "                               switches because --device-memory counts file rows of one matrix and a --device list also deals\n"
+    "                               the hashing threads; with --hibf both stay refused.  Not with --update or --verify-index\n"
     "      --layout arg             [--hibf] how the tree is chosen: rule (from the targets' hash counts alone), sketch (by size,\n"
     "                               from HyperLogLog estimates of the unions of neighbouring targets) or similarity (as sketch,\n"
     "                               with targets of comparable size reordered so that related ones are neighbours; the\n"
@@ -351,7 +382,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -431,26 +462,31 @@ int parse_args(int argc, char** argv, Config& c)
             c.tmp_output_folder = vals["--tmp-output-folder"];
         if (vals.count("--threads"))
             c.threads = (uint16_t)u("--threads", 65535);
-        if (vals.count("--device")) // one index, or a list a,b,...
-        {
-            c.devices.clear();
-            std::istringstream list(vals["--device"]);
+        auto device_list = [&](const char* k) { // one index, or a list a,b,...
+            std::vector<int>   out;
+            std::istringstream list(vals[k]);
             for (std::string e; std::getline(list, e, ',');)
             {
                 size_t pos = 0;
                 if (e.empty() || e[0] == '-' || e[0] == '+')
-                    throw std::invalid_argument("--device");
+                    throw std::invalid_argument(k);
                 const uint64_t x = std::stoull(e, &pos);
                 if (pos != e.size() || x > (1u << 20))
-                    throw std::invalid_argument("--device");
-                c.devices.push_back((int)x);
+                    throw std::invalid_argument(k);
+                out.push_back((int)x);
             }
-            if (c.devices.empty() || vals["--device"].back() == ',')
-                throw std::invalid_argument("--device");
-            c.device = c.devices[0];
-        }
+            if (out.empty() || vals[k].back() == ',')
+                throw std::invalid_argument(k);
+            return out;
+        };
+        if (vals.count("--device"))
+            c.devices = device_list("--device"), c.device = c.devices[0];
         if (vals.count("--device-memory"))
             c.device_memory = u("--device-memory", ~0ull), c.device_memory_given = true;
+        if (vals.count("--hibf-devices"))
+            c.hibf_devices = device_list("--hibf-devices"), c.hibf_devices_given = true;
+        if (vals.count("--hibf-memory"))
+            c.hibf_memory = u("--hibf-memory", ~0ull), c.hibf_memory_given = true;
         c.verbose = vals.count("--verbose") && vals["--verbose"] != "false";
         c.quiet   = vals.count("--quiet") && vals["--quiet"] != "false";
         c.extend  = vals.count("--extend") && vals["--extend"] != "false";
@@ -594,6 +630,9 @@ bool run(Config c)
     for (int d : c.devices)
         if (d >= n_dev)
             return fail("--device " + std::to_string(d) + " does not exist (" + std::to_string(n_dev) + " visible)");
+    for (int d : c.hibf_devices)
+        if (d >= n_dev)
+            return fail("--hibf-devices " + std::to_string(d) + " does not exist (" + std::to_string(n_dev) + " visible)");
 
     Totals              totals;
     const bool          remove_only = (c.remove_given || c.fold_given) && c.input_file.empty();

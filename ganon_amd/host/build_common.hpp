@@ -1,10 +1,13 @@
 // build_common.hpp -- what the modes of `ganon-build` share: build.cpp (arguments, hashing, the flat .ibf), build_hibf.cpp (--hibf),
 // build_verify.cpp (--hibf --verify-index), build_update.cpp (--hibf --update; its report is build_update_report.cpp, what the two share
-// build_update.hpp) and build_write.cpp (the two file writers).
+// build_update.hpp), build_slabs.cpp and build_hibf_parts.cpp (a filter larger than a device, flat in row slabs and hierarchical in
+// parts) and build_write.cpp (the two file writers).
 #pragma once
 
 #include "build_params.hpp"
 #include "device_sink.hpp"
+#include "hibf_build_parts.hpp"
+#include "hibf_paths.hpp"
 
 #include "ganon_hip.h"
 
@@ -39,6 +42,9 @@ struct Config // Config.hpp:10-27
     uint64_t    device_memory = 0;    // (--device-memory: most bytes of filter rows on a list entry at one time; 0 = from what is free)
     bool        device_memory_given = false;
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
+    uint64_t    hibf_memory = 0; // (--hibf-memory: most device bytes of IBF rows on an entry of hibf_devices at one time; 0 = from what is free)
+    bool        hibf_memory_given = false, hibf_devices_given = false;
+    std::vector<int> hibf_devices; // (--hibf-devices a,b,...: the entries the parts of a tree are dealt to; empty = the single --device)
     uint64_t    tmax = 0;       // (--hibf only: most technical bins of an IBF; 0 = ceil(sqrt(user bins) / 64) * 64)
     bool        tmax_given = false, filter_size_given = false;
     std::string layout = "rule"; // (--hibf only: rule = hibf_layout.hpp, sketch = hibf_layout_sketch.hpp on HyperLogLog union estimates,
@@ -211,6 +217,33 @@ struct FlatFill
     const std::vector<uint64_t>& shares; // hashes per bin of each target (lay_out_bins)
 };
 bool fill_and_save_flat(const FlatFill& w, Lap& filling, Lap& writing);
+// (build_slabs.cpp) most bytes of rows on a list entry at one time when the user names none: the smallest share of free memory over the
+// entries -- what gn_device_memory reports free now, less the staging of the fills that run there and a reserve, divided by how often
+// the device is named.  The rule of the flat build in row slabs and of the hierarchical build in parts.
+bool budget_from_free_memory(const std::vector<int>& devices, uint64_t& budget, std::string& err);
+
+// The raptor index in pieces, for a build in parts (build_write.cpp): everything but the payloads -- the header, every IBF's own header
+// at its offset, the tables behind the last payload -- and a file of full size, whose descriptor (>= 0; the caller closes it) and
+// payload offsets (one per IBF) come back; then rows [0, n_rows) of IBF `ibf` of a part's filter to byte `at` of the file.
+int  open_hibf(const Config& c, const std::vector<HibfShape>& ibfs, uint8_t hash_functions, const std::vector<std::vector<std::string>>& bin_path,
+               const std::vector<std::string>& user_files, std::vector<uint64_t>& payload_at, std::string& err);
+bool save_piece(int fd, gn_filter* flt, uint32_t ibf, uint64_t n_rows, uint64_t row_bytes, uint64_t at, gnhost::PinnedBlock& stage, std::string& err);
+
+// build_hibf_parts.cpp: the tree of a hierarchical filter, filled part by part over `devices` (one worker an entry) and written as it
+// goes; any failure removes the output file.  hash_bytes_uploaded: what the parts' passes over the hash sets sent to the devices.
+struct HibfPartsFill
+{
+    const Config&                                        c;
+    const std::vector<HibfShape>&                        ibfs;
+    uint8_t                                              hash_functions;
+    const HibfPartPlan&                                  plan;
+    const std::vector<int>&                              devices;
+    const gnhibf::Paths&                                 paths;
+    const std::vector<std::pair<const uint64_t*, uint64_t>>& sets; // per user bin
+    const std::vector<std::vector<std::string>>&         bin_path;
+    const std::vector<std::string>&                      user_files;
+};
+bool fill_and_save_hibf_parts(const HibfPartsFill& w, uint64_t& hash_bytes_uploaded);
 
 // the modes, after the inputs are hashed (build.cpp: run)
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting);   // build_hibf.cpp

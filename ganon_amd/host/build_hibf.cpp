@@ -4,6 +4,8 @@
 //   one user bin per target -> tree of IBFs (hibf_layout.hpp) -> exact cardinalities of the merged bins (gn_hashes_union)
 //   -> rows per IBF (gnbuild::hibf_run_bits) -> zero-filled HIBF in HBM -> every user bin ORed in along its whole path
 //   (gn_filter_emplace_path) -> IBF after IBF streamed into the file (save_hibf: the twin of ganon_amd/ibf_file.py:save_hibf).
+// A tree that does not fit what a device may hold at one time (--hibf-memory, or what is free) is filled in parts over --hibf-devices
+// instead (hibf_build_parts.hpp: the plan; build_hibf_parts.cpp: the workers) and gives the same file.
 #include "build_common.hpp"
 #include "hibf_layout.hpp"
 #include "hibf_layout_similarity.hpp"
@@ -198,15 +200,81 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         std::cerr << "Filter size: " << device_bits << " Bits (" << device_bits / static_cast<double>(8388608u) << " Megabytes)" << std::endl;
     }
 
+    // the end of either build: the laps and what was built
+    auto report = [&]() {
+        whole.stop();
+        if (c.quiet)
+            return;
+        print_stats(c, totals, counting, "Layout and unions start: ", uniting, filling, writing, whole);
+        std::cerr << " - hibf: " << n_user << " user bins in " << ibfs.size() << " IBFs on " << lay.levels << " level(s), tmax " << tmax << std::endl;
+        std::cerr << std::fixed << std::setprecision(2) << " - filter size: " << device_bits / static_cast<double>(8388608u) << "MB" << std::endl;
+        // (one line a caller can parse: where the time went)
+        std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
+                  << " write " << writing.seconds();
+        if (c.layout == "sketch" || c.layout == "similarity") // (part of `union`: sketches, union table and search)
+            std::cerr << " layout " << laying.seconds();
+        std::cerr << std::endl;
+        if (c.layout == "similarity") // (where the layout lap went; host = the ordering and the searches)
+            std::cerr << " - layout seconds: sketches " << sketch_laps.sketches << " tables " << sketch_laps.tables << " pairs " << sketch_laps.pairs << " host "
+                      << laying.seconds() - sketch_laps.sketches - sketch_laps.tables - sketch_laps.pairs << std::endl;
+    };
+
     filling.start();
+    // the parts the tree is filled in: one when it fits what an entry of the list may hold at one time
+    const std::vector<int> entries = c.hibf_devices.empty() ? std::vector<int>{ c.device } : c.hibf_devices;
+    uint64_t               budget  = c.hibf_memory;
+    if (!c.hibf_memory_given)
+    {
+        std::string why;
+        if (!budget_from_free_memory(entries, budget, why))
+            return fail(why);
+    }
+    HibfPartPlan plan;
+    try
+    {
+        std::vector<uint64_t> rows, row_bytes;
+        for (const HibfShape& s : ibfs)
+            rows.push_back(s.rows), row_bytes.push_back(gn_hibf_row_stride_words((s.bins + 63) >> 6) * 8);
+        plan = plan_hibf_parts(rows, row_bytes, budget, (uint32_t)entries.size());
+    }
+    catch (const std::exception& e)
+    {
+        return fail(std::string(c.hibf_memory_given ? "--hibf-memory: " : "--hibf-devices: ") + e.what());
+    }
+    // every user bin's path: its run in its leaf IBF, then the merged bin that leads there in each IBF above
+    const gnhibf::Paths paths = gnhibf::paths_of(lay, counts);
+    std::vector<std::vector<std::string>> bin_path; // one file per user bin
+    for (const std::string& f : files)
+        bin_path.push_back({ f });
+    uint64_t one_pass_bytes = 0; // what the one-pass build uploads: every user bin's set once
+    for (uint64_t n : counts)
+        one_pass_bytes += n * 8;
+    if (c.verbose && plan.n_parts <= 100000) // (a plan is a rule: a budget of a few rows makes more parts than anyone reads)
+        for (uint64_t p = 0; p < plan.n_parts; ++p)
+            for (const HibfPiece& x : plan.part(p))
+                std::cerr << "part " << p << " device " << entries[plan.entry_of(p)] << ": ibf " << x.ibf << " rows [" << x.row_begin << ", "
+                          << x.row_begin + x.n_rows << ")\n";
+    if (plan.n_parts > 1)
+    {
+        std::vector<std::pair<const uint64_t*, uint64_t>> sets;
+        for (uint64_t u = 0; u < n_user; ++u)
+            sets.push_back(hash_set(targets[user_target[u]]));
+        uint64_t uploaded = 0;
+        if (!fill_and_save_hibf_parts(HibfPartsFill{ c, ibfs, h, plan, entries, paths, sets, bin_path, files }, uploaded))
+            return false;
+        filling.stop();
+        writing.start(), writing.stop(); // (the rows went out piece by piece, inside the fill)
+        if (c.verbose)
+            std::cerr << "filled in " << plan.n_parts << " parts, " << uploaded << " hash bytes uploaded (one pass: " << one_pass_bytes << ")" << std::endl;
+        report();
+        return true;
+    }
     gnhost::HibfDescs descs;
     for (const HibfShape& s : ibfs)
         descs.add(s.bins, s.rows, h, s.next_ibf_id, s.bin_to_user);
-    gnhost::OwnedFilter flt = descs.upload(c.device, n_user);
+    gnhost::OwnedFilter flt = descs.upload(entries[0], n_user);
     if (!flt)
         return fail(gn_last_error());
-    // every user bin's path: its run in its leaf IBF, then the merged bin that leads there in each IBF above
-    const gnhibf::Paths paths = gnhibf::paths_of(lay, counts);
     try
     {
         gnhibf::for_each_pooled(
@@ -226,31 +294,14 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
 
     writing.start();
     std::string err;
-    std::vector<std::vector<std::string>> bin_path; // one file per user bin
-    for (const std::string& f : files)
-        bin_path.push_back({ f });
-    const bool saved = save_hibf(c, flt.get(), ibfs, h, bin_path, files, err);
+    const bool  saved = save_hibf(c, flt.get(), ibfs, h, bin_path, files, err);
     flt.reset();
     if (!saved)
         return fail(err);
     writing.stop();
-    whole.stop();
-
-    if (!c.quiet)
-    {
-        print_stats(c, totals, counting, "Layout and unions start: ", uniting, filling, writing, whole);
-        std::cerr << " - hibf: " << n_user << " user bins in " << ibfs.size() << " IBFs on " << lay.levels << " level(s), tmax " << tmax << std::endl;
-        std::cerr << std::fixed << std::setprecision(2) << " - filter size: " << device_bits / static_cast<double>(8388608u) << "MB" << std::endl;
-        // (one line a caller can parse: where the time went)
-        std::cerr << std::setprecision(6) << " - seconds: hash " << counting.seconds() << " union " << uniting.seconds() << " emplace " << filling.seconds()
-                  << " write " << writing.seconds();
-        if (c.layout == "sketch" || c.layout == "similarity") // (part of `union`: sketches, union table and search)
-            std::cerr << " layout " << laying.seconds();
-        std::cerr << std::endl;
-        if (c.layout == "similarity") // (where the layout lap went; host = the ordering and the searches)
-            std::cerr << " - layout seconds: sketches " << sketch_laps.sketches << " tables " << sketch_laps.tables << " pairs " << sketch_laps.pairs << " host "
-                      << laying.seconds() - sketch_laps.sketches - sketch_laps.tables - sketch_laps.pairs << std::endl;
-    }
+    if (c.verbose)
+        std::cerr << "filled in 1 part, " << one_pass_bytes << " hash bytes uploaded" << std::endl;
+    report();
     return true;
 }
 

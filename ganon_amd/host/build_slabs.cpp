@@ -54,8 +54,7 @@ struct Runs
     }
 };
 
-// most bytes of rows on a list entry at one time: --device-memory, else the smallest share of free memory over the entries -- what
-// gn_device_memory reports free now, less the staging of the fills that run there and the reserve, divided by how often the device is named
+// most bytes of rows on a list entry at one time: --device-memory, else what the free memory allows
 bool budget_of(const Config& c, uint64_t& budget, std::string& err)
 {
     if (c.device_memory_given)
@@ -63,8 +62,15 @@ bool budget_of(const Config& c, uint64_t& budget, std::string& err)
         budget = c.device_memory;
         return true;
     }
+    return budget_from_free_memory(c.devices, budget, err);
+}
+
+} // namespace
+
+bool budget_from_free_memory(const std::vector<int>& devices, uint64_t& budget, std::string& err)
+{
     std::map<int, uint64_t> named;
-    for (int d : c.devices)
+    for (int d : devices)
         ++named[d];
     budget = ~0ull;
     for (const auto& [d, k] : named)
@@ -80,8 +86,6 @@ bool budget_of(const Config& c, uint64_t& budget, std::string& err)
     }
     return true;
 }
-
-} // namespace
 
 bool fill_and_save_flat(const FlatFill& w, Lap& filling, Lap& writing)
 {

@@ -1,5 +1,6 @@
-// build_write.cpp -- the files `ganon-build` writes: the flat .ibf (save_filter) and the raptor 3.0.1 index (save_hibf).  The header
-// comes from the host; the bit matrices are streamed out of HBM through one page-locked stage (write_rows).
+// build_write.cpp -- the files `ganon-build` writes: the flat .ibf (save_filter; in row slabs open_filter + save_slab) and the raptor
+// 3.0.1 index (save_hibf; in parts open_hibf + save_piece).  The header comes from the host; the bit matrices are streamed out of HBM
+// through one page-locked stage (write_rows).
 #include "build_common.hpp"
 #include "hasher.hpp"
 
@@ -210,9 +211,48 @@ bool save_slab(int fd, gn_filter* flt, uint64_t n_rows, uint64_t row_bytes, uint
 }
 
 // The raptor 3.0.1 index (reader: GanonClassify.cpp:875-938 with hibf.hpp:163-169,293-298), field for field what
-// ganon_amd/ibf_file.py:save_hibf writes; the matrices streamed IBF after IBF out of HBM.
+// ganon_amd/ibf_file.py:save_hibf writes.  The fields before the first IBF and those behind the last one, for the two writers below.
 // bin_path: the files of every user bin (this builder writes one each; a raptor file that `--update` carries over may list several);
 // user_files: user_bin_filenames, one per user bin.
+static void hibf_front(Writer& w, const Config& c, const std::vector<std::vector<std::string>>& bin_path, uint64_t n_ibf)
+{
+    w.raw<uint32_t>(1);                                     // raptor index version
+    w.raw<uint64_t>(c.window_size);
+    w.raw<uint64_t>(c.kmer_size);                           // seqan3::shape: size, bits
+    w.raw<uint64_t>(c.kmer_size >= 64 ? ~0ull : (1ull << c.kmer_size) - 1);
+    w.raw<uint8_t>(1);                                      // parts
+    w.raw<uint8_t>(0);                                      // compressed
+    w.raw<uint64_t>(bin_path.size());                       // bin_path
+    for (const std::vector<std::string>& lst : bin_path)
+    {
+        w.raw<uint64_t>(lst.size());
+        for (const std::string& f : lst)
+            w.str(f);
+    }
+    w.raw<double>(c.max_fp);                                // fpr
+    w.raw<uint8_t>(1);                                      // is_hibf
+    w.raw<uint64_t>(n_ibf);                                 // ibf_vector
+}
+
+static void hibf_back(Writer& w, const std::vector<HibfShape>& ibfs, const std::vector<std::string>& user_files)
+{
+    auto tables = [&](bool next) {
+        w.raw<uint64_t>(ibfs.size());
+        for (const HibfShape& s : ibfs)
+        {
+            const std::vector<int64_t>& v = next ? s.next_ibf_id : s.bin_to_user;
+            w.raw<uint64_t>(v.size());
+            w.buf.append(reinterpret_cast<const char*>(v.data()), v.size() * 8);
+        }
+    };
+    tables(true);                                           // next_ibf_id
+    w.raw<uint64_t>(user_files.size());                     // user_bins: user_bin_filenames
+    for (const std::string& f : user_files)
+        w.str(f);
+    tables(false);                                          //            ibf_bin_to_filename_position
+}
+
+// the matrices streamed IBF after IBF out of HBM
 bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ibfs, uint8_t hash_functions,
                const std::vector<std::vector<std::string>>& bin_path, const std::vector<std::string>& user_files, std::string& err)
 {
@@ -230,22 +270,7 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
         w.buf.clear();
     };
     Writer w;
-    w.raw<uint32_t>(1);                                     // raptor index version
-    w.raw<uint64_t>(c.window_size);
-    w.raw<uint64_t>(c.kmer_size);                           // seqan3::shape: size, bits
-    w.raw<uint64_t>(c.kmer_size >= 64 ? ~0ull : (1ull << c.kmer_size) - 1);
-    w.raw<uint8_t>(1);                                      // parts
-    w.raw<uint8_t>(0);                                      // compressed
-    w.raw<uint64_t>(bin_path.size());                       // bin_path
-    for (const std::vector<std::string>& lst : bin_path)
-    {
-        w.raw<uint64_t>(lst.size());
-        for (const std::string& f : lst)
-            w.str(f);
-    }
-    w.raw<double>(c.max_fp);                                // fpr
-    w.raw<uint8_t>(1);                                      // is_hibf
-    w.raw<uint64_t>(ibfs.size());                           // ibf_vector
+    hibf_front(w, c, bin_path, ibfs.size());
     flush(w);
     uint64_t stage_bytes = 0; // the largest chunk of any IBF
     for (const HibfShape& s : ibfs)
@@ -265,25 +290,70 @@ bool save_hibf(const Config& c, gn_filter* flt, const std::vector<HibfShape>& ib
         ok = ok && write_rows(fd, flt, i, s.rows, row_bytes_of(s.bins), at, stage.get(), 1, err);
         at += s.rows * row_bytes_of(s.bins);
     }
-    auto tables = [&](bool next) {
-        w.raw<uint64_t>(ibfs.size());
-        for (const HibfShape& s : ibfs)
-        {
-            const std::vector<int64_t>& v = next ? s.next_ibf_id : s.bin_to_user;
-            w.raw<uint64_t>(v.size());
-            w.buf.append(reinterpret_cast<const char*>(v.data()), v.size() * 8);
-        }
-    };
-    tables(true);                                           // next_ibf_id
-    w.raw<uint64_t>(user_files.size());                     // user_bins: user_bin_filenames
-    for (const std::string& f : user_files)
-        w.str(f);
-    tables(false);                                          //            ibf_bin_to_filename_position
+    hibf_back(w, ibfs, user_files);
     flush(w);
     ::close(fd);
     if (!ok && err.empty())
         err = "write error on " + c.output_file;
     return ok;
+}
+
+// The same file for a build in parts: everything but the payloads, and the file extended to its full size, so that every piece's rows
+// have their place (payload_at[ibf] + row_begin * row bytes) whichever part is written first.  -1: `err` says why.
+int open_hibf(const Config& c, const std::vector<HibfShape>& ibfs, uint8_t hash_functions, const std::vector<std::vector<std::string>>& bin_path,
+              const std::vector<std::string>& user_files, std::vector<uint64_t>& payload_at, std::string& err)
+{
+    const int fd = ::open(c.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0)
+    {
+        err = "cannot write " + c.output_file;
+        return -1;
+    }
+    uint64_t at    = 0;
+    bool     ok    = true;
+    auto     flush = [&](Writer& w) {
+        ok = ok && pwrite_all(fd, w.buf.data(), w.buf.size(), at);
+        at += w.buf.size();
+        w.buf.clear();
+    };
+    Writer w;
+    hibf_front(w, c, bin_path, ibfs.size());
+    flush(w);
+    payload_at.assign(ibfs.size(), 0);
+    for (uint32_t i = 0; i < ibfs.size(); ++i)
+    {
+        ibf_header(w, ibfs[i].bins, ibfs[i].rows, hash_functions);
+        flush(w);
+        payload_at[i] = at;
+        at += ibfs[i].rows * row_bytes_of(ibfs[i].bins);
+    }
+    hibf_back(w, ibfs, user_files);
+    flush(w); // (behind the last payload: the file has its full size, the payloads in between read as zeros until they are written)
+    if (!ok || ::ftruncate(fd, (off_t)at) != 0)
+    {
+        err = "write error on " + c.output_file;
+        ::close(fd);
+        return -1;
+    }
+    return fd;
+}
+
+// rows [0, n_rows) of IBF `ibf` of a part's filter to byte `at` of the file; `stage` is the caller's (one per worker) and grows to a chunk
+bool save_piece(int fd, gn_filter* flt, uint32_t ibf, uint64_t n_rows, uint64_t row_bytes, uint64_t at, PinnedBlock& stage, std::string& err)
+{
+    if (!stage.reserve(chunk_rows(n_rows, row_bytes) * row_bytes))
+    {
+        err = gnhost::hip_error();
+        return false;
+    }
+    // (one writer a chunk, as save_hibf: the workers of a build in parts write side by side already)
+    if (!write_rows(fd, flt, ibf, n_rows, row_bytes, at, stage.get(), 1, err))
+    {
+        if (err.empty())
+            err = "write error on the output file";
+        return false;
+    }
+    return true;
 }
 
 } // namespace gnbuild

@@ -449,6 +449,23 @@ int gn_hashes_union(int device, const uint64_t* const* sets, const uint64_t* siz
                     uint64_t* n_union);
 int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t* set_off, uint32_t n_sets, const gn_path_entry* paths,
                            uint32_t depth);
+/* A tree built in parts (`ganon-build --hibf --hibf-memory / --hibf-devices`; no counterpart in the reference).
+ * gn_filter_create_hibf_storage: a zero-filled, STORAGE-ONLY HIBF of n_ibf IBFs without tables (ibfs[i].rows == NULL): hashes can be
+ * inserted and rows read back (gn_filter_download_rows, gn_filter_info), no stream can be created on it.  Rows are padded on the
+ * device as gn_filter_upload_hibf pads them (gn_hibf_row_stride_words).  Its IBFs need not hang together: a part of a tree is any set
+ * of its IBFs, or a range of rows of one.
+ * gn_filter_emplace_path_window: gn_filter_emplace_path for such a filter.  Set s is sets[s][0 .. set_sizes[s]), ascending, in host
+ * memory, taken by pointer; paths as above, their `ibf` numbering f's IBFs.  IBF j of f stands for rows [row_begin[j], row_begin[j] +
+ * its rows) of an IBF of total_rows[j] rows (1 .. 2^32 - 1; both arrays have one entry per IBF of f).  For each hash function the
+ * row is that of the WHOLE IBF -- hash_and_fit with total_rows[j] and countl_zero(total_rows[j]) -- and the bit is set at row -
+ * row_begin[j] only when the row lies in the piece; nothing else is touched.  With row_begin all 0 and total_rows equal to f's rows
+ * the call sets exactly the bits gn_filter_emplace_path sets.  All sets of a call go through two page-locked staging chunks of
+ * chunk_hashes hashes (0: 1 Mi), the upload of one under the kernel of the one before, one launch per chunk.  Everything is checked
+ * before anything is launched and a refused call writes nothing: GN_EINVAL for a null argument, a filter that is not an HIBF, an
+ * IBF or a bin out of range, hashes that do not fit their run, row_begin + rows > total_rows; GN_ERANGE for total_rows >= 2^32. */
+int gn_filter_create_hibf_storage(int device, uint32_t n_ibf, const gn_ibf_desc* ibfs, gn_filter** out);
+int gn_filter_emplace_path_window(gn_filter* f, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, const gn_path_entry* paths,
+                                  uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t chunk_hashes);
 
 /* `ganon-build --hibf --verify-index`: the insert read back.  Same sets, same paths, same hashes; loads where gn_filter_emplace_path ORs.
  * set s = hashes[set_off[s] .. set_off[s+1]) (host memory; any order, repeats allowed).  A hash is CONTAINED in an entry when, for at

@@ -33,7 +33,10 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --lognormal S   file i has len * exp(S * z_i) bases, z_i standard normal (seeded): `len` is the median, not every file's length
   --device LIST   passed on as `--device LIST` to every build; a list a,b,... only to the flat build (the hierarchical modes take one)
   --device-memory BYTES  passed on to the flat build: the filter is filled in row slabs when it is larger; the run reports "slabs",
-                  "passes", "hash_bytes_uploaded" and per slab its fill and write seconds"""
+                  "passes", "hash_bytes_uploaded" and per slab its fill and write seconds
+  --hibf-memory BYTES / --hibf-devices LIST  [--hibf] passed on to the hierarchical build: the tree is filled in parts when it is larger
+                  than BYTES of device rows, the parts dealt to the entries of LIST; the run reports "parts", "hash_bytes_uploaded"
+                  beside "one_pass_hash_bytes", and per part its device bytes, the sets it took and its fill and write seconds"""
 import json
 import math
 import os
@@ -45,7 +48,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hibf-memory": "", "--hibf-devices": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -106,6 +109,7 @@ if opts["--lognormal"]:
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
 device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["--device-memory", opts["--device-memory"]] if opts["--device-memory"] else [])
 device_hibf = ["--device", opts["--device"]] if opts["--device"] else []
+parts_hibf = (["--hibf-memory", opts["--hibf-memory"]] if opts["--hibf-memory"] else []) + (["--hibf-devices", opts["--hibf-devices"]] if opts["--hibf-devices"] else [])
 
 
 def flat_run(max_fp="0.05", extra=()):
@@ -144,9 +148,14 @@ def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     res = {}
     t0 = time.time()
     cmd = [exe, "-i", os.path.join(d, tsv), "-o", os.path.join(d, db), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
-           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf + (parts_hibf if db == "db.hibf" else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    m = re.search(r"filled in (\d+) parts?, (\d+) hash bytes uploaded(?: \(one pass: (\d+)\))?", p.stderr)
+    if m:
+        res["parts"], res["hash_bytes_uploaded"], res["one_pass_hash_bytes"] = int(m.group(1)), int(m.group(2)), int(m.group(3) or m.group(2))
+        res["part_bytes_sets_fill_write"] = [(int(a), int(b), float(c), float(e)) for a, b, c, e in re.findall(
+            r"^part \d+ entry \d+: (\d+) device bytes, (\d+) sets taken, filled in ([0-9.eE+-]+) s, written in ([0-9.eE+-]+) s$", p.stderr, re.M)][:64]
     m = re.search(r" - seconds: hash ([0-9.eE+-]+) union ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)", p.stderr)
     if m:
         res["hash_s"], res["union_s"], res["emplace_s"], res["write_s"] = (float(x) for x in m.groups())
