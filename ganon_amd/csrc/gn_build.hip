@@ -4,14 +4,18 @@
 //   gn_filter_emplace_split    insert a target's hashes into its run of technical bins, equal shares per bin
 //                              (create_bin_map_hash :619-653 + build :655-698: hash i of the target goes to bin
 //                              first_bin + i / hashes_per_bin)
+//   gn_stream_distinct_hashes_packed  that set packed where it lies, as blocks of deltas of fixed width (gn_packed_set.h)
 //   gn_filter_emplace_runs_window  the same rule for many runs in one call, into a filter that stands for a window of the rows of a
 //                              larger one: one launch per staging chunk, uploads under the kernels (a flat filter built in row slabs)
+//   gn_filter_emplace_packed_window  its twin for packed runs: the staging moves payload words, the kernel decodes a block per wave
 // HBM-bound integer work: a radix sort (hipCUB) over the hash array, a unique pass, an atomic-OR scatter.
 #include "gn_internal.h"
 #include <hipcub/hipcub.hpp>
 
 #include "gn_build_row.h" // gn_build_row: seqan3::interleaved_bloom_filter's hash_and_fit
 #include "gn_emplace_window.h"
+#include "gn_packed_set.h"
+#include "gn_scan.h"
 
 #include <algorithm>
 #include <string.h>
@@ -81,6 +85,7 @@ extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t c
         GN_HIP(hipMemcpy(out, s->build.d_build[0], s->build_distinct * 8, hipMemcpyDeviceToHost));
         return GN_OK;
     }
+    s->pack_words = ~0ull; // (a new set: what gn_stream_distinct_hashes_packed made of the last one is stale)
     // every read's count is at most its window count, so the slot total bounds the packed size
     uint64_t slots = 0;
     GN_HIP(hipMemcpyAsync(&slots, s->d_slot_off + n, 8, hipMemcpyDeviceToHost, s->st));
@@ -122,6 +127,161 @@ extern "C" int gn_stream_distinct_hashes(gn_stream* s, uint64_t* out, uint64_t c
     if (cap < nd)
         return gn_fail(GN_EOVERFLOW, "hash buffer too small: need %llu", nd);
     GN_HIP(hipMemcpy(out, s->build.d_build[0], nd * 8, hipMemcpyDeviceToHost));
+    return GN_OK;
+}
+
+// ---- gn_stream_distinct_hashes_packed: the sorted set, packed where it lies ------------------------------------------------------
+// One wave per block of 512 hashes, twice: the first kernel finds the block's width and payload length, a scan over the lengths gives
+// every block its place in the payload, the second kernel writes the deltas.  A lane holds 8 consecutive hashes and the last hash of
+// the lane before it, so delta e = q - 1 leads to the lane's hash q.  No global atomics: a block's words are assembled in LDS (a delta
+// may share a word with those of other lanes) and stored coalesced.
+static_assert(sizeof(gn_packed_block) == sizeof(GnPackedBlock) && offsetof(gn_packed_block, word_at) == offsetof(GnPackedBlock, word_at) &&
+                  offsetof(gn_packed_block, cnt) == offsetof(GnPackedBlock, cnt) && offsetof(gn_packed_block, width) == offsetof(GnPackedBlock, width),
+              "gn_packed_block (ganon_hip.h) is GnPackedBlock (gn_packed_set.h)");
+
+// the lane's deltas d[j] = v[q] - v[q - 1], q = 8 * lane + j, of a block of cnt hashes that starts at `v`; 0 where there is none
+__device__ __forceinline__ void gn_pack_lane_deltas(const uint64_t* __restrict__ v, uint32_t cnt, uint32_t lane, uint64_t (&d)[GN_WIN_PER_LANE])
+{
+    const uint32_t q0   = lane * GN_WIN_PER_LANE;
+    uint64_t       prev = q0 >= 1 && q0 - 1 < cnt ? v[q0 - 1] : 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = q0 + j;
+        const uint64_t x = q < cnt ? v[q] : 0;
+        d[j]             = q >= 1 && q < cnt ? x - prev : 0;
+        prev             = x;
+    }
+}
+
+__global__ __launch_bounds__(256) void gn_pack_width_kernel(const uint64_t* __restrict__ v, uint64_t n, GnPackedBlock* __restrict__ blocks,
+                                                            uint32_t* __restrict__ words, uint32_t n_blocks)
+{
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (b >= n_blocks)
+        return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t base = (uint64_t)b * GN_WIN_ITEM;
+    const uint32_t cnt  = (uint32_t)(n - base < GN_WIN_ITEM ? n - base : GN_WIN_ITEM);
+    uint64_t       d[GN_WIN_PER_LANE];
+    gn_pack_lane_deltas(v + base, cnt, lane, d);
+    uint64_t widest = 0; // (the OR of the deltas has the bit length of the largest)
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+        widest |= d[j];
+#pragma unroll
+    for (uint32_t o = 32; o >= 1; o >>= 1)
+        widest |= __shfl_xor(widest, o);
+    if (lane == 0)
+    {
+        const uint32_t width = gn_packed_bits(widest);
+        blocks[b]            = GnPackedBlock{ v[base], 0, cnt, width };
+        words[b]             = gn_packed_words(cnt, width);
+        if (b == 0)
+            words[n_blocks] = 0; // (the scan runs over one entry more: its last offset is the total)
+    }
+}
+
+__global__ __launch_bounds__(256) void gn_pack_payload_kernel(const uint64_t* __restrict__ v, uint64_t n, GnPackedBlock* __restrict__ blocks,
+                                                              const uint64_t* __restrict__ word_at, uint64_t* __restrict__ payload, uint32_t n_blocks)
+{
+    __shared__ unsigned long long lds[4][GN_WIN_ITEM];
+    const uint32_t b    = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const bool     live = b < n_blocks; // (every wave of the workgroup reaches both barriers)
+    const uint64_t base = (uint64_t)b * GN_WIN_ITEM;
+    const uint32_t cnt = live ? blocks[b].cnt : 0, width = live ? blocks[b].width : 0, n_words = live ? gn_packed_words(cnt, width) : 0;
+    const uint64_t at = live ? word_at[b] : 0;
+    for (uint32_t w = lane; w < n_words; w += 64)
+        lds[wv][w] = 0;
+    __syncthreads();
+    if (live && width)
+    {
+        uint64_t d[GN_WIN_PER_LANE];
+        gn_pack_lane_deltas(v + base, cnt, lane, d);
+#pragma unroll
+        for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+        {
+            const uint32_t q = lane * GN_WIN_PER_LANE + j;
+            if (q < 1 || q >= cnt)
+                continue;
+            const uint32_t bit = (q - 1) * width, w = bit >> 6, off = bit & 63u; // (gn_packed_put, with ORs that other lanes may share)
+            atomicOr(&lds[wv][w], (unsigned long long)(d[j] << off));
+            if (off + width > 64)
+                atomicOr(&lds[wv][w + 1], (unsigned long long)(d[j] >> (64u - off)));
+        }
+    }
+    __syncthreads();
+    for (uint32_t w = lane; w < n_words; w += 64)
+        payload[at + w] = lds[wv][w];
+    if (live && lane == 0)
+        blocks[b].word_at = at;
+}
+
+static int gn_pack_reserve(gn_stream* s, uint64_t n_blocks)
+{
+    if (s->pack.cap >= n_blocks)
+        return GN_OK;
+    GnPackBufs     b;
+    const uint64_t cap = n_blocks + n_blocks / 8 + 64;
+    s->pack            = GnPackBufs{}; // free before malloc
+    GN_HIP(b.d_blocks.alloc(cap));
+    GN_HIP(b.d_words.alloc(cap + 1));
+    GN_HIP(b.d_off.alloc(cap + 1));
+    GN_HIP(gn_scan_counts(nullptr, b.tmp_bytes, b.d_words.get(), b.d_off.get(), (int)(cap + 1), s->st));
+    GN_HIP(b.d_tmp.alloc(b.tmp_bytes));
+    b.cap   = cap;
+    s->pack = std::move(b);
+    return GN_OK;
+}
+
+extern "C" int gn_stream_distinct_hashes_packed(gn_stream* s, gn_packed_block* blocks, uint64_t cap_blocks, uint64_t* payload, uint64_t cap_words,
+                                                uint64_t* n_distinct, uint64_t* n_blocks, uint64_t* n_words)
+{
+    if (!s || !n_distinct || !n_blocks || !n_words)
+        return gn_fail(GN_EINVAL, "null argument");
+    *n_distinct = *n_blocks = *n_words = 0;
+    uint64_t nd = 0;
+    int      rc = gn_stream_distinct_hashes(s, nullptr, 0, &nd); // (sorts and uniques, or finds the set of an earlier call)
+    if (rc)
+        return rc;
+    *n_distinct = nd;
+    if (nd == 0)
+        return GN_OK;
+    if (s->pack_words == ~0ull)
+    {
+        const uint64_t nb = gn_packed_max_blocks(nd); // (one set: every block but the last is full)
+        rc                = gn_pack_reserve(s, nb);
+        if (rc)
+            return rc;
+        const dim3 grid((unsigned)((nb + 3) / 4));
+        hipLaunchKernelGGL(gn_pack_width_kernel, grid, dim3(256), 0, s->st, (const uint64_t*)s->build.d_build[0], nd, s->pack.d_blocks.get(),
+                           s->pack.d_words.get(), (uint32_t)nb);
+        GN_HIP(hipGetLastError());
+        size_t tmp = s->pack.tmp_bytes;
+        GN_HIP(gn_scan_counts(s->pack.d_tmp, tmp, s->pack.d_words.get(), s->pack.d_off.get(), (int)(nb + 1), s->st));
+        // the payload takes the sort's second buffer: it holds nd hashes or more, a packed set fewer words than hashes
+        hipLaunchKernelGGL(gn_pack_payload_kernel, grid, dim3(256), 0, s->st, (const uint64_t*)s->build.d_build[0], nd, s->pack.d_blocks.get(),
+                           (const uint64_t*)s->pack.d_off, s->build.d_build[1].get(), (uint32_t)nb);
+        GN_HIP(hipGetLastError());
+        uint64_t total = 0;
+        GN_HIP(hipMemcpyAsync(&total, s->pack.d_off + nb, 8, hipMemcpyDeviceToHost, s->st));
+        GN_HIP(hipStreamSynchronize(s->st));
+        s->pack_blocks = nb;
+        s->pack_words  = total;
+    }
+    *n_blocks = s->pack_blocks;
+    *n_words  = s->pack_words;
+    if (!blocks && !payload)
+        return GN_OK;
+    if (!blocks || (!payload && s->pack_words))
+        return gn_fail(GN_EINVAL, "null argument");
+    if (cap_blocks < s->pack_blocks || cap_words < s->pack_words)
+        return gn_fail(GN_EOVERFLOW, "packed buffers too small: need %llu blocks and %llu words", (unsigned long long)s->pack_blocks,
+                       (unsigned long long)s->pack_words);
+    GN_HIP(hipMemcpy(blocks, s->pack.d_blocks, s->pack_blocks * sizeof(GnPackedBlock), hipMemcpyDeviceToHost));
+    if (s->pack_words)
+        GN_HIP(hipMemcpy(payload, s->build.d_build[1], s->pack_words * 8, hipMemcpyDeviceToHost));
     return GN_OK;
 }
 
@@ -310,6 +470,173 @@ extern "C" int gn_filter_emplace_runs_window(gn_filter* f, const uint64_t* const
     }
     GN_HIP(g.d_runs.upload(dev.data(), dev.size()));
     const int rc = gn_runs_window_rounds(f, g, runs, run_sizes, n_runs, total_rows, row_begin, chunk, cap_items);
+    // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
+    const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
+    if (rc != GN_OK)
+        return rc;
+    GN_HIP(e0);
+    GN_HIP(e1);
+    return GN_OK;
+}
+
+// ---- gn_filter_emplace_packed_window: packed runs into a slab of rows ----------------------------------------------------------------
+// The twin of gn_filter_emplace_runs_window for runs packed as gn_packed_set.h says: the same filter, the same bins and rows, the same
+// bits.  One wave per block.  Lane L unpacks deltas 8L .. 8L + 7 -- `width` bytes of the staged payload, adjacent lanes adjacent bytes --
+// and sums them; an inclusive scan of the lane sums across the wave, less the lane's own sum, plus `first` is hash 8L, and the lane's
+// deltas lead from it to hashes 8L + 1 .. 8L + 7.  From there it is gn_emplace_window_kernel with q = 8L + j.
+__global__ __launch_bounds__(256) void gn_emplace_packed_window_kernel(uint64_t* rows, uint64_t S_total, uint32_t shift, uint32_t W, uint32_t h,
+                                                                       uint32_t row_begin, uint32_t n_rows, const uint64_t* __restrict__ stage,
+                                                                       const GnPackedItem* __restrict__ items, uint32_t n_items,
+                                                                       const GnRunDev* __restrict__ runs)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t     lane = threadIdx.x & 63u;
+    const GnPackedItem it   = items[item];
+    const GnRunDev     run  = runs[it.run];
+    const uint64_t*    words = stage + it.stage_at;
+    uint64_t           d[GN_WIN_PER_LANE], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t e = lane * GN_WIN_PER_LANE + j;
+        d[j]             = e + 1 < it.cnt ? gn_packed_delta(words, e, it.width) : 0; // (a delta past the block's last is not read)
+        sum += d[j];
+    }
+    uint64_t incl = sum;
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1)
+    {
+        const uint64_t below = __shfl_up(incl, o);
+        if (lane >= o)
+            incl += below;
+    }
+    uint64_t       v    = it.first + (incl - sum);
+    const uint64_t b0   = it.begin / run.per_bin; // (wave-uniform: once per item)
+    const uint64_t r0   = it.begin - b0 * run.per_bin;
+    const uint32_t bin0 = run.first_bin + (uint32_t)b0;
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = lane * GN_WIN_PER_LANE + j;
+        if (q < it.cnt)
+        {
+            const uint32_t bin  = gn_window_item_bin(bin0, r0, q, run.per_bin);
+            GnGlobalWord*  word = (GnGlobalWord*)rows + (bin >> 6);
+            const uint64_t bit  = 1ULL << (bin & 63);
+            for (uint32_t i = 0; i < h; ++i)
+            {
+                uint32_t local;
+                if (gn_window_local(gn_build_row(v, i, shift, S_total), row_begin, n_rows, &local))
+                    (void)__hip_atomic_fetch_or(word + (uint64_t)local * W, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        v += d[j];
+    }
+}
+
+namespace
+{
+struct GnPackedStage // everything a call holds; freed when the call returns
+{
+    GnStreamPair           streams;
+    GnPinned<uint64_t>     h_stage[2];
+    GnPinned<GnPackedItem> h_items[2];
+    GnDev<uint64_t>        d_stage[2];
+    GnDev<GnPackedItem>    d_items[2];
+    GnDev<GnRunDev>        d_runs;
+};
+} // namespace
+
+// the rounds of gn_runs_window_rounds: what is gathered into the page-locked chunk is the payload of the chunk's blocks
+static int gn_packed_window_rounds(gn_filter* f, GnPackedStage& g, const GnPackedBlock* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                   uint32_t n_runs, uint64_t total_rows, uint64_t row_begin, uint64_t chunk, uint64_t cap_items)
+{
+    const GnIbfHost&          ib = f->ibf;
+    std::vector<GnPackedItem> items;
+    GnPackedCursor            cur;
+    for (uint32_t c = 0;; ++c)
+    {
+        const uint32_t b = c & 1u;
+        GN_HIP(hipStreamSynchronize(g.streams.st[b]));
+        uint64_t       words   = 0;
+        const uint32_t n_items = (uint32_t)gn_packed_next_chunk(blocks, n_blocks, n_runs, cur, chunk, cap_items, items, &words);
+        if (n_items == 0)
+            return GN_OK;
+        for (const GnPackedItem& it : items)
+            if (const uint32_t w = gn_packed_words(it.cnt, it.width))
+                memcpy(g.h_stage[b] + it.stage_at, payload[it.run] + blocks[it.run][it.block].word_at, (size_t)w * 8);
+        memcpy(g.h_items[b].get(), items.data(), items.size() * sizeof(GnPackedItem));
+        if (words)
+            GN_HIP(hipMemcpyAsync(g.d_stage[b], g.h_stage[b], words * 8, hipMemcpyHostToDevice, g.streams.st[b]));
+        GN_HIP(hipMemcpyAsync(g.d_items[b], g.h_items[b], items.size() * sizeof(GnPackedItem), hipMemcpyHostToDevice, g.streams.st[b]));
+        hipLaunchKernelGGL(gn_emplace_packed_window_kernel, dim3((n_items + 3) / 4), dim3(256), 0, g.streams.st[b], ib.d_rows.get(), total_rows,
+                           (uint32_t)__builtin_clzll(total_rows), (uint32_t)ib.Ws, ib.h, (uint32_t)row_begin, (uint32_t)ib.S, (const uint64_t*)g.d_stage[b],
+                           (const GnPackedItem*)g.d_items[b], n_items, (const GnRunDev*)g.d_runs);
+        GN_HIP(hipGetLastError());
+    }
+}
+
+extern "C" int gn_filter_emplace_packed_window(gn_filter* f, const gn_packed_block* const* blocks_abi, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                               const uint32_t* first_bin, const uint64_t* hashes_per_bin, uint32_t n_runs, uint64_t total_rows, uint64_t row_begin,
+                                               uint64_t chunk_words)
+{
+    static const char* const who = "gn_filter_emplace_packed_window";
+    const GnPackedBlock* const* blocks = reinterpret_cast<const GnPackedBlock* const*>(blocks_abi);
+    if (!f || f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs a flat IBF filter", who);
+    const GnIbfHost& ib = f->ibf;
+    if (total_rows == 0 || total_rows > 0xFFFFFFFFull)
+        return gn_fail(GN_ERANGE, "%s: a filter of %llu rows, 1 .. 2^32 - 1 are supported", who, (unsigned long long)total_rows);
+    if (row_begin > total_rows || ib.S > total_rows - row_begin)
+        return gn_fail(GN_EINVAL, "%s: rows %llu .. %llu of a filter of %llu rows", who, (unsigned long long)row_begin, (unsigned long long)(row_begin + ib.S),
+                       (unsigned long long)total_rows);
+    if (n_runs == 0)
+        return GN_OK;
+    if (!blocks || !n_blocks || !payload || !first_bin || !hashes_per_bin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    // every block is looked at and every bin a hash can reach is checked before anything is launched (the local row is below S by the
+    // window test; a block's words are read only as far as cnt and width say)
+    std::vector<GnRunDev> dev(n_runs);
+    uint64_t              total = 0, words = 0;
+    for (uint32_t r = 0; r < n_runs; ++r)
+    {
+        dev[r] = GnRunDev{ hashes_per_bin[r] ? hashes_per_bin[r] : 1, first_bin[r], 0 };
+        if (n_blocks[r] == 0)
+            continue;
+        if (!blocks[r] || hashes_per_bin[r] == 0)
+            return gn_fail(GN_EINVAL, "%s: run %u: bad argument", who, r);
+        uint64_t size = 0;
+        for (uint64_t i = 0; i < n_blocks[r]; ++i)
+        {
+            const GnPackedBlock& b = blocks[r][i];
+            if (b.cnt == 0 || b.cnt > GN_WIN_ITEM || b.width > 64 || (gn_packed_words(b.cnt, b.width) && !payload[r]))
+                return gn_fail(GN_EINVAL, "%s: run %u: block %llu of %u hashes at %u bits", who, r, (unsigned long long)i, b.cnt, b.width);
+            size += b.cnt;
+            words += gn_packed_words(b.cnt, b.width);
+        }
+        if ((uint64_t)first_bin[r] + (size - 1) / hashes_per_bin[r] >= ib.B)
+            return gn_fail(GN_EINVAL, "%s: run %u: bins %u.. exceed the filter's %llu bins", who, r, first_bin[r], (unsigned long long)ib.B);
+        total += n_blocks[r];
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    // (a chunk holds any block: a cap below a block's most words is raised to it)
+    const uint64_t chunk     = std::max<uint64_t>(std::min<uint64_t>(chunk_words ? chunk_words : GN_PACKED_CHUNK, words), GN_PACKED_MAX_WORDS);
+    const uint64_t cap_items = std::min<uint64_t>(chunk / 16 + 16, total); // (a chunk of narrow blocks closes at this many items)
+    GnPackedStage  g;
+    for (int b = 0; b < 2; ++b)
+    {
+        GN_HIP(hipStreamCreateWithFlags(&g.streams.st[b], hipStreamNonBlocking));
+        GN_HIP(g.h_stage[b].alloc(chunk));
+        GN_HIP(g.h_items[b].alloc(cap_items));
+        GN_HIP(g.d_stage[b].alloc(chunk));
+        GN_HIP(g.d_items[b].alloc(cap_items));
+    }
+    GN_HIP(g.d_runs.upload(dev.data(), dev.size()));
+    const int rc = gn_packed_window_rounds(f, g, blocks, n_blocks, payload, n_runs, total_rows, row_begin, chunk, cap_items);
     // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
     const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
     if (rc != GN_OK)

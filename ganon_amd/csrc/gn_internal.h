@@ -10,6 +10,7 @@
 #include "../../include/ganon_hip.h"
 #include "../../include/ganon_ibf_hash.h"
 #include "gn_devmem.h"
+#include "gn_packed_set.h"
 
 #define GN_MAX_CHUNKS 64 // pipeline chunks per batch (minimiser on the side stream || count on the main stream)
 // candidate-driven select of the generic count kernel: targets with more bins than this are scanned from a list
@@ -351,6 +352,18 @@ struct GnBuildBufs
     uint64_t                  cap = 0; // hashes d_build[] hold (0: no buffers)
 };
 
+// ... and what gn_stream_distinct_hashes_packed adds to them, allocated by its first call: the blocks of the packed set, their payload
+// word counts and offsets (one entry more than blocks: the total) and the scan's scratch.  The payload itself goes to d_build[1].
+struct GnPackBufs
+{
+    GnDev<GnPackedBlock> d_blocks;
+    GnDev<uint32_t>      d_words;
+    GnDev<uint64_t>      d_off;
+    GnDev<uint8_t>       d_tmp;
+    size_t               tmp_bytes = 0;
+    uint64_t             cap = 0; // blocks the buffers hold (0: no buffers)
+};
+
 // HIBF sort buffers (gn_hibf.hip), sized to the stream's match_cap
 struct GnHibfSortBufs
 {
@@ -462,6 +475,8 @@ struct gn_stream
     GnDev<uint32_t>           d_long_scratch;
     GnBuildBufs         build;
     uint64_t            build_distinct = ~0ull; // result of the last gn_stream_distinct_hashes on the resident hashes (~0: none)
+    GnPackBufs          pack;
+    uint64_t            pack_blocks = 0, pack_words = ~0ull; // the packed form of that set in pack.d_blocks / build.d_build[1] (~0: not packed yet)
     // device-side pre-pass of filter_matches (gn_postfilter.hip); off unless gn_stream_set_postfilter enabled it
     bool                pf_on = false;
     double              pf_rel_filter = 0, pf_fpr_query = 1;

@@ -14,6 +14,7 @@ READ_OK, READ_SMALL, READ_BIG = 0, 1, 2
 FILL_3_OF_8 = 0x38  # gn_filter_fill_random: density 3/8 (GN_FILL_3_OF_8)
 FILL_3_OF_16 = 0x3F  # density 3/16: m0 & m1 & (m2 | m3) (GN_FILL_3_OF_16)
 MATCH_DTYPE = np.dtype([("read", "<u4"), ("target", "<u4"), ("count", "<u4")])
+PACKED_BLOCK_DTYPE = np.dtype([("first", "<u8"), ("word_at", "<u8"), ("cnt", "<u4"), ("width", "<u4")])  # gn_packed_block
 
 # every symbol include/ganon_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_filter_upload_hibf", "gn_filter_emplace",
@@ -35,7 +36,8 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_stream_upload_text_pair_devices", "gn_hashes_union", "gn_filter_emplace_path", "gn_filter_probe_path", "gn_filter_probe_paths_shared",
                "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_fold_ibf", "gn_filter_extend_path",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table",
-               "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window"]
+               "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window",
+               "gn_stream_distinct_hashes_packed", "gn_filter_emplace_packed_window"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -163,6 +165,8 @@ def load_library():
     L.gn_stream_distinct_hashes.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_split.argtypes = [vp, vp, u64, u32, u64]
     L.gn_filter_emplace_runs_window.argtypes = [vp, vp, vp, vp, vp, u32, u64, u64, u64]
+    L.gn_stream_distinct_hashes_packed.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.gn_filter_emplace_packed_window.argtypes = [vp, vp, vp, vp, vp, vp, u32, u64, u64, u64]
     L.gn_hashes_union.argtypes = [C.c_int, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
     L.gn_filter_create_hibf_storage.argtypes = [i32, u32, C.POINTER(IbfDesc), C.POINTER(vp)]
@@ -630,6 +634,19 @@ class HipFilter:
         assert len(first) == len(per) == len(runs)
         _check(load_library().gn_filter_emplace_runs_window(self._h, ptrs, _p(sizes), _p(first), _p(per), len(runs), total_rows, row_begin, chunk_hashes))
 
+    def emplace_packed_window(self, runs, first_bins, hashes_per_bin, total_rows: int, row_begin: int, chunk_words: int = 0) -> None:
+        """gn_filter_emplace_packed_window: emplace_runs_window for packed runs.  runs[r] = (blocks, payload): PACKED_BLOCK_DTYPE records
+        whose word_at count from payload[0], and the uint64 payload words"""
+        blocks = [np.ascontiguousarray(b, dtype=PACKED_BLOCK_DTYPE) for b, _ in runs]
+        words = [np.ascontiguousarray(w, dtype=np.uint64) for _, w in runs]
+        bptr = (C.c_void_p * max(len(runs), 1))(*[a.ctypes.data for a in blocks])
+        wptr = (C.c_void_p * max(len(runs), 1))(*[a.ctypes.data for a in words])
+        n_blocks = np.array([len(a) for a in blocks], dtype=np.uint64)
+        first = np.ascontiguousarray(first_bins, dtype=np.uint32)
+        per = np.ascontiguousarray(hashes_per_bin, dtype=np.uint64)
+        assert len(first) == len(per) == len(runs)
+        _check(load_library().gn_filter_emplace_packed_window(self._h, bptr, _p(n_blocks), wptr, _p(first), _p(per), len(runs), total_rows, row_begin, chunk_words))
+
     def emplace_path(self, sets: Sequence[np.ndarray], paths: np.ndarray) -> None:
         """gn_filter_emplace_path: sets[s] (ascending uint64) along paths[s] (PATH_DTYPE, shape [len(sets), depth]) of an HIBF"""
         paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
@@ -951,6 +968,17 @@ class HipStream:
         out = np.zeros(max(int(n.value), 1), dtype=np.uint64)
         _check(L.gn_stream_distinct_hashes(self._h, _p(out), len(out), C.byref(n)))
         return out[: int(n.value)]
+
+    def distinct_hashes_packed(self):
+        """that set packed on the device (gn_stream_distinct_hashes_packed) -> (hashes, blocks as PACKED_BLOCK_DTYPE, payload words)"""
+        L = load_library()
+        n, nb, nw = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(L.gn_stream_distinct_hashes_packed(self._h, None, 0, None, 0, C.byref(n), C.byref(nb), C.byref(nw)))
+        blocks = np.zeros(max(int(nb.value), 1), dtype=PACKED_BLOCK_DTYPE)
+        words = np.zeros(max(int(nw.value), 1), dtype=np.uint64)
+        _check(L.gn_stream_distinct_hashes_packed(self._h, blocks.ctypes.data_as(C.c_void_p), int(nb.value), _p(words), int(nw.value), C.byref(n), C.byref(nb),
+                                                  C.byref(nw)))
+        return int(n.value), blocks[: int(nb.value)], words[: int(nw.value)]
 
     def fetch_read_info(self):
         """-> (n_hashes u32[n], status u8[n]) only"""

@@ -11,8 +11,9 @@
 // piece), the classify-side minimiser kernels hash them, a radix sort + unique gives the file's hash SET
 // (gn_stream_distinct_hashes), the filter is created empty in HBM, filled by an atomic-OR scatter
 // (gn_filter_emplace_runs_window) and streamed to the file -- whole when it fits what a device may hold, otherwise in slabs of rows
-// over the entries of --device (build_slabs.cpp).  The host parses FASTA, keeps the hash sets (RAM, not `.min` files:
-// --tmp-output-folder is accepted and validated, nothing is written there) and does the sizing arithmetic.
+// over the entries of --device (build_slabs.cpp).  The host parses FASTA, keeps the hash sets and does the sizing arithmetic.  The sets
+// are held in RAM at 8 bytes a hash (--hash-sets raw, the default; not `.min` files), or packed by the device as deltas of fixed width
+// (csrc/gn_packed_set.h) in RAM (packed) or in files of --tmp-output-folder that live as long as the command (spilled).
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
 //
 // The hierarchical modes (this project's extensions, like --device) take the same hash sets: --hibf (build_hibf.cpp),
@@ -36,10 +37,12 @@
 #include <fstream>
 #include <iomanip>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <sstream>
 #include <thread>
+#include <unistd.h>
 
 using namespace gnbuild;
 
@@ -100,6 +103,11 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         if (on && c.devices.size() > 1)
             return say(std::string("--device takes one device with ") + mode + " (only a flat .ibf is built over a device list)");
     }
+    if (c.hash_sets != "raw" && c.hash_sets != "packed" && c.hash_sets != "spilled")
+        return say("--hash-sets has to be raw, packed or spilled");
+    for (const auto& [on, mode] : { std::pair<bool, const char*>{ c.update_given, "--update" }, { c.verify_given, "--verify-index" }, { c.hibf, "--hibf" } })
+        if (on && c.hash_sets != "raw")
+            return say(std::string("--hash-sets ") + c.hash_sets + " cannot be used with " + mode + " (unions, sketches and probes read raw sets; only a flat .ibf is built from packed ones)");
     if (c.device_memory_given && c.device_memory == 0)
         return say("--device-memory has to be > 0");
     // the hierarchical build in parts has switches of its own (a tree is cut by IBF and by padded device rows, not by file rows)
@@ -232,6 +240,8 @@ void print_config(const Config& c) // Config.hpp:110-133
     }
     if (c.device_memory_given)
         std::cerr << "--device-memory     " << c.device_memory << '\n';
+    if (c.hash_sets != "raw")
+        std::cerr << "--hash-sets         " << c.hash_sets << '\n';
     if (c.hibf)
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
     if (c.hibf_memory_given)
@@ -272,7 +282,8 @@ const char* kHelp =
     "  -f, --filter-size arg        Filter size (MB) [mutually exclusive --max-fp]\n"
     "  -j, --mode arg               mode to build filter [avg, smaller, smallest, faster, fastest]. Default: avg\n"
     "  -y, --min-length arg         min. sequence length (bp) to keep. 0 to keep all. Default: 0\n"
-    "  -m, --tmp-output-folder arg  Folder to write temporary files (accepted; this build keeps the hashes in memory)\n"
+    "  -m, --tmp-output-folder arg  Folder to write temporary files (only --hash-sets spilled writes there; otherwise the hashes\n"
+    "                               stay in memory)\n"
     "  -t, --threads arg            Number of threads (parser threads, one device stream each)\n"
     "      --device arg             HIP device index. Default: 0.  A list a,b,... (an index may repeat) deals the row slabs of a flat\n"
     "                               filter to its entries, one worker each, and the hashing threads to the devices; not with --hibf\n"
@@ -280,6 +291,12 @@ const char* kHelp =
     "                               that is filled in slabs of rows, each one more pass over the hash sets (which stay in host\n"
     "                               memory), and written slab by slab: the same file.  Default: what the device has free when\n"
     "                               filling starts, less staging and a reserve, shared among the entries that name it; not with --hibf\n"
+    "      --hash-sets arg          how a flat build keeps the targets' hash sets between hashing and filling: raw (8 bytes a hash in\n"
+    "                               host memory), packed (deltas of fixed width in blocks of 512 hashes, packed by the device where\n"
+    "                               a set is born and decoded inside the insert; in host memory) or spilled (packed, in one file per\n"
+    "                               hashing thread in --tmp-output-folder, else the output's folder: appended to while hashing,\n"
+    "                               mapped for the passes, removed when the command ends).  The same file.  Default: raw; not with\n"
+    "                               --hibf, --update or --verify-index\n"
     "      --hibf                   Write a hierarchical filter (raptor 3.0.1 index, one user bin per target) sized from\n"
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
@@ -382,7 +399,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -483,6 +500,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.devices = device_list("--device"), c.device = c.devices[0];
         if (vals.count("--device-memory"))
             c.device_memory = u("--device-memory", ~0ull), c.device_memory_given = true;
+        if (vals.count("--hash-sets"))
+            c.hash_sets = vals["--hash-sets"];
         if (vals.count("--hibf-devices"))
             c.hibf_devices = device_list("--hibf-devices"), c.hibf_devices_given = true;
         if (vals.count("--hibf-memory"))
@@ -496,6 +515,16 @@ int parse_args(int argc, char** argv, Config& c)
         std::cerr << "Argument '" << e.what() << "' failed to parse" << std::endl;
         return 2;
     }
+    return 0;
+}
+
+// the process's anonymous resident memory as /proc/self/status gives it (0 where it does not)
+uint64_t rss_anon_kb()
+{
+    std::ifstream in("/proc/self/status");
+    for (std::string line; std::getline(in, line);)
+        if (line.rfind("RssAnon:", 0) == 0)
+            return std::stoull(line.substr(8));
     return 0;
 }
 
@@ -548,22 +577,27 @@ std::vector<Target> read_input_file(const Config& c, Totals& totals)
 }
 
 // count_hashes (:184-249) for the targets this thread draws from the shared cursor
+// (arena: --hash-sets packed|spilled -- this thread's, number arena_no; the files' sets are packed and their payload goes there)
 void hash_targets(const Config& c, int device, std::vector<Target>& targets, std::atomic<size_t>& next, Totals& totals, std::string& fatal,
-                  std::mutex& log_mutex)
+                  std::mutex& log_mutex, SetArena* arena, uint32_t arena_no)
 {
     try
     {
         gnhost::Hasher    hasher(device, c.kmer_size, c.window_size);
         std::string       ids;
         gnhost::ByteBuf   seq;
+        gnhost::PackedFile packed;
         for (;;)
         {
             const size_t t = next.fetch_add(1);
             if (t >= targets.size())
                 break;
             Target& tg = targets[t];
+            tg.arena   = arena_no;
             for (const std::string& file : tg.files)
             {
+                if (arena)
+                    packed.clear();
                 std::vector<uint64_t> file_hashes;
                 unsigned              flushes = 0;
                 try
@@ -582,10 +616,18 @@ void hash_targets(const Config& c, int device, std::vector<Target>& targets, std
                         }
                         totals.sequences++;
                         totals.length_bp += seq.size();
-                        hasher.add(seq.data(), seq.size(), file_hashes, flushes);
+                        if (arena)
+                            hasher.add(seq.data(), seq.size(), packed);
+                        else
+                            hasher.add(seq.data(), seq.size(), file_hashes, flushes);
                     }
-                    hasher.flush(file_hashes, flushes);
-                    hasher.flush_short(file_hashes, flushes);
+                    if (arena)
+                        hasher.flush(packed), hasher.flush_short(packed);
+                    else
+                    {
+                        hasher.flush(file_hashes, flushes);
+                        hasher.flush_short(file_hashes, flushes);
+                    }
                 }
                 catch (const gnhost::ParseError& e)
                 {
@@ -596,6 +638,17 @@ void hash_targets(const Config& c, int device, std::vector<Target>& targets, std
                     std::vector<uint64_t> discard;
                     hasher.flush(discard, dummy);
                     hasher.flush_short(discard, dummy);
+                    continue;
+                }
+                if (arena) // the file's blocks behind the target's, its payload behind the arena's words
+                {
+                    packed.finish();
+                    const uint64_t base = arena->words();
+                    arena->append(packed.payload.data(), packed.payload.size());
+                    for (GnPackedBlock b : packed.blocks)
+                        b.word_at += base, tg.blocks.push_back(b);
+                    tg.count += packed.hashes;
+                    tg.file_ends.push_back(tg.count);
                     continue;
                 }
                 if (flushes > 1) // several device batches: their sets still have to be united
@@ -642,6 +695,10 @@ bool run(Config c)
     if (targets.empty() && !remove_only)
         return fail("No valid input files");
 
+    // --hash-sets packed|spilled: one arena per hashing thread; they live until the command ends (a spilled one's file goes with it)
+    const bool                             packed_sets = c.hash_sets != "raw";
+    std::vector<std::unique_ptr<SetArena>> arenas;
+
     counting.start();
     if (!targets.empty())
     {
@@ -653,9 +710,21 @@ bool run(Config c)
         std::atomic<size_t>      next{ 0 };
         std::string              fatal;
         std::mutex               log_mutex;
+        try
+        {
+            for (unsigned i = 0; packed_sets && i < nt; ++i)
+                arenas.emplace_back(c.hash_sets == "spilled" ? new SetArena((fs::path(output_folder(c)) / (fs::path(c.output_file).filename().string() + ".hashsets." +
+                                                                                                         std::to_string(::getpid()) + "." + std::to_string(i) + ".tmp"))
+                                                                                .string())
+                                                             : new SetArena());
+        }
+        catch (const std::exception& e)
+        {
+            return fail(e.what());
+        }
         for (unsigned i = 0; i < nt; ++i)
             th.emplace_back(hash_targets, std::cref(c), c.devices[i % c.devices.size()], std::ref(targets), std::ref(next), std::ref(per[i]), std::ref(fatal),
-                            std::ref(log_mutex));
+                            std::ref(log_mutex), packed_sets ? arenas[i].get() : nullptr, i);
         for (auto& t : th)
             t.join();
         if (!fatal.empty())
@@ -676,13 +745,38 @@ bool run(Config c)
     if (c.hibf)
         return run_hibf(c, targets, totals, whole, counting);
 
+    std::vector<const uint64_t*> arena_words;
+    if (c.verbose || packed_sets)
+    {
+        uint64_t hashes = 0, blocks = 0, words = 0;
+        for (const Target& t : targets)
+            hashes += n_hashes(t), blocks += t.blocks.size();
+        try
+        {
+            for (auto& a : arenas)
+                arena_words.push_back(a->data()), words += a->words();
+        }
+        catch (const std::exception& e)
+        {
+            return fail(e.what());
+        }
+        if (c.verbose)
+        {
+            std::cerr << "hash sets: " << hashes << " hashes held " << c.hash_sets << " in " << (packed_sets ? gn_packed_bytes(blocks, words) : hashes * 8)
+                      << " bytes (8 x hashes = " << hashes * 8 << " bytes)";
+            if (c.hash_sets == "spilled")
+                std::cerr << ", " << arenas.size() << " files in " << output_folder(c);
+            std::cerr << '\n' << "RssAnon after hashing: " << rss_anon_kb() << " kB" << std::endl;
+        }
+    }
+
     sizing.start();
     IbfParams p;
     p.kmer_size   = c.kmer_size;
     p.window_size = c.window_size;
     std::vector<uint64_t> counts;
     for (const Target& t : targets)
-        counts.push_back(t.hashes.size());
+        counts.push_back(n_hashes(t));
     gnbuild::choose_capacity(c.max_fp, c.filter_size, counts, c.hash_functions, c.mode, p);
     if (p.n_bins != 0)
         gnbuild::true_fp(counts, p);
@@ -721,7 +815,7 @@ bool run(Config c)
                   << " hash function(s): --filter-size / --max-fp do not fit " << targets.size() << " target(s)" << std::endl;
         return false;
     }
-    if (!fill_and_save_flat(FlatFill{ c, p, targets, bins, shares }, filling, writing))
+    if (!fill_and_save_flat(FlatFill{ c, p, targets, bins, shares, packed_sets ? &arena_words : nullptr }, filling, writing))
         return false;
     whole.stop();
 

@@ -8,6 +8,9 @@
 #include "device_sink.hpp"
 #include "hibf_build_parts.hpp"
 #include "hibf_paths.hpp"
+#include "set_arena.hpp"
+
+#include "../csrc/gn_packed_set.h"
 
 #include "ganon_hip.h"
 
@@ -41,6 +44,8 @@ struct Config // Config.hpp:10-27
     std::vector<int> devices = { 0 }; // (--device a,b,...: the flat build deals row slabs to the entries; an entry may repeat)
     uint64_t    device_memory = 0;    // (--device-memory: most bytes of filter rows on a list entry at one time; 0 = from what is free)
     bool        device_memory_given = false;
+    std::string hash_sets = "raw";    // (--hash-sets: how the flat build keeps the hash sets between hashing and filling -- raw: 8 bytes a hash in
+                                      //  memory; packed: csrc/gn_packed_set.h in memory; spilled: the same in files of output_folder())
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    hibf_memory = 0; // (--hibf-memory: most device bytes of IBF rows on an entry of hibf_devices at one time; 0 = from what is free)
     bool        hibf_memory_given = false, hibf_devices_given = false;
@@ -67,7 +72,18 @@ struct Target
     std::vector<std::string> files;
     std::vector<uint64_t>    hashes; // per file: its distinct hashes, ascending; files behind each other (:236-238)
     std::vector<uint64_t>    file_ends; // where each file's hashes end in `hashes` (--hibf unites the files of a target)
+    // --hash-sets packed|spilled: `hashes` stays empty; the target keeps its count and the blocks of its files' packed sets behind each
+    // other, whose word_at count from the start of arena `arena` (the one of the thread that hashed the target)
+    uint64_t                   count = 0;
+    std::vector<GnPackedBlock> blocks;
+    uint32_t                   arena = 0;
 };
+
+// how many hashes a target has, however its sets are kept
+inline uint64_t n_hashes(const Target& t)
+{
+    return t.blocks.empty() ? t.hashes.size() : t.count;
+}
 
 // a target's hashes as the pooler (hibf_pool.hpp) asks for a set
 inline std::pair<const uint64_t*, uint64_t> hash_set(const Target& t)
@@ -215,6 +231,7 @@ struct FlatFill
     const std::vector<Target>&  targets;
     const std::vector<BinSpan>& bins;
     const std::vector<uint64_t>& shares; // hashes per bin of each target (lay_out_bins)
+    const std::vector<const uint64_t*>* arenas = nullptr; // --hash-sets packed|spilled: the arenas' words (Target::arena); null: raw sets
 };
 bool fill_and_save_flat(const FlatFill& w, Lap& filling, Lap& writing);
 // (build_slabs.cpp) most bytes of rows on a list entry at one time when the user names none: the smallest share of free memory over the

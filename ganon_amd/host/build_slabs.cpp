@@ -4,7 +4,9 @@
 // list entry takes its slabs in ascending order -- an empty storage-only filter of the slab's rows, every target's hashes through the
 // windowed insert (gn_filter_emplace_runs_window: the rows are those of the whole filter, a slab takes the bits of the rows it holds),
 // the rows streamed to their place in the file, the filter freed.  The hash sets stay in host memory and are read by all workers; every
-// slab is one more pass over them.  The file is byte for byte the one-pass build's.
+// slab is one more pass over them.  The file is byte for byte the one-pass build's.  With --hash-sets packed|spilled the sets are packed
+// (csrc/gn_packed_set.h) in the hashing threads' arenas, in memory or in mapped files, and go through gn_filter_emplace_packed_window: a
+// pass uploads the payload words and the tables of the blocks instead of 8 bytes a hash; the same bits, the same file.
 #include "build_common.hpp"
 #include "build_slabs.hpp"
 
@@ -21,8 +23,8 @@ namespace gnbuild
 namespace
 {
 
-// Device memory a fill takes besides the filter's rows: the two staging chunks of gn_filter_emplace_runs_window (1 Mi hashes each) and
-// their item tables, rounded up.
+// Device memory a fill takes besides the filter's rows: the two staging chunks of gn_filter_emplace_runs_window (1 Mi hashes each; 1 Mi
+// payload words each for gn_filter_emplace_packed_window) and their item tables, rounded up.
 constexpr uint64_t kFillStagingBytes = 24ull << 20;
 // What a budget taken from the free memory leaves alone on every device: the runtime's own allocations on first use of a stream or a
 // kernel, and room for whatever else runs on a shared card to grow a little while the build runs.
@@ -35,21 +37,38 @@ struct Runs
     std::vector<uint64_t>        size, per_bin;
     std::vector<uint32_t>        first_bin;
     uint64_t                     hashes = 0;
-    explicit Runs(const FlatFill& w)
+    // packed sets: per run its blocks and the words of its arena instead of `ptr`; what one pass uploads
+    bool                                packed = false;
+    std::vector<const gn_packed_block*> blocks;
+    std::vector<uint64_t>               n_blocks;
+    uint64_t                            pass_bytes = 0;
+    explicit Runs(const FlatFill& w) : packed(w.arenas != nullptr)
     {
         uint32_t bin = 0;
         for (size_t t = 0; t < w.targets.size(); ++t)
         {
-            const uint64_t n = w.targets[t].hashes.size();
+            const Target&  tg = w.targets[t];
+            const uint64_t n  = n_hashes(tg);
             if (n == 0)
                 continue;
-            ptr.push_back(w.targets[t].hashes.data()), size.push_back(n), per_bin.push_back(w.shares[t]), first_bin.push_back(bin);
+            if (packed)
+            {
+                ptr.push_back((*w.arenas)[tg.arena]), blocks.push_back(reinterpret_cast<const gn_packed_block*>(tg.blocks.data())), n_blocks.push_back(tg.blocks.size());
+                for (const GnPackedBlock& b : tg.blocks)
+                    pass_bytes += 8ull * gn_packed_words(b.cnt, b.width) + sizeof(GnPackedItem);
+            }
+            else
+                ptr.push_back(tg.hashes.data()), pass_bytes += n * 8;
+            size.push_back(n), per_bin.push_back(w.shares[t]), first_bin.push_back(bin);
             bin += (uint32_t)((n + w.shares[t] - 1) / w.shares[t]);
             hashes += n;
         }
     }
     bool insert(gn_filter* f, uint64_t total_rows, uint64_t row_begin) const
     {
+        if (packed)
+            return gn_filter_emplace_packed_window(f, blocks.data(), n_blocks.data(), ptr.data(), first_bin.data(), per_bin.data(), (uint32_t)ptr.size(), total_rows,
+                                                   row_begin, 0) == GN_OK;
         return gn_filter_emplace_runs_window(f, ptr.data(), size.data(), first_bin.data(), per_bin.data(), (uint32_t)ptr.size(), total_rows, row_begin, 0) == GN_OK;
     }
 };
@@ -169,7 +188,7 @@ bool fill_and_save_flat(const FlatFill& w, Lap& filling, Lap& writing)
                 std::cerr << "slab " << i << ": filled in " << fill_s[i] << " s, written in " << write_s[i] << " s\n";
     }
     if (c.verbose)
-        std::cerr << "filled in " << plan.n_slabs << (plan.n_slabs == 1 ? " pass" : " passes") << " over the hash sets, " << runs.hashes * 8 * plan.n_slabs
+        std::cerr << "filled in " << plan.n_slabs << (plan.n_slabs == 1 ? " pass" : " passes") << " over the hash sets, " << runs.pass_bytes * plan.n_slabs
                   << " hash bytes uploaded" << std::endl;
     return true;
 }

@@ -128,7 +128,7 @@ static void filter_header(Writer& w, const IbfParams& p, const std::vector<Targe
     for (const Target& t : targets)
     {
         w.str(t.name);
-        w.raw<uint64_t>(t.hashes.size());
+        w.raw<uint64_t>(n_hashes(t));
     }
     w.raw<uint64_t>(bins.size()); // bin_map
     for (uint64_t b = 0; b < bins.size(); ++b)

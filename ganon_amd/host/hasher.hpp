@@ -5,6 +5,8 @@
 
 #include "ganon_hip.h"
 
+#include "../csrc/gn_packed_set.h"
+
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -20,6 +22,34 @@ inline std::string hip_error()
 {
     return gn_last_error();
 }
+
+// One file's set in packed form (csrc/gn_packed_set.h; `ganon-build --hash-sets packed|spilled`): what the hasher leaves when the file
+// is done.  A file hashed in one flush -- the common case -- is packed by the device and only the packed bytes are downloaded; a second
+// flush unpacks the first into `raw`, the later ones append to it as without packing, and finish() unites them on the host and packs
+// the result with the header's encoder.  word_at of the blocks counts from payload[0].
+struct PackedFile
+{
+    std::vector<GnPackedBlock> blocks;
+    std::vector<uint64_t>      payload, raw;
+    uint64_t                   hashes  = 0;
+    unsigned                   flushes = 0;
+    void clear()
+    {
+        blocks.clear(), payload.clear(), raw.clear();
+        hashes = 0, flushes = 0;
+    }
+    void finish()
+    {
+        if (flushes <= 1)
+            return;
+        std::sort(raw.begin(), raw.end());
+        raw.erase(std::unique(raw.begin(), raw.end()), raw.end());
+        blocks.clear(), payload.clear();
+        gn_packed_encode(raw.data(), raw.size(), blocks, payload);
+        hashes = raw.size();
+        raw.clear();
+    }
+};
 
 // One parser thread's device side: a stream on a placeholder filter (hashing does not look at the filter)
 class Hasher
@@ -56,7 +86,23 @@ public:
     }
 
     // add one sequence; `out` receives the distinct hashes of everything flushed so far for the current file
-    void add(const uint8_t* seq, uint64_t len, std::vector<uint64_t>& out, unsigned& flushes)
+    void add(const uint8_t* seq, uint64_t len, std::vector<uint64_t>& out, unsigned& flushes) { add(seq, len, Sink{ &out, &flushes, nullptr }); }
+    void flush(std::vector<uint64_t>& out, unsigned& flushes) { flush(Sink{ &out, &flushes, nullptr }); }
+    void flush_short(std::vector<uint64_t>& out, unsigned& flushes) { flush_short(Sink{ &out, &flushes, nullptr }); }
+    // the same with a packed output (call out.finish() behind the file's last flush)
+    void add(const uint8_t* seq, uint64_t len, PackedFile& out) { add(seq, len, Sink{ &out.raw, &out.flushes, &out }); }
+    void flush(PackedFile& out) { flush(Sink{ &out.raw, &out.flushes, &out }); }
+    void flush_short(PackedFile& out) { flush_short(Sink{ &out.raw, &out.flushes, &out }); }
+
+private:
+    struct Sink // where a device batch's set goes: appended to *raw, or -- a packed file's first batch -- into *packed
+    {
+        std::vector<uint64_t>* raw;
+        unsigned*              flushes;
+        PackedFile*            packed;
+    };
+
+    void add(const uint8_t* seq, uint64_t len, const Sink& to)
     {
         if (len < k_)
             return;
@@ -69,26 +115,23 @@ public:
         {
             const uint64_t n = std::min<uint64_t>(len - at, (uint64_t)stride_ + w_ - 1);
             if (fill_ + n > kMaxBases || off_.size() > kMaxPieces)
-                flush(out, flushes);
+                flush(to);
             std::memcpy(bases_ + fill_, seq + at, n);
             fill_ += n;
             off_.push_back(fill_);
         }
     }
 
-    void flush(std::vector<uint64_t>& out, unsigned& flushes)
+    void flush(const Sink& to)
     {
         if (off_.size() > 1)
-        {
-            run(w_, out);
-            ++flushes;
-        }
+            run(w_, to);
         fill_ = 0;
         off_.assign(1, 0);
     }
 
     // sequences shorter than the window: one launch per length, the window being the whole sequence
-    void flush_short(std::vector<uint64_t>& out, unsigned& flushes)
+    void flush_short(const Sink& to)
     {
         for (auto& [len, cat] : short_)
         {
@@ -100,8 +143,7 @@ public:
                 for (size_t i = 1; i <= n_seq; ++i)
                     off_.push_back(i * len);
                 fill_ = n_seq * len;
-                run(len, out);
-                ++flushes;
+                run(len, to);
                 at += n_seq * len;
             }
         }
@@ -110,18 +152,33 @@ public:
         off_.assign(1, 0);
     }
 
-private:
     // one device batch: enough for a bacterial genome in one go; every parser thread has its own (page-locked) copy, so the
     // size is also what start-up pays per thread
     static constexpr uint64_t kMaxBases  = 64ull << 20;
     static constexpr uint32_t kMaxPieces = 1u << 18;
 
-    void run(uint32_t w, std::vector<uint64_t>& out)
+    void run(uint32_t w, const Sink& to)
     {
         const uint32_t n = (uint32_t)off_.size() - 1;
         if (gn_stream_upload_reads(st_, bases_, fill_, off_.data(), nullptr, n) != GN_OK || gn_stream_minimisers(st_, k_, w) != GN_OK)
             throw std::runtime_error(hip_error());
-        uint64_t nd = 0;
+        const unsigned before = (*to.flushes)++;
+        if (to.packed && before == 0) // the file's first batch: packed where it lies, only the packed bytes come back
+        {
+            PackedFile& pk = *to.packed;
+            uint64_t    nb = 0, nw = 0;
+            if (gn_stream_distinct_hashes_packed(st_, nullptr, 0, nullptr, 0, &pk.hashes, &nb, &nw) != GN_OK)
+                throw std::runtime_error(hip_error());
+            pk.blocks.resize(nb), pk.payload.resize(nw);
+            if (nb && gn_stream_distinct_hashes_packed(st_, reinterpret_cast<gn_packed_block*>(pk.blocks.data()), nb, pk.payload.data(), nw, &pk.hashes, &nb,
+                                                       &nw) != GN_OK)
+                throw std::runtime_error(hip_error());
+            return;
+        }
+        if (to.packed && before == 1) // a second batch after all: the first one's set joins the raw hashes, to be united at the end
+            gn_packed_decode(to.packed->blocks.data(), to.packed->blocks.size(), to.packed->payload.data(), *to.raw);
+        std::vector<uint64_t>& out = *to.raw;
+        uint64_t               nd  = 0;
         if (gn_stream_distinct_hashes(st_, nullptr, 0, &nd) != GN_OK)
             throw std::runtime_error(hip_error());
         const size_t at = out.size();

@@ -419,6 +419,28 @@ int gn_filter_emplace_split(gn_filter* f, const uint64_t* hashes, uint64_t n, ui
  * of the one before, one launch per chunk; every bin a run can reach is checked before anything is launched. */
 int gn_filter_emplace_runs_window(gn_filter* f, const uint64_t* const* runs, const uint64_t* run_sizes, const uint32_t* first_bin,
                                   const uint64_t* hashes_per_bin, uint32_t n_runs, uint64_t total_rows, uint64_t row_begin, uint64_t chunk_hashes);
+/* Hash sets packed as deltas of fixed width (ganon_amd/csrc/gn_packed_set.h has the format, a host encoder and decoder).  A block holds
+ * cnt hashes (1 .. 512), strictly ascending: `first` is the first, `width` the bit length of the largest difference of neighbours (0 for
+ * one hash), and delta i-1 = v[i] - v[i-1] occupies bits [(i-1) * width, i * width) of the payload words from `word_at` on, LSB first,
+ * across word boundaries; a block has ceil((cnt-1) * width / 64) words and its padding bits are zero.  A set is cut every 512 hashes.
+ * gn_stream_distinct_hashes_packed: the set of gn_stream_distinct_hashes, packed on the device; only the packed bytes are copied.
+ * With blocks and payload NULL the call answers *n_distinct, *n_blocks and *n_words alone; word_at counts from payload[0].  The result is
+ * word for word what gn_packed_encode makes of the output of gn_stream_distinct_hashes.
+ * gn_filter_emplace_packed_window: gn_filter_emplace_runs_window for packed runs.  Run r is blocks[r][0 .. n_blocks[r]) with word_at
+ * counting from payload[r][0]; its hashes are those of its blocks behind each other (a short block may lie in the middle: a run is a
+ * target's files' sets), hash i of them belongs to bin first_bin[r] + i / hashes_per_bin[r].  The same filter, window, checks and bits as
+ * gn_filter_emplace_runs_window; the two staging chunks hold chunk_words payload words (0: 1 Mi words; at least the 511 words a block can
+ * have) and the tables of their blocks. */
+typedef struct gn_packed_block
+{
+    uint64_t first, word_at;
+    uint32_t cnt, width;
+} gn_packed_block;
+int gn_stream_distinct_hashes_packed(gn_stream* s, gn_packed_block* blocks, uint64_t cap_blocks, uint64_t* payload, uint64_t cap_words,
+                                     uint64_t* n_distinct, uint64_t* n_blocks, uint64_t* n_words);
+int gn_filter_emplace_packed_window(gn_filter* f, const gn_packed_block* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                    const uint32_t* first_bin, const uint64_t* hashes_per_bin, uint32_t n_runs, uint64_t total_rows, uint64_t row_begin,
+                                    uint64_t chunk_words);
 /* The membership check of the reference's build test (validate_elements, /root/reference/tests/ganon-build/GanonBuild.test.cpp:53-98:
  * hash a sequence, bulk_count, add up the counts of its target's bins, compare with the number of hashes) for a flat IBF on the
  * device: *hits = sum over the n hashes (host memory) of the number of `bins` that contain the hash, *missing = hashes no bin

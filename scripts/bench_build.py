@@ -34,6 +34,8 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
   --device LIST   passed on as `--device LIST` to every build; a list a,b,... only to the flat build (the hierarchical modes take one)
   --device-memory BYTES  passed on to the flat build: the filter is filled in row slabs when it is larger; the run reports "slabs",
                   "passes", "hash_bytes_uploaded" and per slab its fill and write seconds
+  --hash-sets MODE  passed on to the flat build (raw | packed | spilled): the run reports "hash_sets", "hashes", "hash_set_bytes" (what the
+                  sets hold, beside 8 x hashes) and "rss_anon_kb", the process's anonymous memory when hashing ends
   --hibf-memory BYTES / --hibf-devices LIST  [--hibf] passed on to the hierarchical build: the tree is filled in parts when it is larger
                   than BYTES of device rows, the parts dealt to the entries of LIST; the run reports "parts", "hash_bytes_uploaded"
                   beside "one_pass_hash_bytes", and per part its device bytes, the sets it took and its fill and write seconds"""
@@ -48,7 +50,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hibf-memory": "", "--hibf-devices": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hash-sets": "", "--hibf-memory": "", "--hibf-devices": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -107,7 +109,8 @@ if n_families:
 if opts["--lognormal"]:
     out["lognormal_sigma"], out["largest_file"], out["smallest_file"] = float(opts["--lognormal"]), max(lengths), min(lengths)
 exe = os.path.join(ROOT, "ganon_amd", "host", "ganon-build")
-device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["--device-memory", opts["--device-memory"]] if opts["--device-memory"] else [])
+device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["--device-memory", opts["--device-memory"]] if opts["--device-memory"] else []) + \
+              (["--hash-sets", opts["--hash-sets"]] if opts["--hash-sets"] else [])
 device_hibf = ["--device", opts["--device"]] if opts["--device"] else []
 parts_hibf = (["--hibf-memory", opts["--hibf-memory"]] if opts["--hibf-memory"] else []) + (["--hibf-devices", opts["--hibf-devices"]] if opts["--hibf-devices"] else [])
 
@@ -123,6 +126,12 @@ def flat_run(max_fp="0.05", extra=()):
         res["passes"], res["hash_bytes_uploaded"] = int(m.group(1)), int(m.group(2))
         res["slabs"] = [ln for ln in p.stderr.splitlines() if re.match(r"slab \d+: rows ", ln)][:64]
         res["slab_fill_write_s"] = [(float(a), float(b)) for a, b in re.findall(r"^slab \d+: filled in ([0-9.eE+-]+) s, written in ([0-9.eE+-]+) s$", p.stderr, re.M)][:64]
+    m = re.search(r"^hash sets: (\d+) hashes held (\w+) in (\d+) bytes", p.stderr, re.M)
+    if m:
+        res["hashes"], res["hash_sets"], res["hash_set_bytes"] = int(m.group(1)), m.group(2), int(m.group(3))
+    m = re.search(r"^RssAnon after hashing: (\d+) kB", p.stderr, re.M)
+    if m:
+        res["rss_anon_kb"] = int(m.group(1))
     for key, pat in (("count_hashes_s", r"Count/save hashes start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
                      ("sizing_s", r"Estimate params   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
                      ("fill_s", r"Building filter   start:.*\n.*\n\s*elapsed \(s\): ([0-9.eE+-]+)"),
