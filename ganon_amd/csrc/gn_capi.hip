@@ -5,6 +5,7 @@
 #include <hipcub/hipcub.hpp>
 #include "gn_scan.h"
 #include "gn_screen_table.h"
+#include "gn_stray_probe.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -47,7 +48,7 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
     {
         const char* name;
         bool GnSwitches::* flag;
-    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"lean_screen", &GnSwitches::lean_screen},     {"cand_select", &GnSwitches::cand_select},
+    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"lean_screen", &GnSwitches::lean_screen},     {"stray_masks", &GnSwitches::stray_masks},     {"cand_select", &GnSwitches::cand_select},
                               {"csr_identity", &GnSwitches::csr_identity},   {"uniform_select", &GnSwitches::uniform_select},
                               {"run_select", &GnSwitches::run_select},       {"max_first", &GnSwitches::max_first},
                               {"const_nb", &GnSwitches::const_nb},           {"split_kernel", &GnSwitches::split_kernel},
@@ -1321,6 +1322,7 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     p.emit_probe = gn_sw().emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
     p.early_exit = gn_sw().early_exit ? 0u : 1u; // (bench.py's every-row measurement and the parity tests of the exit)
     p.skip_ctr   = s->d_ctr + 7;
+    p.probe_hashes = gn_sw().stray_masks ? 0u : GN_PROBE_HASHES; // (0: the finish's one-stage probe, for the A/B and the parity tests)
     if (f->identity && p.early_exit && !gn_sw().row_screen && (f->geom.lw == 1 || p.W > 128)) // (the instances that screen: gn_launch_fast_one)
     {
         // per launch: how many hashes a read of n minimisers is screened on with two of its rows (gn_screen_table.h; all zero = the flow

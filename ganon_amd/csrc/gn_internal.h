@@ -34,6 +34,7 @@ struct GnSwitches
     bool early_exit = false;      // fast kernel: fetch every row (no exact early exit)
     bool row_screen = false;      // fast kernel: no two-row screen in front of the exit (every read takes the unscreened flow)
     bool lean_screen = false;     // fast kernel: no screen-only kernel + launch over its list (the screening instance takes every unit, one launch)
+    bool stray_masks = false;     // fast kernel: the finish probes a bin on rows 2 and 3 of every screened hash at once (2 ds words; no stage on the hashes known to have hit)
     bool cand_select = false;     // generic kernel: scan every target instead of the candidate-driven select
     bool csr_identity = false;    // split-bin kernel family: treat an ordered CSR map as a general one
     bool uniform_select = false;  // ... no packed select for equal bins-per-target
@@ -161,6 +162,7 @@ struct GnCountParams
     uint32_t                  early_exit;      // fast kernel: stop fetching rows of reads that cannot reach the cutoff
     unsigned long long*       skip_ctr;        // row bytes not fetched thanks to early exits
     uint32_t                  screen[32];      // fast kernel: byte n = hashes a read of n minimisers is screened on with rows 0 and 1 only (0: no screen), gn_screen_table
+    uint32_t                  probe_hashes;    // fast kernel: screened hashes whose hit masks stage the finish's probe (GN_PROBE_HASHES, gn_stray_probe.h; 0: one stage, switch stray_masks)
     unsigned long long*       grab;            // fast kernel: the cursor its waves take their later units from (zero at launch; nullptr: units i, i + waves, ...)
     // fast kernel, with a filter_matches pre-pass set on the stream: matches that the --rel-filter rule is bound to drop are
     // not written at all (see the epilogue).  0 off, 1: the read's minimum is at least its cutoff count T (this filter sees all

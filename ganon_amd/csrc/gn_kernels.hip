@@ -24,6 +24,9 @@
 #ifndef GN_NARROW_MAX
 #define GN_NARROW_MAX 4u
 #endif
+// the screen keeps the hit masks (rows 0 AND 1) of its first GN_PROBE_HASHES hashes for the finish's staged probe: gn_stray_probe.h
+#include "gn_stray_probe.h"
+static_assert(GN_PROBE_HASHES % 2u == 0 && GN_PROBE_HASHES * 4u <= GN_WAVE, "whole screen iterations (two hashes each), and stage 1 is one load a lane");
 #define GN_MATCH_CHUNK 256u      // first wave-private chunk of the match buffer ...
 #ifndef GN_MATCH_CHUNK_MAX
 #define GN_MATCH_CHUNK_MAX 8192u
@@ -1092,6 +1095,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     const uint32_t hsub  = lane >> gpl;
     uint32_t*      rowtab = gn_lds + (size_t)wave * 128 * HFP;
     uint32_t*      mlist  = gn_lds + (size_t)(blockDim.x >> 6) * 128 * HFP + (size_t)wave * GN_FAST_LIST; // the epilogue's match list (low cutoffs)
+    // the screening instances: hit masks of the first GN_PROBE_HASHES screened hashes, dword (q * ND + d) * 64 + lane (behind the lists;
+    // in LDS in both: <4,1,true,false,true> has no register for them, and the finish reads the owner lane's by address)
+    uint32_t*      pmask  = gn_lds + (size_t)(blockDim.x >> 6) * (128 * HFP + GN_FAST_LIST) + (size_t)wave * (GN_PROBE_HASHES * ND * GN_WAVE);
 
     // Persistent waves: unit = (read, column slice), handed out in chunks (below).  The metadata of the NEXT unit
     // (status, n, hash slot) is loaded at the top of the current one (the screening instances: under its first rows) and its
@@ -1366,6 +1372,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
             for (int d = 0; d < ND; ++d)
             {
                 const uint32_t a = R.m[0][d] & R.m[1][d] & on, b = R.m[2 % HF][d] & R.m[3 % HF][d] & on2;
+                if (2 * it < GN_PROBE_HASHES) // kept for the finish's probe (a hash an odd ds masks off keeps 0)
+                {
+                    pmask[((2 * it) * ND + (uint32_t)d) * GN_WAVE + (uint32_t)lane]     = a;
+                    pmask[((2 * it + 1) * ND + (uint32_t)d) * GN_WAVE + (uint32_t)lane] = b;
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     nib[d][j] += ((a >> j) & 0x11111111u) + ((b >> j) & 0x11111111u);
@@ -1566,8 +1577,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
     // AND-ed with shifts of the ballot -- and the hits are added to the owner lane's byte counter before the normal epilogue runs.
     // The screened flow's finish is the same pass from hash 0: the exact count replaces the bin's byte (it held c2).  A bin that
     // every screened hash hit (c2 = ds, an error-free read of its genome) needs no second look at rows 0 and 1 of those hashes.
-    // Any other bin is first probed on the rows 2 .. of the screened hashes alone (2 ds words): a stray bin, ahead on rows 0 and
-    // 1 by chance, falls below the bound there and gets 0; what is left is read in full.
+    // Any other bin is first probed on the rows 2 .. of the screened hashes alone: a stray bin, ahead on rows 0 and 1 by chance,
+    // falls below the bound there and gets 0; what is left is read in full.  The probe is staged (gn_stray_probe.h): first the
+    // hashes among the first GN_PROBE_HASHES that are known to have hit (2 m words; the screen kept their hit masks in LDS), which
+    // settles nearly every stray, then the other screened hashes (2 (ds - F') words).  Switch stray_masks: one stage of 2 ds words.
     uint32_t narrow_loads = 0;
     if (EE && (narrow || (SCR && finish)))
     {
@@ -1582,6 +1595,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
 #pragma unroll
         for (int d = 0; d < ND; ++d)
             any_sm |= sm[d];
+        if constexpr (SCR)
+            gn_wave_lds_sync(); // the screen's hit masks are in LDS
         uint64_t lm = __ballot(any_sm != 0);
         while (lm)
         {
@@ -1599,30 +1614,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                     const uint32_t word = slice * 64 * LW + (uint32_t)L * LW + (tp >> 6);
                     const uint32_t sh   = tp & 63u;
                     uint32_t       add  = 0;
+                    uint32_t       q_lo    = q_from;
                     uint32_t       q_known = 0;     // hashes below this one are taken to have the bit in rows 0 and 1
                     uint32_t       q_to    = n;
                     bool           probe   = false; // a first pass over the other rows of the screened hashes only
-                    if (SCR && finish)
-                    {
-                        uint32_t c2 = 0;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-#pragma unroll
-                            for (int pp = 0; pp < 2; ++pp)
-                                if ((bit & 3u) == (uint32_t)j && ((bit >> 2) & 1u) == (uint32_t)pp)
-                                    c2 = byt[d][j][pp];
-                        c2      = ((uint32_t)__builtin_amdgcn_readlane((int)c2, L) >> (8u * (bit >> 3))) & 0xFFu;
-                        q_known = ds;
-                        if (c2 != ds) // which hashes missed is not known: the rows 2 .. of the screened hashes say whether the bin is worth it
+                    bool           dropped = false; // the probe's first stage settled it: no pass at all
+                    uint32_t       e1      = 0;     // what that stage counted
+                    if constexpr (SCR)
+                        if (finish)
                         {
-                            probe = true;
-                            q_to  = ds;
+                            uint32_t c2 = 0;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                                for (int pp = 0; pp < 2; ++pp)
+                                    if ((bit & 3u) == (uint32_t)j && ((bit >> 2) & 1u) == (uint32_t)pp)
+                                        c2 = byt[d][j][pp];
+                            c2      = ((uint32_t)__builtin_amdgcn_readlane((int)c2, L) >> (8u * (bit >> 3))) & 0xFFu;
+                            q_known = ds;
+                            if (c2 != ds)
+                            {
+                                // which hashes missed is known for the first Fp (gn_stray_probe.h).  Stage 1: rows 2 and 3 of those that hit, a
+                                // lane a word; a stray bin, ahead on rows 0 and 1 by chance, nearly always falls below the bound here
+                                const uint32_t Fp   = gn_probe_first(p.probe_hashes, ds);
+                                bool           hitq = false;
+                                if (l_q < Fp)
+                                    hitq = ((pmask[(l_q * ND + (uint32_t)d) * GN_WAVE + (uint32_t)L] >> bit) & 1u) != 0;
+                                const bool ld = hitq && l_i >= 2;
+                                uint64_t   w1 = 0;
+                                if (ld)
+                                    w1 = p.rows[(uint64_t)rowtab[l_q * HFP + l_i] * p.W + word];
+                                const uint64_t hb = __ballot(ld && ((w1 >> sh) & 1ULL));
+                                const uint32_t m  = (uint32_t)__popcll(__ballot(hitq && l_i == 2));
+                                e1                = (uint32_t)__popcll(hb & (hb >> 1) & (grp << 2));
+                                narrow_loads += 2 * m;
+                                dropped = gn_probe_drop1(n, T, ds, c2, m, e1);
+                                // stage 2: the rows 2 .. of the other screened hashes say whether the bin is worth it
+                                probe = true;
+                                q_lo  = Fp;
+                                q_to  = ds;
+                            }
                         }
-                    }
-                    for (;;)
+                    while (!dropped)
                     {
                         add = 0;
-                        for (uint32_t q0 = q_from; q0 < q_to; q0 += 2 * QPC)
+                        for (uint32_t q0 = q_lo; q0 < q_to; q0 += 2 * QPC)
                         {
                             // a lane takes two hash slots, l_q and l_q + QPC, and both of its word loads are requested before either
                             // ballot waits for one: a pass covers 2 QPC hashes in one round trip (every 150 bp read in one)
@@ -1643,18 +1679,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
                             }
                             add += (uint32_t)__popcll(alla & grp) + (uint32_t)__popcll(allb & grp);
                         }
-                        narrow_loads += (q_to - q_from) * HF - 2 * q_known;
+                        narrow_loads += (q_to - q_lo) * HF - 2 * (q_known - (SCR && probe ? q_lo : 0u));
                         if (!(SCR && probe))
                             break;
                         // add = screened hashes with the bit in rows 2 .. >= the bin's count over them: below the survey's bound the bin
                         // cannot reach T, whatever rows 0 and 1 say hash by hash, and vanishes; else every word of every hash is read
                         probe = false;
-                        if (add + (n - ds) < T)
+                        add += e1;
+                        if (gn_probe_drop2(n, T, ds, add))
                         {
                             add = 0;
                             break;
                         }
                         q_known = 0;
+                        q_lo    = 0;
                         q_to    = n;
                     }
                     // into byte (bit >> 3) of byt[d][bit & 3][(bit >> 2) & 1] of lane L
@@ -2023,6 +2061,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
     const int      wave   = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t wpr    = p.wpr;
     uint32_t*      rowtab = gn_lds + (size_t)wave * 128 * HF;
+    // hit masks of the first GN_PROBE_HASHES screened hashes, dword (q * ND + d) * 64 + lane: in LDS (2 KiB a wave), there is no register for them
+    uint32_t*      pmask  = gn_lds + (size_t)(blockDim.x >> 6) * 128 * HF + (size_t)wave * (GN_PROBE_HASHES * ND * GN_WAVE);
 
     // units are handed out as in gn_ibf_count_fast_kernel
     const uint64_t n_units = (uint64_t)(p.n_reads - p.read_begin) * wpr;
@@ -2214,6 +2254,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
         for (int d = 0; d < ND; ++d)
         {
             const uint32_t a = R.m[0][d] & R.m[1][d] & on, b = R.m[2][d] & R.m[3][d] & on2;
+            if (2 * it < GN_PROBE_HASHES) // kept for the finish's probe (a hash an odd ds masks off keeps 0)
+            {
+                uint32_t l = (uint32_t)lane; // (through an empty asm: the lane's address is made here, not kept across the loop)
+                asm volatile("" : "+v"(l));
+                pmask[((2 * it) * ND + (uint32_t)d) * GN_WAVE + l]     = a;
+                pmask[((2 * it + 1) * ND + (uint32_t)d) * GN_WAVE + l] = b;
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 nib[d][j] += ((a >> j) & 0x11111111u) + ((b >> j) & 0x11111111u);
@@ -2307,6 +2354,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
         for (uint32_t q = 0; q < QPC; ++q)
             grp |= 1ULL << (q * HF);
         const uint32_t l_q = (uint32_t)lane / HF, l_i = (uint32_t)lane - l_q * HF;
+        // (the passes' bounds are set from these copies: n and ds themselves are captured by the lambdas above, and "q_to = n" in one
+        // branch, "q_to = ds" in another comes out as one load through a selected address, which keeps both in scratch)
+        const uint32_t n_f = n, ds_f = ds;
+        gn_wave_lds_sync(); // the screen's hit masks are in LDS
         uint64_t       lm  = __ballot((sm[0] | sm[1]) != 0);
         while (lm)
         {
@@ -2331,15 +2382,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
                                 c2 = byt[d][j][pp];
                     c2 = ((uint32_t)__builtin_amdgcn_readlane((int)c2, L) >> (8u * (bit >> 3))) & 0xFFu;
                     uint32_t add     = 0;
-                    uint32_t q_known = ds;      // hashes below this one are taken to have the bit in rows 0 and 1
-                    uint32_t q_to    = n;
-                    bool     probe   = c2 != ds; // which hashes missed is not known: first the rows 2 and 3 of the screened hashes alone
+                    uint32_t q_lo    = 0;
+                    uint32_t q_known = ds_f;     // hashes below this one are taken to have the bit in rows 0 and 1
+                    uint32_t q_to    = n_f;
+                    bool     probe   = c2 != ds; // which hashes missed: known for the first Fp, else first the rows 2 and 3 of the screened hashes alone
+                    bool     dropped = false;    // the probe's first stage settled it: no pass at all
+                    uint32_t e1      = 0;        // what that stage counted
                     if (probe)
-                        q_to = ds;
-                    for (;;)
+                    {
+                        // stage 1 (gn_stray_probe.h): rows 2 and 3 of the hashes among the first Fp that hit, a lane a word
+                        const uint32_t Fp   = gn_probe_first(p.probe_hashes, ds);
+                        bool           hitq = false;
+                        if (l_q < Fp)
+                            hitq = ((pmask[(l_q * ND + (uint32_t)d) * GN_WAVE + (uint32_t)L] >> bit) & 1u) != 0;
+                        const bool ld = hitq && l_i >= 2;
+                        uint64_t   w1 = 0;
+                        if (ld)
+                            w1 = p.rows[(uint64_t)rowtab[l_q * HF + l_i] * p.W + word];
+                        const uint64_t hb = __ballot(ld && ((w1 >> sh) & 1ULL));
+                        const uint32_t m  = (uint32_t)__popcll(__ballot(hitq && l_i == 2));
+                        e1                = (uint32_t)__popcll(hb & (hb >> 1) & (grp << 2));
+                        narrow_loads += 2 * m;
+                        dropped = gn_probe_drop1(n, T, ds, c2, m, e1);
+                        q_lo    = Fp; // stage 2: the other screened hashes
+                        q_to    = ds_f;
+                    }
+                    while (!dropped)
                     {
                         add = 0;
-                        for (uint32_t q0 = 0; q0 < q_to; q0 += 2 * QPC)
+                        for (uint32_t q0 = q_lo; q0 < q_to; q0 += 2 * QPC)
                         {
                             const uint32_t qa = q0 + l_q, qb = qa + QPC;
                             const bool     ina = qa < q_to, inb = qb < q_to;
@@ -2358,17 +2429,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
                             }
                             add += (uint32_t)__popcll(alla & grp) + (uint32_t)__popcll(allb & grp);
                         }
-                        narrow_loads += q_to * HF - 2 * q_known;
+                        narrow_loads += (q_to - q_lo) * HF - 2 * (q_known - (probe ? q_lo : 0u));
                         if (!probe)
                             break;
                         probe = false;
-                        if (add + (n - ds) < T) // below the survey's bound on rows 2 and 3 alone: the bin cannot reach T
+                        add += e1;
+                        if (gn_probe_drop2(n, T, ds, add)) // below the survey's bound on rows 2 and 3 alone: the bin cannot reach T
                         {
                             add = 0;
                             break;
                         }
                         q_known = 0;
-                        q_to    = n;
+                        q_lo    = 0;
+                        q_to    = n_f;
                     }
                     if (add >= T)
                     {
@@ -2449,6 +2522,7 @@ static hipError_t gn_launch_fast_one(const GnCountParams& p, hipStream_t st)
     if (blocks > p.max_blocks_fast)
         blocks = p.max_blocks_fast;
     const size_t   lds    = 4 * (128 * (HF <= 4 ? 4 : 8) + GN_FAST_LIST) * 4; // per wave: the row table + the epilogue's match list
+    const size_t   lds_pm = 4 * (GN_PROBE_HASHES * 2 * LW * GN_WAVE) * 4;     // ... the screening instances: + the probe's hit masks
     // the screening instance only for a launch whose table gives some read a screen (gn_capi.hip fills it for the shapes that have one)
     bool scr = false;
     if constexpr (HF == 4)
@@ -2458,18 +2532,18 @@ static hipError_t gn_launch_fast_one(const GnCountParams& p, hipStream_t st)
     if constexpr (HF == 4 && LW == 2)
         if (scr && p.W > 128)
         {
-            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, true, true>), dim3(blocks), dim3(256), lds, st, p);
+            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, true, true>), dim3(blocks), dim3(256), lds + lds_pm, st, p);
             return hipGetLastError();
         }
     if constexpr (HF == 4 && LW == 1)
         if (scr && p.unit_list_out != nullptr)
         {
-            // the screen-only kernel (its LDS: the row table), then the instance without a screen over the units it left: the list
+            // the screen-only kernel (its LDS: the row table and the probe's hit masks, 16 KiB a block), then the instance without a screen over the units it left: the list
             // is usually short (reads whose n has no table entry, aborted screens), so that grid follows the last batch's list
             uint32_t lean_blocks = (uint32_t)((units + 3) / 4);
             if (lean_blocks > p.max_blocks_lean)
                 lean_blocks = p.max_blocks_lean;
-            hipLaunchKernelGGL(gn_ibf_count_fast_kernel_lean, dim3(lean_blocks), dim3(256), 4 * 128 * HF * 4, st, p);
+            hipLaunchKernelGGL(gn_ibf_count_fast_kernel_lean, dim3(lean_blocks), dim3(256), 4 * (128 * HF + GN_PROBE_HASHES * 2 * GN_WAVE) * 4, st, p);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess)
                 return e;
@@ -2485,7 +2559,7 @@ static hipError_t gn_launch_fast_one(const GnCountParams& p, hipStream_t st)
     if constexpr (HF == 4 && LW == 1)
         if (scr)
         {
-            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, false, true>), dim3(blocks), dim3(256), lds, st, p);
+            hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, true, false, true>), dim3(blocks), dim3(256), lds + lds_pm, st, p);
             return hipGetLastError();
         }
     if (ee && LW == 2 && p.W > 128)

@@ -356,7 +356,7 @@ int gn_peer_stats(int dst, int src, int* state, uint64_t* bytes);
 /* Switches (test and measurement hook; no counterpart in the reference).  The library reads its environment in ONE place:
  * $GANON_HIP_ABLATE, a comma list parsed once when the library is loaded.  gn_ablate() replaces that list in-process so a
  * test can cross-check a fast path against the path it replaces (NULL or "" = the product path).  Call it only while no
- * launch is in flight.  Names that switch a path OFF: early_exit row_screen lean_screen cand_select csr_identity uniform_select run_select
+ * launch is in flight.  Names that switch a path OFF: early_exit row_screen lean_screen stray_masks cand_select csr_identity uniform_select run_select
  * max_first const_nb split_kernel predrop deferred_grids hibf_reg hibf_pack hibf_one_pack; test set-ups:
  * pinned_malloc gather_copy joint_apart inflate_ahead on_demand hibf_dense_rows chunk=N hibf_pair_limit=N; runtime: sync=spin|yield|block debug; measurement with WRONG results: fake_count (flat IBF: the count +
  * select kernels are not run, every second read gets one made-up match -- what is left is what the host around the device sustains).  Unknown name -> GN_EINVAL and
