@@ -702,6 +702,497 @@ extern "C" int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes
     return GN_OK;
 }
 
+// ---- gn_filter_probe_path_window / gn_filter_probe_paths_shared_window: the probes on pieces of IBFs --------------------------------
+// IBF j of the filter stands for rows [row_begin[j], row_begin[j] + S_j) of an IBF of total_rows[j] rows, as for the windowed insert
+// (`ganon-build --hibf --verify-index --verify-memory / --verify-devices`: build_verify_parts.cpp).  A lookup cannot be cut as cheaply as
+// an insert: a hash is in a run only if ONE bin has its bit in all h rows, and those rows may lie in different pieces.  So the answer of
+// a piece that is a slab of its IBF is carried per bin: plane b of an entry says "every row of the hash seen so far has the bit of bin
+// first_bin + b", and the caller closes the entry when the last slab is through (host/hibf_verify_parts.hpp).  An entry whose piece is
+// the whole IBF needs no planes: its answer per hash is final.
+
+// One path entry as the two kernels read it: the geometry of the WHOLE IBF and the piece of it this filter holds (48 bytes).
+struct GnProbeWinDev
+{
+    uint64_t* rows;              // the piece: n_rows rows of Ws words
+    uint64_t  S_total;           // rows of the whole IBF
+    uint64_t  plane_at;          // gn_probe_shared_window_kernel: word of the entry's first plane in the planes buffer
+    uint32_t  Ws, shift;         // words from one row to the next; countl_zero(S_total)
+    uint32_t  first_bin, n_bins; // n_bins == 0: the path ends above this entry
+    uint32_t  row_begin, n_rows; // the piece is rows [row_begin, row_begin + n_rows) of the whole IBF
+    uint32_t  slab, reserved;    // slab != 0: answered per bin into planes
+};
+
+// One wave per item, as gn_probe_path_kernel: item and path entries in SGPRs, 8 hashes a lane in registers.  An item starts at a multiple
+// of 512 hashes of its set (the host cuts them so), so slot j of the wave is word begin / 64 + j of every bitmap of the set and a ballot
+// IS that word: the wave writes whole words that no other wave writes, to out + out_at[item] -- per used entry in order 8 words (bit l of
+// word j: the hash in slot j of lane l is contained) for a whole piece, 8 * n_bins words (plane b at b * 8) for a slab -- and the host ANDs
+// them into the caller's bitmaps.  Per entry and word of the run the row words of all 8 * H (hash, row) pairs are fetched before any is
+// used.  A row outside the piece contributes all ones: its lane loads *ones_word, a word of all ones that is surely there -- the address
+// is selected, not the value, so no flag has to outlive the loads and no load sits behind a lane-dependent branch.  A lane without a hash in a slot probes hash 0 there and the host masks its bit away.
+template <uint32_t H>
+__global__ __launch_bounds__(256) void gn_probe_path_window_kernel(const uint64_t* __restrict__ stage, const GnRunItem* __restrict__ items,
+                                                                   const uint64_t* __restrict__ out_at, uint32_t n_items,
+                                                                   const GnProbeWinDev* __restrict__ paths, uint32_t depth,
+                                                                   const unsigned long long* __restrict__ ones_word, unsigned long long* __restrict__ out)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t  lane = threadIdx.x & 63u;
+    const GnRunItem it   = items[item];
+    uint64_t        v[GN_WIN_PER_LANE];
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = j * 64u + lane;
+        v[j]             = q < it.cnt ? stage[it.stage_at + q] : 0;
+    }
+    const GnProbeWinDev* __restrict__ p = paths + (uint64_t)it.run * depth;
+    unsigned long long* __restrict__ o  = out + out_at[item];
+    for (uint32_t d = 0; d < depth; ++d)
+    {
+        const GnProbeWinDev e = p[d];
+        if (e.n_bins == 0)
+            break;
+        GnGlobalConstWord* rows = (GnGlobalConstWord*)e.rows;
+        const uint64_t     ones_at = ((uint64_t)ones_word - (uint64_t)e.rows) >> 3; // *ones_word as a word of `rows`, modulo 2^64
+        const uint32_t     w1   = (e.first_bin + e.n_bins - 1) >> 6;
+        uint32_t           hit  = 0;
+        for (uint32_t w = e.first_bin >> 6; w <= w1; ++w)
+        {
+            uint64_t r[GN_WIN_PER_LANE][H];
+#pragma unroll
+            for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+#pragma unroll
+                for (uint32_t i = 0; i < H; ++i)
+                {
+                    // gn_window_local in arithmetic, and the mask made opaque: 8 * H compares kept as lane masks until their selects
+                    // would take 16 * H SGPRs, more than there are
+                    const uint32_t local = gn_build_row(v[j], i, e.shift, e.S_total) - e.row_begin;
+                    uint32_t       m     = 0u - (uint32_t)(((uint64_t)local - (uint64_t)e.n_rows) >> 63); // all ones: local < n_rows
+                    asm("" : "+v"(m));
+                    const uint64_t at = (uint64_t)local * e.Ws + w;
+                    r[j][i]           = rows[ones_at + ((at - ones_at) & (uint64_t)(int64_t)(int32_t)m)];
+                }
+            uint64_t a[GN_WIN_PER_LANE];
+#pragma unroll
+            for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+            {
+                a[j] = r[j][0];
+#pragma unroll
+                for (uint32_t i = 1; i < H; ++i)
+                    a[j] &= r[j][i];
+            }
+            if (!e.slab)
+            {
+                const uint64_t mask = gn_run_mask(e.first_bin, e.n_bins, w);
+#pragma unroll
+                for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+                    hit |= ((a[j] & mask) != 0 ? 1u : 0u) << j;
+                continue;
+            }
+            // a slab: one plane per bin of the run that lies in this word; lane j < 8 keeps ballot j, the eight leave as one 64-byte store
+            const uint32_t b_lo = max(e.first_bin, w << 6), b_hi = min(e.first_bin + e.n_bins, (w + 1u) << 6);
+            for (uint32_t b = b_lo; b < b_hi; ++b)
+            {
+                unsigned long long mine = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+                {
+                    const unsigned long long bal = __ballot((a[j] >> (b & 63u)) & 1ull);
+                    mine                         = lane == j ? bal : mine;
+                }
+                if (lane < GN_WIN_PER_LANE)
+                    o[(uint64_t)(b - e.first_bin) * GN_WIN_PER_LANE + lane] = mine;
+            }
+        }
+        if (!e.slab)
+        {
+            unsigned long long mine = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+            {
+                const unsigned long long bal = __ballot((hit >> j) & 1u);
+                mine                         = lane == j ? bal : mine;
+            }
+            if (lane < GN_WIN_PER_LANE)
+                o[lane] = mine;
+        }
+        o += (uint64_t)(e.slab ? e.n_bins : 1u) * GN_WIN_PER_LANE;
+    }
+}
+
+template <uint32_t H>
+static void gn_probe_path_window_launch(hipStream_t st, const uint64_t* stage, const GnRunItem* items, const uint64_t* out_at, uint32_t n_items,
+                                        const GnProbeWinDev* paths, uint32_t depth, const unsigned long long* ones, unsigned long long* out)
+{
+    hipLaunchKernelGGL(gn_probe_path_window_kernel<H>, dim3((n_items + 3) / 4), dim3(256), 0, st, stage, items, out_at, n_items, paths, depth, ones, out);
+}
+
+// What the two windowed probes check before anything is launched, with the codes of gn_filter_emplace_path_window: the windows, then
+// every entry of every path -- the IBF and the bins in range, every IBF of h hash functions -- resolved into `dev`.  slab(s, d) says
+// whether the caller gave planes for the entry.
+template <typename Slab>
+static int gn_probe_window_resolve(const char* who, const gn_filter* f, uint32_t n_paths, const gn_path_entry* paths, uint32_t depth, const uint64_t* total_rows,
+                                   const uint64_t* row_begin, Slab slab, std::vector<GnProbeWinDev>& dev)
+{
+    for (size_t j = 0; j < f->ibfs.size(); ++j)
+    {
+        if (total_rows[j] == 0 || total_rows[j] > 0xFFFFFFFFull)
+            return gn_fail(GN_ERANGE, "%s: ibf %zu: an IBF of %llu rows, 1 .. 2^32 - 1 are supported", who, j, (unsigned long long)total_rows[j]);
+        if (row_begin[j] > total_rows[j] || f->ibfs[j].S > total_rows[j] - row_begin[j])
+            return gn_fail(GN_EINVAL, "%s: ibf %zu: rows %llu .. %llu of an IBF of %llu rows", who, j, (unsigned long long)row_begin[j],
+                           (unsigned long long)(row_begin[j] + f->ibfs[j].S), (unsigned long long)total_rows[j]);
+    }
+    const uint32_t h = f->ibfs[0].h;
+    if (h < 1 || h > GN_IBF_MAX_HASH_FUNS)
+        return gn_fail(GN_EINVAL, "%s: %u hash functions", who, h);
+    dev.assign((size_t)n_paths * depth, GnProbeWinDev{ nullptr, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0 });
+    for (uint32_t s = 0; s < n_paths; ++s)
+        for (uint32_t d = 0; d < depth && paths[(size_t)s * depth + d].n_bins != 0; ++d)
+        {
+            GnPathDev            o;
+            const gn_path_entry& e = paths[(size_t)s * depth + d];
+            if (const int rc = gn_path_resolve(who, f, e, s, d, false, 0, o))
+                return rc;
+            const GnIbfHost& ib = f->ibfs[e.ibf];
+            if (ib.h != h)
+                return gn_fail(GN_EINVAL, "%s: ibf %u has %u hash functions, ibf 0 has %u", who, e.ibf, ib.h, h);
+            dev[(size_t)s * depth + d] = GnProbeWinDev{ o.rows, total_rows[e.ibf], 0, o.Ws, (uint32_t)__builtin_clzll(total_rows[e.ibf]), o.first_bin, o.n_bins,
+                                                        (uint32_t)row_begin[e.ibf], (uint32_t)ib.S, slab(s, d) ? 1u : 0u, 0 };
+        }
+    return GN_OK;
+}
+
+namespace
+{
+struct GnProbeWindowStage // everything a call holds; freed when the call returns
+{
+    GnStreamPair                 streams;
+    GnPinned<uint64_t>           h_stage[2], h_out_at[2], h_out[2];
+    GnPinned<GnRunItem>          h_items[2];
+    GnDev<uint64_t>              d_stage[2], d_out_at[2];
+    GnDev<unsigned long long>    d_out[2];
+    GnDev<GnRunItem>             d_items[2];
+    GnDev<GnProbeWinDev>         d_paths;
+    GnDev<unsigned long long>    d_ones; // one word of all ones: what a row outside its piece reads
+    uint32_t                     n_items[2] = { 0, 0 };
+};
+} // namespace
+
+extern "C" int gn_filter_probe_path_window(gn_filter* f, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, const gn_path_entry* paths,
+                                           uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t* const* alive,
+                                           uint64_t* const* planes, uint64_t* lost_at, uint64_t chunk_hashes)
+{
+    static const char* const who = "gn_filter_probe_path_window";
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs an HIBF filter", who);
+    if (!total_rows || !row_begin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    if (n_sets && (!sets || !set_sizes || !paths || !alive || !lost_at || depth == 0))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    std::vector<GnProbeWinDev> dev;
+    if (const int rc = gn_probe_window_resolve(who, f, n_sets, paths, depth, total_rows, row_begin,
+                                               [&](uint32_t s, uint32_t d) { return planes && planes[(size_t)s * depth + d]; }, dev))
+        return rc;
+    if (n_sets == 0)
+        return GN_OK;
+    const uint32_t        h = f->ibfs[0].h;
+    uint64_t              total = 0, widest = GN_WIN_PER_LANE;
+    std::vector<uint64_t> item_words(n_sets, 0); // words an item of the set leaves in `out`
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        if (set_sizes[s] && (!sets[s] || !alive[s]))
+            return gn_fail(GN_EINVAL, "%s: set %u is null", who, s);
+        total += set_sizes[s];
+        for (uint32_t d = 0; d < depth && dev[(size_t)s * depth + d].n_bins != 0; ++d)
+            item_words[s] += (uint64_t)(dev[(size_t)s * depth + d].slab ? dev[(size_t)s * depth + d].n_bins : 1u) * GN_WIN_PER_LANE;
+        widest = std::max(widest, item_words[s]);
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    // a chunk is a multiple of an item, and no item is cut by the end of a chunk (below): every item starts at a multiple of GN_WIN_ITEM
+    // hashes of its set and owns whole words of the set's bitmaps
+    uint64_t chunk = chunk_hashes ? chunk_hashes : GN_WIN_CHUNK;
+    chunk          = std::min<uint64_t>((chunk + GN_WIN_ITEM - 1) / GN_WIN_ITEM * GN_WIN_ITEM, (total + GN_WIN_ITEM - 1) / GN_WIN_ITEM * GN_WIN_ITEM);
+    const uint64_t cap_items = chunk / 64 + 16;
+    const uint64_t cap_out   = std::max<uint64_t>(widest, chunk / 8); // words of answers a chunk may leave: one item's at least
+    GnProbeWindowStage g;
+    for (int b = 0; b < 2; ++b)
+    {
+        GN_HIP(hipStreamCreateWithFlags(&g.streams.st[b], hipStreamNonBlocking));
+        GN_HIP(g.h_stage[b].alloc(chunk));
+        GN_HIP(g.h_items[b].alloc(cap_items));
+        GN_HIP(g.h_out_at[b].alloc(cap_items));
+        GN_HIP(g.h_out[b].alloc(cap_out));
+        GN_HIP(g.d_stage[b].alloc(chunk));
+        GN_HIP(g.d_items[b].alloc(cap_items));
+        GN_HIP(g.d_out_at[b].alloc(cap_items));
+        GN_HIP(g.d_out[b].alloc(cap_out));
+    }
+    GN_HIP(g.d_paths.upload(dev.data(), dev.size()));
+    const unsigned long long all_ones = ~0ull;
+    GN_HIP(g.d_ones.upload(&all_ones, 1));
+    // the answers of the chunk that went through buffer b, ANDed into the caller's bitmaps (its stream has been waited for)
+    auto take = [&](uint32_t b) {
+        for (uint32_t k = 0; k < g.n_items[b]; ++k)
+        {
+            const GnRunItem& it = g.h_items[b][k];
+            const uint64_t*  o  = g.h_out[b] + g.h_out_at[b][k];
+            const uint32_t   s = it.run, nw = (it.cnt + 63u) / 64u;
+            const uint64_t   w0 = it.begin / 64, words = (set_sizes[s] + 63) / 64;
+            for (uint32_t d = 0; d < depth && dev[(size_t)s * depth + d].n_bins != 0; ++d)
+            {
+                const GnProbeWinDev& e = dev[(size_t)s * depth + d];
+                if (!e.slab)
+                {
+                    uint64_t lost = 0;
+                    for (uint32_t j = 0; j < nw; ++j)
+                    {
+                        const uint32_t left  = it.cnt - j * 64u;
+                        const uint64_t valid = left >= 64u ? ~0ull : (1ull << left) - 1;
+                        lost += (uint64_t)__builtin_popcountll(valid & ~o[j]);
+                        alive[s][w0 + j] &= o[j] | ~valid; // (bits behind the set's last hash stay as they are: zero)
+                    }
+                    lost_at[(size_t)s * depth + d] += lost;
+                    o += GN_WIN_PER_LANE;
+                    continue;
+                }
+                uint64_t* pl = planes[(size_t)s * depth + d];
+                for (uint32_t bin = 0; bin < e.n_bins; ++bin, o += GN_WIN_PER_LANE)
+                    for (uint32_t j = 0; j < nw; ++j)
+                        pl[(uint64_t)bin * words + w0 + j] &= o[j];
+            }
+        }
+        g.n_items[b] = 0;
+    };
+    std::vector<GnRunItem> items;
+    GnRunCursor            cur;
+    hipError_t             err = hipSuccess;
+    for (uint32_t c = 0; err == hipSuccess; ++c)
+    {
+        const uint32_t b = c & 1u;
+        if ((err = hipStreamSynchronize(g.streams.st[b])) != hipSuccess)
+            break;
+        take(b);
+        uint64_t taken = gn_window_next_chunk(set_sizes, n_sets, cur, chunk, cap_items, items);
+        if (taken == 0)
+            break;
+        // an item the end of the chunk has cut goes to the next chunk whole, and so do the items whose answers the buffer does not hold
+        uint64_t words = 0;
+        size_t   keep  = 0;
+        for (; keep < items.size(); ++keep)
+        {
+            const GnRunItem& it = items[keep];
+            if (it.cnt < GN_WIN_ITEM && it.begin + it.cnt < set_sizes[it.run])
+                break;
+            if (keep && words + item_words[it.run] > cap_out)
+                break;
+            g.h_out_at[b][keep] = words;
+            words += item_words[it.run];
+        }
+        if (keep < items.size())
+        {
+            cur.run = items[keep].run, cur.at = items[keep].begin;
+            taken = items[keep].stage_at;
+            items.resize(keep);
+        }
+        for (const GnRunItem& it : items)
+            memcpy(g.h_stage[b] + it.stage_at, sets[it.run] + it.begin, (size_t)it.cnt * 8);
+        memcpy(g.h_items[b].get(), items.data(), items.size() * sizeof(GnRunItem));
+        const uint32_t n_items = (uint32_t)items.size();
+        hipStream_t    st = g.streams.st[b];
+        if ((err = hipMemcpyAsync(g.d_stage[b], g.h_stage[b], taken * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (err = hipMemcpyAsync(g.d_items[b], g.h_items[b], n_items * sizeof(GnRunItem), hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (err = hipMemcpyAsync(g.d_out_at[b], g.h_out_at[b], n_items * sizeof(uint64_t), hipMemcpyHostToDevice, st)) != hipSuccess)
+            break;
+        const uint64_t*      d_stage = g.d_stage[b];
+        const GnRunItem*     d_items = g.d_items[b];
+        const uint64_t*      d_at    = g.d_out_at[b];
+        const GnProbeWinDev* d_paths = g.d_paths;
+        switch (h)
+        {
+        case 1: gn_probe_path_window_launch<1>(st, d_stage, d_items, d_at, n_items, d_paths, depth, g.d_ones, g.d_out[b]); break;
+        case 2: gn_probe_path_window_launch<2>(st, d_stage, d_items, d_at, n_items, d_paths, depth, g.d_ones, g.d_out[b]); break;
+        case 3: gn_probe_path_window_launch<3>(st, d_stage, d_items, d_at, n_items, d_paths, depth, g.d_ones, g.d_out[b]); break;
+        case 4: gn_probe_path_window_launch<4>(st, d_stage, d_items, d_at, n_items, d_paths, depth, g.d_ones, g.d_out[b]); break;
+        default: gn_probe_path_window_launch<5>(st, d_stage, d_items, d_at, n_items, d_paths, depth, g.d_ones, g.d_out[b]); break;
+        }
+        if ((err = hipGetLastError()) != hipSuccess || (words && (err = hipMemcpyAsync(g.h_out[b], g.d_out[b], words * 8, hipMemcpyDeviceToHost, st)) != hipSuccess))
+            break;
+        g.n_items[b] = n_items;
+    }
+    // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
+    const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
+    GN_HIP(err);
+    GN_HIP(e0);
+    GN_HIP(e1);
+    take(0), take(1);
+    return GN_OK;
+}
+
+// The shape of gn_probe_shared_kernel: a lane owns a path, a wave 64 paths and `chunks` chunks of 64 probes; word c of the lane's `alive`
+// bitmap is its mask of chunk c.  An entry in a whole piece clears the probes it does not hold from the mask, as there.  An entry in a slab
+// ANDs per-bin masks into the lane's planes (plane b at plane_at + b * n_chunks): eight bins at a time in registers, so the rows of a probe
+// are fetched once per eight bins of a word.  A row outside the piece contributes all ones.  No ballots, no atomics: the lane owns every
+// word it writes.  A probe that an earlier entry or part has cleared from `alive` is not looked at again -- its planes then say nothing,
+// and nobody asks them: the caller ANDs the closed planes into `alive`.
+template <uint32_t H>
+__global__ __launch_bounds__(256) void gn_probe_shared_window_kernel(const uint64_t* __restrict__ probes, uint64_t n, const GnProbeWinDev* __restrict__ paths,
+                                                                     uint32_t n_paths, uint32_t depth, uint32_t path_waves, uint32_t chunks,
+                                                                     unsigned long long* __restrict__ alive_words, unsigned long long* __restrict__ planes)
+{
+    const uint32_t wave     = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const uint32_t group    = wave % path_waves;
+    const uint64_t c0       = (uint64_t)(wave / path_waves) * chunks;
+    const uint64_t n_chunks = (n + 63) / 64;
+    const uint32_t path     = group * 64u + (threadIdx.x & 63u);
+    const bool     mine     = path < n_paths;
+    const GnProbeWinDev* __restrict__ p = paths + (uint64_t)(mine ? path : 0) * depth;
+    for (uint64_t c = c0; c < c0 + chunks && c < n_chunks; ++c)
+    {
+        const uint64_t* __restrict__ pr  = probes + c * 64u;
+        const uint32_t               cnt = (uint32_t)min((uint64_t)64, n - c * 64u);
+        uint64_t                     alive = mine ? alive_words[(uint64_t)path * n_chunks + c] : 0;
+        for (uint32_t d = depth; d-- > 0;)
+        {
+            const GnProbeWinDev e    = p[d];
+            const bool          used = e.n_bins != 0 && alive != 0;
+            if (__ballot(used) == 0)
+                continue;
+            GnGlobalConstWord* rows = (GnGlobalConstWord*)e.rows;
+            const uint32_t     w0 = e.first_bin >> 6, w1 = used ? (e.first_bin + e.n_bins - 1) >> 6 : w0;
+            // the AND of the probe's rows inside the piece at word w
+            auto rows_and = [&](uint64_t v, uint32_t w) {
+                uint64_t a = ~0ULL;
+#pragma unroll
+                for (uint32_t i = 0; i < H; ++i)
+                {
+                    uint32_t   local;
+                    const bool inside = gn_window_local(gn_build_row(v, i, e.shift, e.S_total), e.row_begin, e.n_rows, &local);
+                    const uint64_t r  = rows[(uint64_t)(inside ? local : 0u) * e.Ws + w];
+                    a &= inside ? r : ~0ULL;
+                }
+                return a;
+            };
+            if (!e.slab || !used)
+            {
+                for (uint32_t q = 0; q < cnt; ++q)
+                {
+                    const uint64_t v = pr[q];
+                    if (!used || !((alive >> q) & 1))
+                        continue;
+                    bool hit = false;
+                    for (uint32_t w = w0; w <= w1 && !hit; ++w)
+                        hit = (rows_and(v, w) & gn_run_mask(e.first_bin, e.n_bins, w)) != 0;
+                    if (!hit)
+                        alive &= ~(1ULL << q);
+                }
+                continue;
+            }
+            unsigned long long* __restrict__ pl = planes + e.plane_at + c;
+            for (uint32_t w = w0; w <= w1; ++w)
+            {
+                const uint32_t b_lo = max(e.first_bin, w << 6), b_hi = min(e.first_bin + e.n_bins, (w + 1u) << 6);
+                for (uint32_t b0 = b_lo; b0 < b_hi; b0 += 8u)
+                {
+                    uint64_t m[8];
+#pragma unroll
+                    for (uint32_t t = 0; t < 8u; ++t)
+                        m[t] = ~0ULL;
+                    for (uint32_t q = 0; q < cnt; ++q)
+                    {
+                        const uint64_t v = pr[q];
+                        if (!((alive >> q) & 1))
+                            continue;
+                        const uint64_t a = rows_and(v, w) >> (b0 & 63u);
+#pragma unroll
+                        for (uint32_t t = 0; t < 8u; ++t)
+                            m[t] &= ~(((~a >> t) & 1ULL) << q);
+                    }
+#pragma unroll
+                    for (uint32_t t = 0; t < 8u; ++t)
+                        if (b0 + t < b_hi)
+                            pl[(uint64_t)(b0 + t - e.first_bin) * n_chunks] &= m[t];
+                }
+            }
+        }
+        if (mine)
+            alive_words[(uint64_t)path * n_chunks + c] = alive;
+    }
+}
+
+extern "C" int gn_filter_probe_paths_shared_window(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths,
+                                                   uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t* alive,
+                                                   uint64_t* const* planes)
+{
+    static const char* const who = "gn_filter_probe_paths_shared_window";
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs an HIBF filter", who);
+    if (!total_rows || !row_begin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    if (n_paths && (!paths || depth == 0 || (n && (!probes || !alive))))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    std::vector<GnProbeWinDev> dev;
+    if (const int rc = gn_probe_window_resolve(who, f, n_paths, paths, depth, total_rows, row_begin,
+                                               [&](uint32_t s, uint32_t d) { return planes && planes[(size_t)s * depth + d]; }, dev))
+        return rc;
+    if (n_paths == 0 || n == 0)
+        return GN_OK;
+    const uint32_t h        = f->ibfs[0].h;
+    const uint64_t n_chunks = (n + 63) / 64, path_waves = ((uint64_t)n_paths + 63) / 64;
+    const uint64_t chunks   = std::max<uint64_t>(1, (n_chunks * path_waves + 8191) / 8192);
+    const uint64_t waves    = path_waves * ((n_chunks + chunks - 1) / chunks);
+    if (chunks > 0xFFFFFFFFull || (waves + 3) / 4 > 0x7FFFFFFFull)
+        return gn_fail(GN_ERANGE, "%s: %llu probes against %u paths in one call", who, (unsigned long long)n, n_paths);
+    // the planes of the call behind each other, in the order of the entries
+    uint64_t plane_words = 0;
+    for (GnProbeWinDev& e : dev)
+        if (e.n_bins && e.slab)
+            e.plane_at = plane_words, plane_words += (uint64_t)e.n_bins * n_chunks;
+    std::vector<uint64_t> h_planes(plane_words);
+    for (size_t k = 0; k < dev.size(); ++k)
+        if (dev[k].n_bins && dev[k].slab)
+            memcpy(h_planes.data() + dev[k].plane_at, planes[k], (size_t)dev[k].n_bins * n_chunks * 8);
+    GN_HIP(hipSetDevice(f->device));
+    if (!f->load_st)
+        GN_HIP(hipStreamCreateWithFlags(&f->load_st, hipStreamNonBlocking));
+    GnDev<uint64_t>           d_probes;
+    GnDev<GnProbeWinDev>      d_paths;
+    GnDev<unsigned long long> d_alive, d_planes;
+    std::vector<uint64_t>     h_alive((size_t)n_paths * n_chunks);
+    GN_HIP(d_probes.alloc(n));
+    GN_HIP(d_paths.alloc(dev.size()));
+    GN_HIP(d_alive.alloc(h_alive.size()));
+    GN_HIP(d_planes.alloc(std::max<uint64_t>(plane_words, 1)));
+    GN_HIP(hipMemcpyAsync(d_probes, probes, n * 8, hipMemcpyHostToDevice, f->load_st));
+    GN_HIP(hipMemcpyAsync(d_paths, dev.data(), dev.size() * sizeof(GnProbeWinDev), hipMemcpyHostToDevice, f->load_st));
+    GN_HIP(hipMemcpyAsync(d_alive, alive, h_alive.size() * 8, hipMemcpyHostToDevice, f->load_st));
+    if (plane_words)
+        GN_HIP(hipMemcpyAsync(d_planes, h_planes.data(), plane_words * 8, hipMemcpyHostToDevice, f->load_st));
+    const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
+    switch (h)
+    {
+    case 1: hipLaunchKernelGGL(gn_probe_shared_window_kernel<1>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_alive, d_planes); break;
+    case 2: hipLaunchKernelGGL(gn_probe_shared_window_kernel<2>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_alive, d_planes); break;
+    case 3: hipLaunchKernelGGL(gn_probe_shared_window_kernel<3>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_alive, d_planes); break;
+    case 4: hipLaunchKernelGGL(gn_probe_shared_window_kernel<4>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_alive, d_planes); break;
+    default: hipLaunchKernelGGL(gn_probe_shared_window_kernel<5>, grid, block, 0, f->load_st, d_probes, n, d_paths, n_paths, depth, (uint32_t)path_waves, (uint32_t)chunks, d_alive, d_planes); break;
+    }
+    GN_HIP(hipGetLastError());
+    // into buffers of the call's own first: a copy that fails leaves the caller's as they were
+    GN_HIP(hipMemcpyAsync(h_alive.data(), d_alive, h_alive.size() * 8, hipMemcpyDeviceToHost, f->load_st));
+    if (plane_words)
+        GN_HIP(hipMemcpyAsync(h_planes.data(), d_planes, plane_words * 8, hipMemcpyDeviceToHost, f->load_st));
+    GN_HIP(hipStreamSynchronize(f->load_st));
+    memcpy(alive, h_alive.data(), h_alive.size() * 8);
+    for (size_t k = 0; k < dev.size(); ++k)
+        if (dev[k].n_bins && dev[k].slab)
+            memcpy(planes[k], h_planes.data() + dev[k].plane_at, (size_t)dev[k].n_bins * n_chunks * 8);
+    return GN_OK;
+}
+
 // ---- gn_filter_extend_path: more hashes for user bins that are filled already ------------------------------------------------------
 // Two sweeps over the items of the whole call, as gn_path_rounds cuts them; item g of the call is item g - item_base of its round.
 // Sweep 1 is the probe restricted to entry 0 (the user bin's leaf run): per word of the run all 8 * H row words are loaded before any is

@@ -37,7 +37,8 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_filter_bin_popcounts", "gn_filter_copy_ibf", "gn_filter_copy_ibf_spans", "gn_filter_fold_ibf", "gn_filter_extend_path",
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table",
                "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window",
-               "gn_stream_distinct_hashes_packed", "gn_filter_emplace_packed_window"]
+               "gn_stream_distinct_hashes_packed", "gn_filter_emplace_packed_window",
+               "gn_filter_probe_path_window", "gn_filter_probe_paths_shared_window"]
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -173,6 +174,8 @@ def load_library():
     L.gn_filter_emplace_path_window.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, u64]
     L.gn_filter_probe_path.argtypes =[vp, vp, vp, u32, vp, u32, vp, vp, vp]
     L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
+    L.gn_filter_probe_path_window.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u64]
+    L.gn_filter_probe_paths_shared_window.argtypes = [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp]
     L.gn_filter_bin_popcounts.argtypes = [vp, u32, vp]
     L.gn_filter_copy_ibf.argtypes = [vp, u32, vp, u32]
     L.gn_filter_copy_ibf_spans.argtypes = [vp, u32, vp, u32, vp, u32]
@@ -725,6 +728,50 @@ class HipFilter:
         _check(load_library().gn_filter_probe_paths_shared(self._h, _p(probes), len(probes), paths.ctypes.data_as(C.c_void_p), paths.shape[0],
                                                            paths.shape[1], _p(found)))
         return found
+
+    def _plane_pointers(self, planes, n: int, depth: int):
+        """planes: None, or {(path, entry): C-contiguous uint64 [n_bins, words]} -> the array of n * depth pointers the library takes"""
+        if not planes:
+            return None
+        ptrs = (C.c_void_p * (n * depth))()
+        for (s, d), a in planes.items():
+            assert a.dtype == np.uint64 and a.flags.c_contiguous and a.flags.writeable and 0 <= s < n and 0 <= d < depth
+            ptrs[s * depth + d] = a.ctypes.data
+        return ptrs
+
+    def probe_path_window(self, sets: Sequence[np.ndarray], paths: np.ndarray, total_rows, row_begin, alive: Sequence[np.ndarray],
+                          lost_at: np.ndarray, planes=None, chunk_hashes: int = 0) -> None:
+        """gn_filter_probe_path_window on a storage filter of pieces (see emplace_path_window for total_rows / row_begin).  In/out, only ever
+        ANDed into (lost_at: added to): alive[s] uint64 [ceil(len(sets[s]) / 64)], lost_at uint64 [len(sets), depth], planes
+        {(s, d): uint64 [n_bins, ceil(len(sets[s]) / 64)]} for the entries whose piece is a slab of its IBF"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(sets) == len(alive)
+        sets = [np.ascontiguousarray(a, dtype=np.uint64) for a in sets]
+        assert all(a.dtype == np.uint64 and a.flags.c_contiguous and len(a) == (len(x) + 63) // 64 for a, x in zip(alive, sets))
+        assert lost_at.dtype == np.uint64 and lost_at.flags.c_contiguous and lost_at.shape == paths.shape
+        ptrs = (C.c_void_p * max(len(sets), 1))(*[a.ctypes.data for a in sets])
+        aptrs = (C.c_void_p * max(len(sets), 1))(*[a.ctypes.data for a in alive])
+        sizes = np.array([len(a) for a in sets], dtype=np.uint64)
+        total = np.ascontiguousarray(total_rows, dtype=np.uint64)
+        begin = np.ascontiguousarray(row_begin, dtype=np.uint64)
+        assert len(total) == len(begin) == len(self._bins)
+        _check(load_library().gn_filter_probe_path_window(self._h, ptrs, _p(sizes), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1], _p(total),
+                                                          _p(begin), aptrs, self._plane_pointers(planes, len(sets), paths.shape[1]), _p(lost_at),
+                                                          chunk_hashes))
+
+    def probe_paths_shared_window(self, probes: np.ndarray, paths: np.ndarray, total_rows, row_begin, alive: np.ndarray, planes=None) -> None:
+        """gn_filter_probe_paths_shared_window: alive uint64 [n_paths, ceil(len(probes) / 64)] in/out; planes {(p, d): uint64 [n_bins,
+        ceil(len(probes) / 64)]} for the entries whose piece is a slab of its IBF"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2
+        probes = np.ascontiguousarray(probes, dtype=np.uint64)
+        assert alive.dtype == np.uint64 and alive.flags.c_contiguous and alive.shape == (paths.shape[0], (len(probes) + 63) // 64)
+        total = np.ascontiguousarray(total_rows, dtype=np.uint64)
+        begin = np.ascontiguousarray(row_begin, dtype=np.uint64)
+        assert len(total) == len(begin) == len(self._bins)
+        _check(load_library().gn_filter_probe_paths_shared_window(self._h, _p(probes), len(probes), paths.ctypes.data_as(C.c_void_p), paths.shape[0],
+                                                                  paths.shape[1], _p(total), _p(begin), _p(alive),
+                                                                  self._plane_pointers(planes, paths.shape[0], paths.shape[1])))
 
     def bin_popcounts(self, bins: Optional[int] = None, ibf_idx: int = 0) -> np.ndarray:
         """gn_filter_bin_popcounts: set bits per technical bin of IBF ibf_idx -> uint64 [bins of that IBF].  The library writes as many

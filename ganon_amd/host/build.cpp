@@ -17,7 +17,7 @@
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
 //
 // The hierarchical modes (this project's extensions, like --device) take the same hash sets: --hibf (build_hibf.cpp),
-// --hibf --verify-index (build_verify.cpp), --hibf --update (build_update.cpp).  The files are written by build_write.cpp.
+// --hibf --verify-index (build_verify.cpp; in parts build_verify_parts.cpp), --hibf --update (build_update.cpp).  The files are written by build_write.cpp.
 //
 // Differences from the reference that cannot be avoided here: targets are laid out in the order of
 // their first appearance in the input file and a target's hashes in ascending order -- the reference uses the iteration
@@ -122,6 +122,12 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
     }
     if (c.hibf_memory_given && c.hibf_memory == 0)
         return say("--hibf-memory has to be > 0");
+    // ... and so has the check of an index in parts (--hibf-memory and --hibf-devices stay the build's)
+    for (const auto& [given, name] : { std::pair<bool, const char*>{ c.verify_memory_given, "--verify-memory" }, { c.verify_devices_given, "--verify-devices" } })
+        if (given && !c.verify_given)
+            return say(std::string(name) + " needs --verify-index (it says in what parts an index is checked; a build in parts takes --hibf-memory and --hibf-devices)");
+    if (c.verify_memory_given && c.verify_memory == 0)
+        return say("--verify-memory has to be > 0");
     if (c.tmax_given && !c.hibf)
         return say("--tmax needs --hibf");
     if (c.layout_given && !c.hibf)
@@ -257,6 +263,15 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--layout            " << c.layout << '\n';
     if (c.verify_given)
         std::cerr << "--verify-index      " << c.verify_index << '\n';
+    if (c.verify_memory_given)
+        std::cerr << "--verify-memory     " << c.verify_memory << '\n';
+    if (c.verify_devices_given)
+    {
+        std::cerr << "--verify-devices    ";
+        for (size_t i = 0; i < c.verify_devices.size(); ++i)
+            std::cerr << (i ? "," : "") << c.verify_devices[i];
+        std::cerr << '\n';
+    }
     if (c.update_given)
         std::cerr << "--update            " << c.update << '\n';
     if (c.extend)
@@ -321,6 +336,13 @@ const char* kHelp =
     "                               target's minimiser the user bin answers to (WARN fp when clearly above the index's fpr;\n"
     "                               a warning does not fail).  k, w and the hash functions come from the index; give the\n"
     "                               --min-length of the build.  Not with --output-file\n"
+    "      --verify-memory arg      [--verify-index] most device bytes of IBF rows held on an entry of --verify-devices at one time\n"
+    "                               (rows as the device pads them).  An index larger than that is checked in parts -- whole IBFs\n"
+    "                               grouped in file order, an IBF over the budget in slabs of rows -- and what a hash's rows in\n"
+    "                               other parts said is carried along in host memory: the same report.  Default: what the device\n"
+    "                               has free when loading starts, less staging and a reserve, shared among the entries that name it\n"
+    "      --verify-devices arg     [--verify-index] a list a,b,... (an index may repeat): the parts are dealt to its entries, one\n"
+    "                               worker each.  Default: the single --device\n"
     "      --update arg             [--hibf] add the targets of --input-file to the index `arg` and write the result to\n"
     "                               --output-file; `arg` is left as it is.  The old genomes are not needed: how full every bin is\n"
     "                               is read off the index's bits.  The tree is kept: a new target goes below a merged bin that\n"
@@ -399,7 +421,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--verify-memory", "--verify-devices", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -506,6 +528,10 @@ int parse_args(int argc, char** argv, Config& c)
             c.hibf_devices = device_list("--hibf-devices"), c.hibf_devices_given = true;
         if (vals.count("--hibf-memory"))
             c.hibf_memory = u("--hibf-memory", ~0ull), c.hibf_memory_given = true;
+        if (vals.count("--verify-devices"))
+            c.verify_devices = device_list("--verify-devices"), c.verify_devices_given = true;
+        if (vals.count("--verify-memory"))
+            c.verify_memory = u("--verify-memory", ~0ull), c.verify_memory_given = true;
         c.verbose = vals.count("--verbose") && vals["--verbose"] != "false";
         c.quiet   = vals.count("--quiet") && vals["--quiet"] != "false";
         c.extend  = vals.count("--extend") && vals["--extend"] != "false";
@@ -686,6 +712,9 @@ bool run(Config c)
     for (int d : c.hibf_devices)
         if (d >= n_dev)
             return fail("--hibf-devices " + std::to_string(d) + " does not exist (" + std::to_string(n_dev) + " visible)");
+    for (int d : c.verify_devices)
+        if (d >= n_dev)
+            return fail("--verify-devices " + std::to_string(d) + " does not exist (" + std::to_string(n_dev) + " visible)");
 
     Totals              totals;
     const bool          remove_only = (c.remove_given || c.fold_given) && c.input_file.empty();

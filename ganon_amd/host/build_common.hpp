@@ -56,6 +56,9 @@ struct Config // Config.hpp:10-27
                                  //  similarity = hibf_layout_similarity.hpp: sketch over an order that groups related targets)
     bool        layout_given = false;
     std::string verify_index;    // (--hibf only: check this index against the inputs instead of building one)
+    uint64_t    verify_memory = 0; // (--verify-memory: most device bytes of IBF rows on an entry of verify_devices at one time; 0 = from what is free)
+    bool        verify_memory_given = false, verify_devices_given = false;
+    std::vector<int> verify_devices; // (--verify-devices a,b,...: the entries the parts of an index are dealt to; empty = the single --device)
     std::string update;          // (--hibf only: add the inputs' targets to this index and write the result to --output-file)
     bool        update_given = false, max_fp_given = false, mode_given = false;
     bool        extend = false;  // (--update only: a target the index holds gains the inputs' sequences)
@@ -264,6 +267,10 @@ bool fill_and_save_hibf_parts(const HibfPartsFill& w, uint64_t& hash_bytes_uploa
 
 // the modes, after the inputs are hashed (build.cpp: run)
 bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting);   // build_hibf.cpp
+// build_verify_parts.cpp: the same check of an index that does not fit what an entry of `devices` may hold at one time, part by part
+// (hibf_build_parts.hpp: the plan; hibf_verify_parts.hpp: what is carried from part to part); the same report on stdout
+bool run_verify_parts(const Config& c, std::vector<Target>& targets, const gnhost::FilterMeta& meta, const std::vector<uint64_t>& payload_at,
+                      const HibfPartPlan& plan, const std::vector<int>& devices, double hash_s);
 bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counting);                                  // build_verify.cpp
 bool run_update(const Config& c, std::vector<Target>& targets, const Lap& counting);                                  // build_update.cpp
 

@@ -3,8 +3,9 @@
 // target found in every IBF on the user bin's root-to-leaf path (gn_filter_probe_path along hibf_paths.hpp:derive_paths -- the paths
 // come from the FILE's tables, whoever wrote it), and how often does the user bin answer to values that are no target's minimiser
 // (gn_filter_probe_paths_shared).
-#include "build_common.hpp"
-#include "hibf_paths.hpp"
+// An index that does not fit what the device may hold at one time (--verify-memory, or what is free) is checked in parts over
+// --verify-devices instead (build_verify_parts.cpp) and gives the same report, which is why the report is a function of its own here.
+#include "build_verify.hpp"
 #include "hibf_pool.hpp"
 
 #include <algorithm>
@@ -17,8 +18,6 @@ namespace gnbuild
 
 namespace
 {
-
-constexpr uint64_t kVerifyProbes = 65536; // P of the false-positive pass
 
 // probe i of the false-positive pass (include/ganon_hip.h states the generator): splitmix64 of i + 1 with bit 63 set -- a
 // (k,w)-minimiser hash is below 4^k, so for k <= 31 no target holds such a value
@@ -33,6 +32,95 @@ uint64_t verify_probe(uint64_t i)
 
 } // namespace
 
+std::vector<uint64_t> verify_probes()
+{
+    std::vector<uint64_t> probes(kVerifyProbes);
+    for (uint64_t i = 0; i < kVerifyProbes; ++i)
+        probes[i] = verify_probe(i);
+    return probes;
+}
+
+bool print_verify_report(const Config& c, const std::vector<Target>& targets, const gnhost::FilterMeta& meta, const gnhibf::Paths& paths, const VerifyCounts& r,
+                         const VerifyLookup& lookup)
+{
+    constexpr uint64_t           none = ~0ull;
+    const std::vector<uint64_t>& user = r.user, &found = r.found, &first_lost = r.first_lost, &false_hits = r.false_hits;
+    const uint64_t               looked_up = r.looked_up, n_user = meta.n_user_bins;
+    const bool                   fp_pass = r.fp_pass;
+    const uint32_t               depth = paths.depth;
+    const unsigned               k = meta.ibf_config.kmer_size, h = (unsigned)meta.shapes.at(0).hash_funs;
+    const double                 fpr = meta.ibf_config.max_fp;
+    const double                 P = (double)kVerifyProbes;
+    const uint64_t               warn_above = (uint64_t)std::ceil(P * fpr + 4.0 * std::sqrt(P * fpr * (1.0 - fpr)));
+
+    std::cout << "index\t" << c.verify_index << "\tk=" << k << " w=" << meta.ibf_config.window_size << " h=" << h << " ibfs=" << meta.shapes.size()
+              << " levels=" << depth << " user_bins=" << n_user << " fpr=" << fpr << "\n";
+    std::cout << "#target\tuser_bin\tleaf_ibf\tbins\tdepth\tdistinct_hashes\tmissing\tfalse_hits\tobserved_fp\tverdict\n";
+    uint64_t          n_checked = 0, n_bad = 0, fp_sum = 0, fp_max = 0;
+    std::vector<bool> named(n_user, false);
+    std::cout << std::fixed << std::setprecision(6);
+    for (size_t t = 0; t < targets.size(); ++t)
+    {
+        const std::vector<uint64_t>& hs = targets[t].hashes;
+        if (user[t] == none)
+        {
+            // a target without a hash has no user bin in an index built from these inputs: nothing to look for
+            std::cout << targets[t].name << "\t-\t-\t0\t0\t" << hs.size() << "\t0\t" << (fp_pass ? "0" : "n/a") << "\t" << (fp_pass ? "0.000000" : "n/a") << "\t"
+                      << (hs.empty() ? "ok" : "FAIL: no such user bin") << "\n";
+            n_bad += !hs.empty();
+            continue;
+        }
+        const gn_path_entry* p = &paths.entries[user[t] * depth];
+        uint32_t             used = 0;
+        while (used < depth && p[used].n_bins)
+            ++used;
+        const uint64_t missing = hs.size() - found[t], hits = false_hits[user[t]];
+        const bool     warn    = fp_pass && hits > warn_above;
+        ++n_checked;
+        named[user[t]] = true;
+        n_bad += missing != 0;
+        fp_sum += hits, fp_max = std::max(fp_max, hits);
+        std::cout << targets[t].name << "\t" << user[t] << "\t" << p[0].ibf << "\t" << p[0].n_bins << "\t" << used << "\t" << hs.size() << "\t" << missing << "\t";
+        if (fp_pass)
+            std::cout << hits << "\t" << hits / P;
+        else
+            std::cout << "n/a\tn/a";
+        std::cout << "\t" << (missing ? "FAIL" : warn ? "WARN fp" : "ok") << "\n";
+        if (missing)
+        {
+            // the first false negative: its hash, the first entry of the path that lacks it, its h rows there and the bits found
+            const uint64_t          v = hs[first_lost[t]];
+            std::vector<uint64_t>   rows, words;
+            const uint32_t          d = lookup(p, used, v, rows, words);
+            const gnhost::IbfShape& m = meta.shapes.at(p[d].ibf);
+            std::cout << "  first false negative: hash " << v << " (index " << first_lost[t] << " of the sorted distinct hashes); lost at level " << d << ", ibf "
+                      << p[d].ibf << ", bins " << p[d].first_bin << ".." << p[d].first_bin + p[d].n_bins - 1 << "; rows";
+            for (auto r : rows)
+                std::cout << " " << r;
+            std::cout << "; bits [bin: one per hash function]";
+            for (uint32_t b = p[d].first_bin; b < p[d].first_bin + p[d].n_bins && b < p[d].first_bin + 8; ++b)
+            {
+                std::cout << " [" << b << ":";
+                for (unsigned i = 0; i < m.hash_funs; ++i)
+                    std::cout << " " << ((words[i * m.bin_words + (b >> 6)] >> (b & 63)) & 1);
+                std::cout << "]";
+            }
+            std::cout << "\n";
+        }
+    }
+    uint64_t unnamed = 0;
+    for (uint64_t u = 0; u < n_user; ++u)
+        unnamed += !named[u];
+    std::cout << "result\t" << (n_bad ? "FAIL" : "ok") << "\t" << n_checked << " target(s) checked, " << n_bad << " failing, " << unnamed
+              << " user bin(s) of the index not named by the input, " << looked_up << " distinct minimisers looked up, max_observed_fp ";
+    if (fp_pass)
+        std::cout << fp_max / P << ", mean_observed_fp " << (n_checked ? fp_sum / P / (double)n_checked : 0.0);
+    else
+        std::cout << "n/a, mean_observed_fp n/a";
+    std::cout << std::endl;
+    return n_bad == 0 && n_checked > 0;
+}
+
 bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counting)
 {
     auto t0 = std::chrono::steady_clock::now();
@@ -40,11 +128,46 @@ bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counti
         if (!unite_files(c, tg))
             return fail(gn_last_error());
     const double hash_s = counting.seconds() + since(t0);
+    // the parts the index is checked in: one when it fits what an entry of the list may hold at one time
+    const std::vector<int> entries = c.verify_devices.empty() ? std::vector<int>{ c.device } : c.verify_devices;
+    {
+        gnhost::FilterMeta    meta;
+        std::vector<uint64_t> payload_at;
+        try
+        {
+            gnhost::read_hibf_meta(c.verify_index, meta, payload_at);
+        }
+        catch (const std::exception& e)
+        {
+            return fail(std::string("ERROR: ") + e.what());
+        }
+        uint64_t budget = c.verify_memory;
+        if (!c.verify_memory_given)
+        {
+            std::string why;
+            if (!budget_from_free_memory(entries, budget, why))
+                return fail(why);
+        }
+        HibfPartPlan plan;
+        try
+        {
+            std::vector<uint64_t> rows, row_bytes;
+            for (const gnhost::IbfShape& m : meta.shapes)
+                rows.push_back(m.bin_size), row_bytes.push_back(gn_hibf_row_stride_words(m.bin_words) * 8);
+            plan = plan_hibf_parts(rows, row_bytes, budget, (uint32_t)entries.size());
+        }
+        catch (const std::exception& e)
+        {
+            return fail(std::string(c.verify_memory_given ? "--verify-memory: " : "--verify-devices: ") + e.what());
+        }
+        if (plan.n_parts > 1)
+            return run_verify_parts(c, targets, meta, payload_at, plan, entries, hash_s);
+    }
     try
     {
         t0 = std::chrono::steady_clock::now();
         gnhost::FilterMeta meta;
-        gnhost::DeviceSink sink(c.device);
+        gnhost::DeviceSink sink(entries[0]);
         gnhost::load_filter_file(c.verify_index, true, meta, sink);
         gn_filter* const flt    = sink.filter();
         const double     load_s = since(t0);
@@ -104,15 +227,8 @@ bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counti
         std::vector<uint64_t> false_hits(n_user, 0);
         if (fp_pass && n_user)
         {
-            std::vector<uint64_t> probes(kVerifyProbes), order(n_user), got(n_user, 0);
-            for (uint64_t i = 0; i < kVerifyProbes; ++i)
-                probes[i] = verify_probe(i);
-            for (uint64_t u = 0; u < n_user; ++u)
-                order[u] = u;
-            std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
-                const gn_path_entry &x = paths.entries[a * depth], &y = paths.entries[b * depth];
-                return std::make_pair(x.ibf, x.first_bin) < std::make_pair(y.ibf, y.first_bin);
-            });
+            const std::vector<uint64_t> probes = verify_probes(), order = verify_fp_order(paths, n_user);
+            std::vector<uint64_t>       got(n_user, 0);
             std::vector<gn_path_entry> sorted;
             for (uint64_t u : order)
                 sorted.insert(sorted.end(), paths.entries.begin() + u * depth, paths.entries.begin() + (u + 1) * depth);
@@ -122,87 +238,29 @@ bool run_verify(const Config& c, std::vector<Target>& targets, const Lap& counti
                 false_hits[order[j]] = got[j];
         }
         const double fp_s = since(t0);
-        const double P = (double)kVerifyProbes;
-        const uint64_t warn_above = (uint64_t)std::ceil(P * fpr + 4.0 * std::sqrt(P * fpr * (1.0 - fpr)));
-
-        std::cout << "index\t" << c.verify_index << "\tk=" << k << " w=" << meta.ibf_config.window_size << " h=" << h << " ibfs=" << meta.shapes.size()
-                  << " levels=" << depth << " user_bins=" << n_user << " fpr=" << fpr << "\n";
-        std::cout << "#target\tuser_bin\tleaf_ibf\tbins\tdepth\tdistinct_hashes\tmissing\tfalse_hits\tobserved_fp\tverdict\n";
-        uint64_t          n_checked = 0, n_bad = 0, fp_sum = 0, fp_max = 0;
-        std::vector<bool> named(n_user, false);
-        std::cout << std::fixed << std::setprecision(6);
-        for (size_t t = 0; t < targets.size(); ++t)
-        {
-            const std::vector<uint64_t>& hs = targets[t].hashes;
-            if (user[t] == none)
-            {
-                // a target without a hash has no user bin in an index built from these inputs: nothing to look for
-                std::cout << targets[t].name << "\t-\t-\t0\t0\t" << hs.size() << "\t0\t" << (fp_pass ? "0" : "n/a") << "\t" << (fp_pass ? "0.000000" : "n/a") << "\t"
-                          << (hs.empty() ? "ok" : "FAIL: no such user bin") << "\n";
-                n_bad += !hs.empty();
-                continue;
-            }
-            const gn_path_entry* p = &paths.entries[user[t] * depth];
-            uint32_t             used = 0;
-            while (used < depth && p[used].n_bins)
-                ++used;
-            const uint64_t missing = hs.size() - found[t], hits = false_hits[user[t]];
-            const bool     warn    = fp_pass && hits > warn_above;
-            ++n_checked;
-            named[user[t]] = true;
-            n_bad += missing != 0;
-            fp_sum += hits, fp_max = std::max(fp_max, hits);
-            std::cout << targets[t].name << "\t" << user[t] << "\t" << p[0].ibf << "\t" << p[0].n_bins << "\t" << used << "\t" << hs.size() << "\t" << missing << "\t";
-            if (fp_pass)
-                std::cout << hits << "\t" << hits / P;
-            else
-                std::cout << "n/a\tn/a";
-            std::cout << "\t" << (missing ? "FAIL" : warn ? "WARN fp" : "ok") << "\n";
-            if (missing)
-            {
-                // the first false negative: its hash, the first entry of the path that lacks it, its h rows there and the bits found
-                const uint64_t        v = hs[first_lost[t]], one[2] = { 0, 1 };
-                uint64_t              f1 = 0, fl = 0;
-                std::vector<uint64_t> l1(depth, 0);
-                if (gn_filter_probe_path(flt, &v, one, 1, p, depth, &f1, l1.data(), &fl) != GN_OK)
-                    throw std::runtime_error(gn_last_error());
-                uint32_t d = 0;
-                while (d + 1 < used && l1[d] == 0)
-                    ++d;
-                const gnhost::IbfShape& m = meta.shapes.at(p[d].ibf);
-                std::vector<uint64_t>   rows(m.hash_funs), words(m.hash_funs * m.bin_words);
-                for (unsigned i = 0; i < m.hash_funs; ++i)
-                    rows[i] = gnhost::ibf_row(v, i, m);
-                if (gn_filter_download_row_list(flt, p[d].ibf, rows.data(), rows.size(), words.data()) != GN_OK)
-                    throw std::runtime_error(gn_last_error());
-                std::cout << "  first false negative: hash " << v << " (index " << first_lost[t] << " of the sorted distinct hashes); lost at level " << d << ", ibf "
-                          << p[d].ibf << ", bins " << p[d].first_bin << ".." << p[d].first_bin + p[d].n_bins - 1 << "; rows";
-                for (auto r : rows)
-                    std::cout << " " << r;
-                std::cout << "; bits [bin: one per hash function]";
-                for (uint32_t b = p[d].first_bin; b < p[d].first_bin + p[d].n_bins && b < p[d].first_bin + 8; ++b)
-                {
-                    std::cout << " [" << b << ":";
-                    for (unsigned i = 0; i < m.hash_funs; ++i)
-                        std::cout << " " << ((words[i * m.bin_words + (b >> 6)] >> (b & 63)) & 1);
-                    std::cout << "]";
-                }
-                std::cout << "\n";
-            }
-        }
-        uint64_t unnamed = 0;
-        for (uint64_t u = 0; u < n_user; ++u)
-            unnamed += !named[u];
-        std::cout << "result\t" << (n_bad ? "FAIL" : "ok") << "\t" << n_checked << " target(s) checked, " << n_bad << " failing, " << unnamed
-                  << " user bin(s) of the index not named by the input, " << looked_up << " distinct minimisers looked up, max_observed_fp ";
-        if (fp_pass)
-            std::cout << fp_max / P << ", mean_observed_fp " << (n_checked ? fp_sum / P / (double)n_checked : 0.0);
-        else
-            std::cout << "n/a, mean_observed_fp n/a";
-        std::cout << std::endl;
+        // the first false negative of a target: the first entry of the path that lacks the hash, its h rows there and their words
+        auto lookup = [&](const gn_path_entry* p, uint32_t used, uint64_t v, std::vector<uint64_t>& rows, std::vector<uint64_t>& words) {
+            const uint64_t        one[2] = { 0, 1 };
+            uint64_t              f1 = 0, fl = 0;
+            std::vector<uint64_t> l1(depth, 0);
+            if (gn_filter_probe_path(flt, &v, one, 1, p, depth, &f1, l1.data(), &fl) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+            uint32_t d = 0;
+            while (d + 1 < used && l1[d] == 0)
+                ++d;
+            const gnhost::IbfShape& m = meta.shapes.at(p[d].ibf);
+            rows.resize(m.hash_funs), words.resize(m.hash_funs * m.bin_words);
+            for (unsigned i = 0; i < m.hash_funs; ++i)
+                rows[i] = gnhost::ibf_row(v, i, m);
+            if (gn_filter_download_row_list(flt, p[d].ibf, rows.data(), rows.size(), words.data()) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+            return d;
+        };
+        const VerifyCounts counts{ user, found, first_lost, false_hits, looked_up, fp_pass };
+        const bool         ok = print_verify_report(c, targets, meta, paths, counts, lookup);
         if (c.verbose && !c.quiet)
             std::cerr << std::setprecision(6) << " - seconds: hash " << hash_s << " load " << load_s << " membership " << member_s << " fp " << fp_s << std::endl;
-        return n_bad == 0 && n_checked > 0;
+        return ok;
     }
     catch (const std::exception& e)
     {

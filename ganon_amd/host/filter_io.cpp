@@ -629,12 +629,17 @@ void load_filter_file(const std::string& path, bool hibf, FilterMeta& meta, Filt
         load_ibf(path, meta, sink);
 }
 
-void read_hibf_meta(const std::string& path, FilterMeta& meta)
+void read_hibf_meta(const std::string& path, FilterMeta& meta, std::vector<uint64_t>& payload_at)
 {
     meta = FilterMeta();
-    Reader                r(path);
-    std::vector<uint64_t> payload_at;
+    Reader r(path);
     parse_hibf(r, meta, payload_at);
+}
+
+void read_hibf_meta(const std::string& path, FilterMeta& meta)
+{
+    std::vector<uint64_t> payload_at;
+    read_hibf_meta(path, meta, payload_at);
 }
 
 bool inspect_filter_file(const std::string& path, bool hibf, std::ostream& out)

@@ -104,6 +104,8 @@ void load_filter_file(const std::string& path, bool hibf, FilterMeta& meta, Filt
 
 // Everything of a raptor .hibf but its bits (what load_filter_file leaves in `meta`): no sink, no device.  Throws likewise.
 void read_hibf_meta(const std::string& path, FilterMeta& meta);
+// ... and where the bits are: payload_at[i] = the file offset of row 0 of IBF i (shapes[i].bin_size rows of bin_words words follow)
+void read_hibf_meta(const std::string& path, FilterMeta& meta, std::vector<uint64_t>& payload_at);
 
 // `ganon-classify --inspect-filter`: parse the file's metadata only (no device, no bits), print every header field with its
 // offset and every redundancy check (technical_bins == 64*bin_words, hash_shift == countl_zero(bin_size), the bit_vector

@@ -512,6 +512,34 @@ int gn_filter_probe_path(gn_filter* f, const uint64_t* hashes, const uint64_t* s
 int gn_filter_probe_paths_shared(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths,
                                  uint32_t depth, uint64_t* found);
 
+/* `ganon-build --hibf --verify-index --verify-memory / --verify-devices`: the two probes on a storage filter whose IBFs are pieces of
+ * rows of the tree's IBFs (gn_filter_create_hibf_storage, rows written with gn_filter_write_rows at row - row_begin).  total_rows and
+ * row_begin mean what they mean in gn_filter_emplace_path_window; the rows of a hash are those of the WHOLE IBF and a row outside
+ * the piece counts as "all bits set".  The answers are carried in host bitmaps the caller owns, all in/out and only ever ANDed into:
+ * bit q % 64 of word q / 64 stands for hash (probe) q.  An entry with planes == NULL is taken as a whole piece: a hash that is not
+ * contained in it is cleared from `alive`.  An entry with planes is a slab of a cut IBF: plane b (n_bins planes of the bitmap's
+ * length, behind each other) keeps "every row of the hash seen so far has the bit of bin first_bin + b"; the caller closes the entry
+ * when the IBF's last slab is through -- hit = OR of the planes, alive &= hit (host/hibf_verify_parts.hpp).  Planes start as all ones.
+ * gn_filter_probe_path_window: set s = sets[s][0 .. set_sizes[s]) by pointer, as for the windowed insert.
+ *   alive[s]               ceil(set_sizes[s] / 64) words; the caller starts it with one bit per hash and the padding bits zero
+ *   planes                 NULL, or n_sets * depth pointers: planes[s * depth + d] NULL or n_bins * ceil(set_sizes[s] / 64) words
+ *   lost_at[s * depth + d] ADDED to: the hashes of set s not contained in entry d, for entries without planes only
+ *   chunk_hashes           hashes of a staging chunk (0: 1 Mi), rounded up to a multiple of 512: every wave's 512 hashes start at a
+ *                          multiple of 512 of their set and own whole words of its bitmaps
+ * gn_filter_probe_paths_shared_window: the same n probes against each of n_paths paths.
+ *   alive                  n_paths * ceil(n / 64) words, path p's bitmap at p * ceil(n / 64)
+ *   planes                 NULL, or n_paths * depth pointers: planes[p * depth + d] NULL or n_bins * ceil(n / 64) words
+ *   A probe that is cleared from `alive` already is not looked at again, so the planes of a path say nothing about it.
+ * Both check everything before anything is launched and a refused call changes no buffer: GN_EINVAL for a null argument (planes
+ * excepted), a filter that is not an HIBF, an IBF or a bin out of range, row_begin + rows > total_rows, IBFs of unequal hash
+ * functions; GN_ERANGE for total_rows >= 2^32.  n_sets == 0, n_paths == 0, n == 0 and empty sets are legal and change nothing. */
+int gn_filter_probe_path_window(gn_filter* f, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, const gn_path_entry* paths,
+                                uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t* const* alive,
+                                uint64_t* const* planes, uint64_t* lost_at, uint64_t chunk_hashes);
+int gn_filter_probe_paths_shared_window(gn_filter* f, const uint64_t* probes, uint64_t n, const gn_path_entry* paths, uint32_t n_paths,
+                                        uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t* alive,
+                                        uint64_t* const* planes);
+
 /* `ganon-build --hibf --update`: what an index on the device says about itself, and its move into a wider one (no counterpart in the
  * reference: `ganon update` rebuilds the filter, update() in src/ganon/build_update.py).
  * gn_filter_bin_popcounts: counts[b], for every b below the bins of IBF `ibf_idx` (host memory, that many entries), = the number of
