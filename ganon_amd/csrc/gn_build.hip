@@ -14,6 +14,7 @@
 
 #include "gn_build_row.h" // gn_build_row: seqan3::interleaved_bloom_filter's hash_and_fit
 #include "gn_emplace_window.h"
+#include "gn_packed_decode.h"
 #include "gn_packed_set.h"
 #include "gn_scan.h"
 
@@ -495,24 +496,8 @@ __global__ __launch_bounds__(256) void gn_emplace_packed_window_kernel(uint64_t*
     const uint32_t     lane = threadIdx.x & 63u;
     const GnPackedItem it   = items[item];
     const GnRunDev     run  = runs[it.run];
-    const uint64_t*    words = stage + it.stage_at;
-    uint64_t           d[GN_WIN_PER_LANE], sum = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
-    {
-        const uint32_t e = lane * GN_WIN_PER_LANE + j;
-        d[j]             = e + 1 < it.cnt ? gn_packed_delta(words, e, it.width) : 0; // (a delta past the block's last is not read)
-        sum += d[j];
-    }
-    uint64_t incl = sum;
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1)
-    {
-        const uint64_t below = __shfl_up(incl, o);
-        if (lane >= o)
-            incl += below;
-    }
-    uint64_t       v    = it.first + (incl - sum);
+    uint64_t           v[GN_WIN_PER_LANE];
+    gn_packed_lane_hashes(stage + it.stage_at, it.cnt, it.width, it.first, lane, v);
     const uint64_t b0   = it.begin / run.per_bin; // (wave-uniform: once per item)
     const uint64_t r0   = it.begin - b0 * run.per_bin;
     const uint32_t bin0 = run.first_bin + (uint32_t)b0;
@@ -520,20 +505,183 @@ __global__ __launch_bounds__(256) void gn_emplace_packed_window_kernel(uint64_t*
     for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
     {
         const uint32_t q = lane * GN_WIN_PER_LANE + j;
-        if (q < it.cnt)
+        if (q >= it.cnt)
+            continue;
+        const uint32_t bin  = gn_window_item_bin(bin0, r0, q, run.per_bin);
+        GnGlobalWord*  word = (GnGlobalWord*)rows + (bin >> 6);
+        const uint64_t bit  = 1ULL << (bin & 63);
+        for (uint32_t i = 0; i < h; ++i)
         {
-            const uint32_t bin  = gn_window_item_bin(bin0, r0, q, run.per_bin);
-            GnGlobalWord*  word = (GnGlobalWord*)rows + (bin >> 6);
-            const uint64_t bit  = 1ULL << (bin & 63);
-            for (uint32_t i = 0; i < h; ++i)
-            {
-                uint32_t local;
-                if (gn_window_local(gn_build_row(v, i, shift, S_total), row_begin, n_rows, &local))
-                    (void)__hip_atomic_fetch_or(word + (uint64_t)local * W, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            uint32_t local;
+            if (gn_window_local(gn_build_row(v[j], i, shift, S_total), row_begin, n_rows, &local))
+                (void)__hip_atomic_fetch_or(word + (uint64_t)local * W, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        v += d[j];
     }
+}
+
+// ---- gn_packed_decode_kernel: packed blocks written out as hashes --------------------------------------------------------------------
+// One wave per block: the hashes of item i go to out[items[i].begin ..), its payload lies at stage + items[i].stage_at.  What the sort of
+// gn_packed_union and the fill kernel of gn_sketches_create_packed read: the link carries packed bytes, the hashes are born in HBM.
+__global__ __launch_bounds__(256) void gn_packed_decode_kernel(const uint64_t* __restrict__ stage, const GnPackedItem* __restrict__ items, uint32_t n_items,
+                                                               uint64_t* __restrict__ out)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t     lane = threadIdx.x & 63u;
+    const GnPackedItem it   = items[item];
+    uint64_t           v[GN_WIN_PER_LANE];
+    gn_packed_lane_hashes(stage + it.stage_at, it.cnt, it.width, it.first, lane, v);
+#pragma unroll
+    for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+    {
+        const uint32_t q = lane * GN_WIN_PER_LANE + j;
+        if (q < it.cnt)
+            out[it.begin + q] = v[j];
+    }
+}
+
+hipError_t gn_packed_decode_launch(hipStream_t st, const uint64_t* stage, const GnPackedItem* items, uint32_t n_items, uint64_t* out)
+{
+    if (n_items == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(gn_packed_decode_kernel, dim3((n_items + 3) / 4), dim3(256), 0, st, stage, items, n_items, out);
+    return hipGetLastError();
+}
+
+// one block of a packed run as every call that takes such runs checks it
+bool gn_packed_block_ok(const GnPackedBlock& b, const uint64_t* payload)
+{
+    return b.cnt != 0 && b.cnt <= GN_WIN_ITEM && b.width <= 64 && (gn_packed_words(b.cnt, b.width) == 0 || payload);
+}
+
+// ---- gn_packed_union: the ascending union of packed runs, packed ---------------------------------------------------------------------
+// Blocks and payload go up (a run's words from where they lie: neighbouring blocks' words are copied together), gn_packed_decode_kernel
+// writes the hashes into the sort's input, radix sort and unique as gn_hashes_union, then the packer of gn_stream_distinct_hashes_packed
+// on the unique hashes; blocks and payload come down.  The payload on the device takes the sort's second buffer both times: a packed set
+// has fewer words than hashes, and the sort that overwrites it runs behind the decode.
+extern "C" int gn_packed_union(int device, const gn_packed_block* const* blocks_abi, const uint64_t* n_blocks, const uint64_t* const* payload, uint32_t n_runs,
+                               gn_packed_block* out_blocks, uint64_t cap_blocks, uint64_t* out_payload, uint64_t cap_words, uint64_t* n_union,
+                               uint64_t* n_out_blocks, uint64_t* n_out_words)
+{
+    static const char* const    who    = "gn_packed_union";
+    const GnPackedBlock* const* blocks = reinterpret_cast<const GnPackedBlock* const*>(blocks_abi);
+    if (!n_union || !n_out_blocks || !n_out_words || (n_runs && (!blocks || !n_blocks || !payload)))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    *n_union = *n_out_blocks = *n_out_words = 0;
+    uint64_t total = 0, in_blocks = 0, in_words = 0;
+    for (uint32_t r = 0; r < n_runs; ++r)
+    {
+        if (n_blocks[r] && !blocks[r])
+            return gn_fail(GN_EINVAL, "%s: run %u is null", who, r);
+        for (uint64_t i = 0; i < n_blocks[r]; ++i)
+        {
+            const GnPackedBlock& b = blocks[r][i];
+            if (!gn_packed_block_ok(b, payload[r]))
+                return gn_fail(GN_EINVAL, "%s: run %u: block %llu of %u hashes at %u bits", who, r, (unsigned long long)i, b.cnt, b.width);
+            total += b.cnt;
+            in_words += gn_packed_words(b.cnt, b.width);
+        }
+        in_blocks += n_blocks[r];
+    }
+    if (total == 0)
+        return GN_OK;
+    if (total > 0x7FFFFFFFull) // (the sort / unique calls take their item count as an int)
+        return gn_fail(GN_ERANGE, "%s: %llu hashes in one call, at most 2^31 - 1", who, (unsigned long long)total);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+        return gn_fail(GN_ENODEV, "%s: no HIP device %d", who, device);
+    GN_HIP(hipSetDevice(device));
+    std::vector<GnPackedItem> items; // (before the buffers it is copied into: they are freed, which waits for the device, first)
+    items.reserve(in_blocks);
+    GnDev<uint64_t>           d_a, d_b;
+    GnDev<unsigned long long> d_n;
+    GnDev<uint8_t>            d_tmp;
+    GnDev<GnPackedItem>       d_items;
+    GN_HIP(d_a.alloc(total));
+    GN_HIP(d_b.alloc(total));
+    GN_HIP(d_n.alloc(2));
+    GN_HIP(d_items.alloc(in_blocks));
+    size_t ta = 0, tb = 0, tc = 0;
+    GN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, ta, d_a.get(), d_b.get(), (int)total, 0, 64, nullptr));
+    GN_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_b.get(), d_a.get(), d_n.get(), (int)total, nullptr));
+    GN_HIP(hipcub::DeviceReduce::Max(nullptr, tc, d_a.get(), d_n.get() + 1, (int)total, nullptr));
+    const size_t tmp_bytes = std::max(ta, std::max(tb, tc));
+    GN_HIP(d_tmp.alloc(tmp_bytes));
+    // the payload: word `stage_at` of d_b is where a block's words go; blocks whose words follow each other in the run go up in one copy
+    uint64_t at = 0, words = 0;
+    for (uint32_t r = 0; r < n_runs; ++r)
+    {
+        uint64_t from = 0, len = 0; // the words of the run gathered for the next copy
+        auto     flush = [&]() -> hipError_t {
+            const hipError_t e = len ? hipMemcpy(d_b + (words - len), payload[r] + from, len * 8, hipMemcpyHostToDevice) : hipSuccess;
+            len                = 0;
+            return e;
+        };
+        for (uint64_t i = 0; i < n_blocks[r]; ++i)
+        {
+            const GnPackedBlock& b = blocks[r][i];
+            const uint32_t       w = gn_packed_words(b.cnt, b.width);
+            items.push_back(GnPackedItem{ r, b.cnt, b.width, 0, b.first, at, words, i });
+            at += b.cnt;
+            if (w == 0)
+                continue;
+            if (len && b.word_at != from + len)
+                GN_HIP(flush());
+            if (len == 0)
+                from = b.word_at;
+            len += w, words += w;
+        }
+        GN_HIP(flush());
+    }
+    GN_HIP(hipMemcpy(d_items, items.data(), items.size() * sizeof(GnPackedItem), hipMemcpyHostToDevice));
+    GN_HIP(gn_packed_decode_launch(nullptr, d_b, d_items, (uint32_t)items.size(), d_a));
+    size_t t = tmp_bytes;
+    GN_HIP(hipcub::DeviceReduce::Max(d_tmp.get(), t, d_a.get(), d_n.get() + 1, (int)total, nullptr));
+    unsigned long long top = 0, nu = 0;
+    GN_HIP(hipMemcpy(&top, d_n + 1, sizeof(top), hipMemcpyDeviceToHost));
+    int end_bit = 1;
+    while (end_bit < 64 && (top >> end_bit))
+        ++end_bit;
+    t = tmp_bytes;
+    GN_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.get(), t, d_a.get(), d_b.get(), (int)total, 0, end_bit, nullptr));
+    t = tmp_bytes;
+    GN_HIP(hipcub::DeviceSelect::Unique(d_tmp.get(), t, d_b.get(), d_a.get(), d_n.get(), (int)total, nullptr));
+    GN_HIP(hipMemcpy(&nu, d_n, sizeof(nu), hipMemcpyDeviceToHost));
+    // the union lies in d_a: packed as gn_stream_distinct_hashes_packed packs a file's set
+    const uint64_t       nb = gn_packed_max_blocks(nu);
+    GnDev<GnPackedBlock> d_blocks;
+    GnDev<uint32_t>      d_words;
+    GnDev<uint64_t>      d_off;
+    GN_HIP(d_blocks.alloc(nb));
+    GN_HIP(d_words.alloc(nb + 1));
+    GN_HIP(d_off.alloc(nb + 1));
+    size_t ts = 0;
+    GN_HIP(gn_scan_counts(nullptr, ts, d_words.get(), d_off.get(), (int)(nb + 1), nullptr));
+    if (ts > tmp_bytes)
+        GN_HIP(d_tmp.alloc(ts));
+    const dim3 grid((unsigned)((nb + 3) / 4));
+    hipLaunchKernelGGL(gn_pack_width_kernel, grid, dim3(256), 0, nullptr, (const uint64_t*)d_a, (uint64_t)nu, d_blocks.get(), d_words.get(), (uint32_t)nb);
+    GN_HIP(hipGetLastError());
+    GN_HIP(gn_scan_counts(d_tmp.get(), ts, d_words.get(), d_off.get(), (int)(nb + 1), nullptr));
+    hipLaunchKernelGGL(gn_pack_payload_kernel, grid, dim3(256), 0, nullptr, (const uint64_t*)d_a, (uint64_t)nu, d_blocks.get(), (const uint64_t*)d_off, d_b.get(),
+                       (uint32_t)nb);
+    GN_HIP(hipGetLastError());
+    uint64_t nw = 0;
+    GN_HIP(hipMemcpy(&nw, d_off + nb, 8, hipMemcpyDeviceToHost));
+    *n_union      = nu;
+    *n_out_blocks = nb;
+    *n_out_words  = nw;
+    if (!out_blocks && !out_payload)
+        return GN_OK;
+    if (!out_blocks || (!out_payload && nw))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    if (cap_blocks < nb || cap_words < nw)
+        return gn_fail(GN_EOVERFLOW, "%s: packed buffers too small: need %llu blocks and %llu words", who, (unsigned long long)nb, (unsigned long long)nw);
+    GN_HIP(hipMemcpy(out_blocks, d_blocks, nb * sizeof(GnPackedBlock), hipMemcpyDeviceToHost));
+    if (nw)
+        GN_HIP(hipMemcpy(out_payload, d_b, nw * 8, hipMemcpyDeviceToHost));
+    return GN_OK;
 }
 
 namespace

@@ -7,6 +7,7 @@
 //                            merged bin in each IBF above).  Inserting every member's set into a merged bin sets the bits the
 //                            union of the sets would: the unions are never materialised.
 //   gn_filter_emplace_path_window  the same into a filter whose IBFs are pieces of rows of the tree's IBFs: a tree built in parts
+//   gn_filter_emplace_path_packed_window  its twin for packed sets (gn_packed_set.h): payload words go up, a wave decodes a block in registers
 //   gn_filter_bin_popcounts  set bits per technical bin of an IBF: how full each bin of an index is (towards `--update`)
 //   gn_filter_copy_ibf       an IBF into one with more bins, device to device
 //   gn_filter_copy_ibf_spans the same with runs of bins left out or moved (`--update --remove`)
@@ -17,6 +18,7 @@
 #include "gn_bin_spans.h"
 #include "gn_fold_table.h"
 #include "gn_build_row.h"
+#include "gn_packed_decode.h"
 #include "gn_path_window.h"
 #include "gn_scan.h"
 #include <hipcub/hipcub.hpp>
@@ -426,6 +428,172 @@ extern "C" int gn_filter_emplace_path_window(gn_filter* f, const uint64_t* const
     }
     GN_HIP(g.d_paths.upload(dev.data(), dev.size()));
     const int rc = gn_path_window_rounds(g, sets, set_sizes, n_sets, depth, h, chunk, cap_items);
+    // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
+    const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
+    if (rc != GN_OK)
+        return rc;
+    GN_HIP(e0);
+    GN_HIP(e1);
+    return GN_OK;
+}
+
+// ---- gn_filter_emplace_path_packed_window: the same insert from packed sets ----------------------------------------------------------
+// The twin of gn_filter_emplace_path_window for sets packed as gn_packed_set.h says (`ganon-build --hibf --hibf-hash-sets packed|spilled`):
+// the same filter, paths, pieces and bits.  One wave per block.  Lane L unpacks the block's hashes 8L .. 8L + 7 in registers
+// (gn_packed_lane_hashes: the decode of the flat packed insert) -- they are never written to memory -- and from there it is the depth loop
+// of gn_emplace_path_window_kernel with q = 8L + j and the item's `begin`, the index of the block's first hash in the SET.  Item and path
+// entries are read with scalar loads; behind the decode the wave only issues no-return atomic ORs.
+__global__ __launch_bounds__(256) void gn_emplace_path_packed_window_kernel(const uint64_t* __restrict__ stage, const GnPackedItem* __restrict__ items,
+                                                                            uint32_t n_items, const GnPathWinDev* __restrict__ paths, uint32_t depth, uint32_t h)
+{
+    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (item >= n_items)
+        return;
+    const uint32_t     lane = threadIdx.x & 63u;
+    const GnPackedItem it   = items[item];
+    uint64_t           v[GN_WIN_PER_LANE];
+    gn_packed_lane_hashes(stage + it.stage_at, it.cnt, it.width, it.first, lane, v);
+    const GnPathWinDev* __restrict__ p = paths + (uint64_t)it.run * depth;
+    for (uint32_t d = 0; d < depth; ++d)
+    {
+        const GnPathWinDev e = p[d];
+        if (e.n_bins == 0)
+            break;
+        uint32_t bin0;
+        uint64_t r0;
+        gn_path_window_start(e.first_bin, e.n_bins, e.per_bin, it.begin, &bin0, &r0); // (wave-uniform: once per item and entry)
+#pragma unroll
+        for (uint32_t j = 0; j < GN_WIN_PER_LANE; ++j)
+        {
+            const uint32_t q = lane * GN_WIN_PER_LANE + j;
+            if (q >= it.cnt)
+                continue;
+            const uint32_t bin  = gn_path_window_bin(bin0, r0, q, e.n_bins, e.per_bin);
+            // (a pointer read from memory is generic to the compiler: say that it is global, as gn_emplace_path_kernel does)
+            GnGlobalWord*  word = (GnGlobalWord*)e.rows + (bin >> 6);
+            const uint64_t bit  = 1ULL << (bin & 63);
+            for (uint32_t i = 0; i < h; ++i)
+            {
+                uint32_t local;
+                if (gn_window_local(gn_build_row(v[j], i, e.shift, e.S_total), e.row_begin, e.n_rows, &local))
+                    (void)__hip_atomic_fetch_or(word + (uint64_t)local * e.Ws, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+namespace
+{
+struct GnPathPackedStage // everything a call holds; freed when the call returns
+{
+    GnStreamPair           streams;
+    GnPinned<uint64_t>     h_stage[2];
+    GnPinned<GnPackedItem> h_items[2];
+    GnDev<uint64_t>        d_stage[2];
+    GnDev<GnPackedItem>    d_items[2];
+    GnDev<GnPathWinDev>    d_paths;
+};
+} // namespace
+
+// the rounds of gn_packed_window_rounds (gn_build.hip) with the sets as runs: what is gathered into the page-locked chunk is the payload
+// of the chunk's blocks; chunk c goes through buffer and stream c & 1, a buffer is written again only after its stream has been waited for
+static int gn_path_packed_window_rounds(GnPathPackedStage& g, const GnPackedBlock* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                        uint32_t n_sets, uint32_t depth, uint32_t h, uint64_t chunk, uint64_t cap_items)
+{
+    std::vector<GnPackedItem> items;
+    GnPackedCursor            cur;
+    for (uint32_t c = 0;; ++c)
+    {
+        const uint32_t b = c & 1u;
+        GN_HIP(hipStreamSynchronize(g.streams.st[b]));
+        uint64_t       words   = 0;
+        const uint32_t n_items = (uint32_t)gn_packed_next_chunk(blocks, n_blocks, n_sets, cur, chunk, cap_items, items, &words);
+        if (n_items == 0)
+            return GN_OK;
+        for (const GnPackedItem& it : items)
+            if (const uint32_t w = gn_packed_words(it.cnt, it.width))
+                memcpy(g.h_stage[b] + it.stage_at, payload[it.run] + blocks[it.run][it.block].word_at, (size_t)w * 8);
+        memcpy(g.h_items[b].get(), items.data(), items.size() * sizeof(GnPackedItem));
+        if (words)
+            GN_HIP(hipMemcpyAsync(g.d_stage[b], g.h_stage[b], words * 8, hipMemcpyHostToDevice, g.streams.st[b]));
+        GN_HIP(hipMemcpyAsync(g.d_items[b], g.h_items[b], items.size() * sizeof(GnPackedItem), hipMemcpyHostToDevice, g.streams.st[b]));
+        hipLaunchKernelGGL(gn_emplace_path_packed_window_kernel, dim3((n_items + 3) / 4), dim3(256), 0, g.streams.st[b], (const uint64_t*)g.d_stage[b],
+                           (const GnPackedItem*)g.d_items[b], n_items, (const GnPathWinDev*)g.d_paths, depth, h);
+        GN_HIP(hipGetLastError());
+    }
+}
+
+extern "C" int gn_filter_emplace_path_packed_window(gn_filter* f, const gn_packed_block* const* blocks_abi, const uint64_t* n_blocks,
+                                                    const uint64_t* const* payload, uint32_t n_sets, const gn_path_entry* paths, uint32_t depth,
+                                                    const uint64_t* total_rows, const uint64_t* row_begin, uint64_t chunk_words)
+{
+    static const char* const    who    = "gn_filter_emplace_path_packed_window";
+    const GnPackedBlock* const* blocks = reinterpret_cast<const GnPackedBlock* const*>(blocks_abi);
+    if (!f || !f->is_hibf)
+        return gn_fail(GN_EINVAL, "%s needs an HIBF filter", who);
+    if (!total_rows || !row_begin)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    for (size_t j = 0; j < f->ibfs.size(); ++j)
+    {
+        if (total_rows[j] == 0 || total_rows[j] > 0xFFFFFFFFull)
+            return gn_fail(GN_ERANGE, "%s: ibf %zu: an IBF of %llu rows, 1 .. 2^32 - 1 are supported", who, j, (unsigned long long)total_rows[j]);
+        if (row_begin[j] > total_rows[j] || f->ibfs[j].S > total_rows[j] - row_begin[j])
+            return gn_fail(GN_EINVAL, "%s: ibf %zu: rows %llu .. %llu of an IBF of %llu rows", who, j, (unsigned long long)row_begin[j],
+                           (unsigned long long)(row_begin[j] + f->ibfs[j].S), (unsigned long long)total_rows[j]);
+    }
+    if (n_sets == 0)
+        return GN_OK;
+    if (!blocks || !n_blocks || !payload || !paths || depth == 0)
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    const uint32_t h = f->ibfs[0].h;
+    // every block is looked at and every bin a hash can reach is checked before anything is launched (the local row is below the piece's
+    // rows by the window test; a block's words are read only as far as cnt and width say)
+    std::vector<GnPathWinDev> dev((size_t)n_sets * depth, GnPathWinDev{ nullptr, 1, 1, 1, 0, 0, 0, 0, 0 });
+    uint64_t                  total = 0, words = 0;
+    for (uint32_t s = 0; s < n_sets; ++s)
+    {
+        if (n_blocks[s] && !blocks[s])
+            return gn_fail(GN_EINVAL, "%s: set %u is null", who, s);
+        uint64_t size = 0;
+        for (uint64_t i = 0; i < n_blocks[s]; ++i)
+        {
+            const GnPackedBlock& b = blocks[s][i];
+            if (!gn_packed_block_ok(b, payload[s]))
+                return gn_fail(GN_EINVAL, "%s: set %u: block %llu of %u hashes at %u bits", who, s, (unsigned long long)i, b.cnt, b.width);
+            size += b.cnt;
+            words += gn_packed_words(b.cnt, b.width);
+        }
+        total += n_blocks[s];
+        for (uint32_t d = 0; d < depth && paths[(size_t)s * depth + d].n_bins != 0; ++d)
+        {
+            GnPathDev            o;
+            const gn_path_entry& e = paths[(size_t)s * depth + d];
+            if (const int rc = gn_path_resolve(who, f, e, s, d, true, size, o))
+                return rc;
+            const GnIbfHost& ib = f->ibfs[e.ibf];
+            if (ib.h != h)
+                return gn_fail(GN_EINVAL, "%s: ibf %u has %u hash functions, ibf 0 has %u", who, e.ibf, ib.h, h);
+            dev[(size_t)s * depth + d] = GnPathWinDev{ o.rows, total_rows[e.ibf], o.per_bin, o.Ws, (uint32_t)__builtin_clzll(total_rows[e.ibf]),
+                                                       o.first_bin, o.n_bins, (uint32_t)row_begin[e.ibf], (uint32_t)ib.S };
+        }
+    }
+    if (total == 0)
+        return GN_OK;
+    GN_HIP(hipSetDevice(f->device));
+    // (a chunk holds any block: a cap below a block's most words is raised to it)
+    const uint64_t    chunk     = std::max<uint64_t>(std::min<uint64_t>(chunk_words ? chunk_words : GN_PACKED_CHUNK, words), GN_PACKED_MAX_WORDS);
+    const uint64_t    cap_items = std::min<uint64_t>(chunk / 16 + 16, total); // (a chunk of narrow blocks closes at this many items)
+    GnPathPackedStage g;
+    for (int b = 0; b < 2; ++b)
+    {
+        GN_HIP(hipStreamCreateWithFlags(&g.streams.st[b], hipStreamNonBlocking));
+        GN_HIP(g.h_stage[b].alloc(chunk));
+        GN_HIP(g.h_items[b].alloc(cap_items));
+        GN_HIP(g.d_stage[b].alloc(chunk));
+        GN_HIP(g.d_items[b].alloc(cap_items));
+    }
+    GN_HIP(g.d_paths.upload(dev.data(), dev.size()));
+    const int rc = gn_path_packed_window_rounds(g, blocks, n_blocks, payload, n_sets, depth, h, chunk, cap_items);
     // (also after a failure: nothing of `g` is freed under a copy or a kernel that still uses it)
     const hipError_t e0 = hipStreamSynchronize(g.streams.st[0]), e1 = hipStreamSynchronize(g.streams.st[1]);
     if (rc != GN_OK)

@@ -12,6 +12,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #define GN_SKETCH_CHUNK 8192u // hashes of one set a block folds into its LDS sketch
@@ -257,6 +258,62 @@ extern "C" int gn_sketches_free(gn_sketches* s)
     return GN_OK;
 }
 
+namespace
+{
+struct GnSketchesGuard // a handle that is not handed out yet
+{
+    gn_sketches* p;
+    ~GnSketchesGuard() { delete p; }
+};
+} // namespace
+
+// the handle of gn_sketches_create and gn_sketches_create_packed before a hash is read: n_sets sketches of zeros and the estimate's tables
+static int gn_sketches_open(const char* who, int device, uint32_t n_sets, GnSketchesGuard& g)
+{
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+        return gn_fail(GN_ENODEV, "%s: no HIP device %d", who, device);
+    GN_HIP(hipSetDevice(device));
+    g.p            = new gn_sketches;
+    gn_sketches* s = g.p;
+    s->device      = device;
+    s->n           = n_sets;
+    GN_HIP(s->d_regs.alloc((size_t)n_sets * GN_SKETCH_M));
+    GN_HIP(hipMemset(s->d_regs, 0, s->d_regs.cap())); // an empty set is all zeros
+    const double        m     = (double)GN_SKETCH_M;
+    const double        alpha = 0.7213 / (1.0 + 1.079 / m);
+    std::vector<double> small(GN_SKETCH_M + 1, 0.0);
+    for (uint32_t z = 1; z <= GN_SKETCH_M; ++z)
+        small[z] = m * log(m / (double)z);
+    s->num = alpha * 16777216.0 * 4503599627370496.0; // m^2 = 2^24, then 2^52: both products are exact
+    GN_HIP(s->d_small.upload(small.data(), small.size()));
+    return GN_OK;
+}
+
+// one round's items over the hashes in d_stage: the fill kernel, then the slots' scratch words folded into their sets' registers
+static int gn_sketch_round(gn_sketches* s, const uint64_t* d_stage, const std::vector<GnSketchItem>& items, const std::vector<uint32_t>& slot_seg,
+                           GnDev<GnSketchItem>& d_items, GnDev<uint32_t>& d_scratch, GnDev<uint32_t>& d_slot_seg, uint64_t max_slots)
+{
+    if (items.size() > d_items.cap() || slot_seg.size() > max_slots) // (cannot happen, see the bounds at the allocations)
+        GN_HIP(hipErrorInvalidValue);
+    GN_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GnSketchItem), hipMemcpyHostToDevice, nullptr));
+    if (!slot_seg.empty())
+    {
+        GN_HIP(hipMemsetAsync(d_scratch, 0, slot_seg.size() * GN_SKETCH_M * sizeof(uint32_t), nullptr));
+        GN_HIP(hipMemcpyAsync(d_slot_seg, slot_seg.data(), slot_seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+    }
+    hipLaunchKernelGGL(gn_sketch_fill_kernel, dim3((uint32_t)items.size()), dim3(256), 0, nullptr, d_stage, d_items, d_scratch, s->d_regs);
+    GN_HIP(hipGetLastError());
+    if (!slot_seg.empty())
+    {
+        const uint32_t n_slots = (uint32_t)slot_seg.size();
+        hipLaunchKernelGGL(gn_sketch_pack_kernel, dim3(n_slots * (GN_SKETCH_M / 4 / 256)), dim3(256), 0, nullptr, d_scratch, d_slot_seg, n_slots, s->d_regs);
+        GN_HIP(hipGetLastError());
+    }
+    GN_HIP(hipStreamSynchronize(nullptr)); // (the host's buffers, the staging buffer and the item lists are reused)
+    return GN_OK;
+}
+
 extern "C" int gn_sketches_create(int device, const uint64_t* const* sets, const uint64_t* sizes, uint32_t n_sets, gn_sketches** out)
 {
     if (!out || (n_sets && (!sets || !sizes)))
@@ -265,29 +322,10 @@ extern "C" int gn_sketches_create(int device, const uint64_t* const* sets, const
     for (uint32_t i = 0; i < n_sets; ++i)
         if (sizes[i] && !sets[i])
             return gn_fail(GN_EINVAL, "gn_sketches_create: set %u is null", i);
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-        return gn_fail(GN_ENODEV, "gn_sketches_create: no HIP device %d", device);
-    GN_HIP(hipSetDevice(device));
-    struct Guard
-    {
-        gn_sketches* p;
-        ~Guard() { delete p; }
-    } g{ new gn_sketches };
+    GnSketchesGuard g{ nullptr };
+    if (const int rc = gn_sketches_open("gn_sketches_create", device, n_sets, g))
+        return rc;
     gn_sketches* s = g.p;
-    s->device      = device;
-    s->n           = n_sets;
-    GN_HIP(s->d_regs.alloc((size_t)n_sets * GN_SKETCH_M));
-    GN_HIP(hipMemset(s->d_regs, 0, s->d_regs.cap())); // an empty set is all zeros
-    {
-        const double          m     = (double)GN_SKETCH_M;
-        const double          alpha = 0.7213 / (1.0 + 1.079 / m);
-        std::vector<double> small(GN_SKETCH_M + 1, 0.0);
-        for (uint32_t z = 1; z <= GN_SKETCH_M; ++z)
-            small[z] = m * log(m / (double)z);
-        s->num = alpha * 16777216.0 * 4503599627370496.0; // m^2 = 2^24, then 2^52: both products are exact
-        GN_HIP(s->d_small.upload(small.data(), small.size()));
-    }
 
     // rounds of at most kStep hashes: sets below kDirect are gathered in pinned memory and go up in one copy, larger pieces go up
     // from where they lie
@@ -351,24 +389,114 @@ extern "C" int gn_sketches_create(int device, const uint64_t* const* sets, const
             GN_HIP(flush_pool(at));
             if (items.empty())
                 continue;
-            if (items.size() > d_items.cap() || slot_seg.size() > max_slots) // (cannot happen, see the bounds above)
-                GN_HIP(hipErrorInvalidValue);
-            GN_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(GnSketchItem), hipMemcpyHostToDevice, nullptr));
-            if (!slot_seg.empty())
+            if (const int rc = gn_sketch_round(s, d_stage, items, slot_seg, d_items, d_scratch, d_slot_seg, max_slots))
+                return rc;
+        }
+    }
+    GN_HIP(hipDeviceSynchronize());
+    *out = s;
+    g.p  = nullptr;
+    return GN_OK;
+}
+
+// ---- gn_sketches_create_packed: the same sketches from packed runs --------------------------------------------------------------------
+// A round stages the payload words and the tables of whole blocks -- at most kStep hashes and kBlocks blocks of them -- instead of
+// hashes; gn_packed_decode_kernel (gn_build.hip) writes the round's hashes, run behind run, into the staging buffer gn_sketch_fill_kernel
+// reads.  One more pass over HBM than the raw call makes, for a link that carries packed bytes; the sketch arithmetic stays in one place.
+// A register is a maximum over the set's hashes: how a set is cut into rounds and items does not show in it.
+extern "C" int gn_sketches_create_packed(int device, const gn_packed_block* const* blocks_abi, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                         uint32_t n_runs, gn_sketches** out)
+{
+    static const char* const    who    = "gn_sketches_create_packed";
+    const GnPackedBlock* const* blocks = reinterpret_cast<const GnPackedBlock* const*>(blocks_abi);
+    if (!out || (n_runs && (!blocks || !n_blocks || !payload)))
+        return gn_fail(GN_EINVAL, "%s: null argument", who);
+    *out           = nullptr;
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < n_runs; ++r)
+    {
+        if (n_blocks[r] && !blocks[r])
+            return gn_fail(GN_EINVAL, "%s: run %u is null", who, r);
+        for (uint64_t i = 0; i < n_blocks[r]; ++i)
+        {
+            const GnPackedBlock& b = blocks[r][i];
+            if (!gn_packed_block_ok(b, payload[r]))
+                return gn_fail(GN_EINVAL, "%s: run %u: block %llu of %u hashes at %u bits", who, r, (unsigned long long)i, b.cnt, b.width);
+            total += b.cnt;
+        }
+    }
+    GnSketchesGuard g{ nullptr };
+    if (const int rc = gn_sketches_open(who, device, n_runs, g))
+        return rc;
+    gn_sketches* s = g.p;
+    if (total)
+    {
+        constexpr uint64_t kStep = 8ull << 20;
+        const uint64_t     step  = std::max<uint64_t>(total < kStep ? total : kStep, GN_WIN_ITEM); // (a round holds any block)
+        const uint64_t     kBlocks   = step / 64 + 16; // (a round of short blocks closes at this many of them)
+        const uint64_t     max_slots = step / GN_SKETCH_CHUNK + 2; // runs of more than one chunk that lie in a round, and one cut at each end
+        const uint64_t     max_items = step / GN_SKETCH_CHUNK + kBlocks + 2; // full chunks, and a short one per run (a run has a block)
+        std::vector<GnSketchItem> items; // (before the buffers they are copied into: those are freed, which waits for the device, first)
+        std::vector<uint32_t>     slot_seg;
+        GnDev<uint64_t>           d_stage, d_words;
+        GnDev<GnPackedItem>       d_blocks;
+        GnDev<GnSketchItem>       d_items;
+        GnDev<uint32_t>           d_scratch, d_slot_seg;
+        GnPinned<uint64_t>        h_words;
+        GnPinned<GnPackedItem>    h_blocks;
+        GN_HIP(d_stage.alloc(step));
+        GN_HIP(d_words.alloc(step)); // (a block has fewer words than hashes)
+        GN_HIP(d_blocks.alloc(kBlocks));
+        GN_HIP(d_items.alloc(max_items));
+        GN_HIP(d_scratch.alloc(max_slots * GN_SKETCH_M));
+        GN_HIP(d_slot_seg.alloc(max_slots));
+        GN_HIP(h_words.alloc(step));
+        GN_HIP(h_blocks.alloc(kBlocks));
+        uint32_t run = 0;
+        uint64_t blk = 0; // blocks of run `run` already sketched
+        while (run < n_runs)
+        {
+            items.clear(), slot_seg.clear();
+            uint64_t at = 0, words = 0, nb = 0; // hashes, payload words and blocks of the round
+            while (run < n_runs && nb < kBlocks)
             {
-                GN_HIP(hipMemsetAsync(d_scratch, 0, slot_seg.size() * GN_SKETCH_M * sizeof(uint32_t), nullptr));
-                GN_HIP(hipMemcpyAsync(d_slot_seg, slot_seg.data(), slot_seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+                if (blk == n_blocks[run])
+                {
+                    ++run, blk = 0;
+                    continue;
+                }
+                if (blocks[run][blk].cnt > step - at)
+                    break;
+                const uint64_t from = at, first_blk = blk; // the run's hashes of this round lie behind each other from `from` on
+                for (; blk < n_blocks[run] && nb < kBlocks && blocks[run][blk].cnt <= step - at; ++blk, ++nb)
+                {
+                    const GnPackedBlock& b = blocks[run][blk];
+                    const uint32_t       w = gn_packed_words(b.cnt, b.width);
+                    if (w)
+                        memcpy(h_words + words, payload[run] + b.word_at, (size_t)w * 8);
+                    h_blocks[nb] = GnPackedItem{ run, b.cnt, b.width, 0, b.first, at, words, blk };
+                    at += b.cnt, words += w;
+                }
+                const uint64_t c    = at - from;
+                uint32_t       slot = ~0u;
+                if (c > GN_SKETCH_CHUNK || first_blk != 0 || blk != n_blocks[run]) // more than one item, or a run the round's end cuts
+                {
+                    slot = (uint32_t)slot_seg.size();
+                    slot_seg.push_back(run);
+                }
+                for (uint64_t a = 0; a < c; a += GN_SKETCH_CHUNK)
+                    items.push_back(GnSketchItem{ run, (uint32_t)(c - a < GN_SKETCH_CHUNK ? c - a : GN_SKETCH_CHUNK), slot, 0, from + a });
+                if (blk != n_blocks[run]) // (the round is full)
+                    break;
             }
-            hipLaunchKernelGGL(gn_sketch_fill_kernel, dim3((uint32_t)items.size()), dim3(256), 0, nullptr, d_stage, d_items, d_scratch, s->d_regs);
-            GN_HIP(hipGetLastError());
-            if (!slot_seg.empty())
-            {
-                const uint32_t n_slots = (uint32_t)slot_seg.size();
-                hipLaunchKernelGGL(gn_sketch_pack_kernel, dim3(n_slots * (GN_SKETCH_M / 4 / 256)), dim3(256), 0, nullptr, d_scratch, d_slot_seg, n_slots,
-                                   s->d_regs);
-                GN_HIP(hipGetLastError());
-            }
-            GN_HIP(hipStreamSynchronize(nullptr)); // (the pool, the staging buffer and the item lists are reused)
+            if (items.empty())
+                continue;
+            if (words)
+                GN_HIP(hipMemcpyAsync(d_words, h_words, words * 8, hipMemcpyHostToDevice, nullptr));
+            GN_HIP(hipMemcpyAsync(d_blocks, h_blocks, nb * sizeof(GnPackedItem), hipMemcpyHostToDevice, nullptr));
+            GN_HIP(gn_packed_decode_launch(nullptr, d_words, d_blocks, (uint32_t)nb, d_stage));
+            if (const int rc = gn_sketch_round(s, d_stage, items, slot_seg, d_items, d_scratch, d_slot_seg, max_slots))
+                return rc;
         }
     }
     GN_HIP(hipDeviceSynchronize());

@@ -238,7 +238,13 @@ hipError_t gn_launch_emplace(uint64_t* rows, uint64_t S, uint32_t W, uint32_t sh
 // ---- host-side objects behind the opaque C handles --------------------------------------------
 int gn_fail(int code, const char* fmt, ...);
 
-#define GN_HIP(expr)                                                                                                   \
+// gn_build.hip, for every call that takes packed runs (gn_packed_set.h): is a block one the kernels may read (1 .. 512 hashes, at most 64
+// bits a delta, a payload where it has words); and gn_packed_decode_kernel on `st` -- the hashes of item i to out[items[i].begin ..), its
+// payload at stage + items[i].stage_at
+bool       gn_packed_block_ok(const GnPackedBlock& b, const uint64_t* payload);
+hipError_t gn_packed_decode_launch(hipStream_t st, const uint64_t* stage, const GnPackedItem* items, uint32_t n_items, uint64_t* out);
+
+#define GN_HIP(expr)                                                                                                  \
     do                                                                                                                 \
     {                                                                                                                  \
         hipError_t e__ = (expr);                                                                                       \

@@ -38,6 +38,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_sketches_create", "gn_sketches_free", "gn_sketches_download", "gn_sketches_union_table", "gn_sketches_pair_table",
                "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window",
                "gn_stream_distinct_hashes_packed", "gn_filter_emplace_packed_window",
+               "gn_packed_union", "gn_sketches_create_packed", "gn_filter_emplace_path_packed_window",
                "gn_filter_probe_path_window", "gn_filter_probe_paths_shared_window"]
 
 
@@ -172,6 +173,8 @@ def load_library():
     L.gn_filter_emplace_path.argtypes = [vp, vp, vp, u32, vp, u32]
     L.gn_filter_create_hibf_storage.argtypes = [i32, u32, C.POINTER(IbfDesc), C.POINTER(vp)]
     L.gn_filter_emplace_path_window.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, u64]
+    L.gn_filter_emplace_path_packed_window.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, vp, u64]
+    L.gn_packed_union.argtypes = [C.c_int, vp, vp, vp, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.gn_filter_probe_path.argtypes =[vp, vp, vp, u32, vp, u32, vp, vp, vp]
     L.gn_filter_probe_paths_shared.argtypes = [vp, vp, u64, vp, u32, u32, vp]
     L.gn_filter_probe_path_window.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, u64]
@@ -182,6 +185,7 @@ def load_library():
     L.gn_filter_fold_ibf.argtypes = [vp, u32, u32, u32, vp, u32, vp, u32]
     L.gn_filter_extend_path.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp]
     L.gn_sketches_create.argtypes = [C.c_int, vp, vp, u32, C.POINTER(vp)]
+    L.gn_sketches_create_packed.argtypes = [C.c_int, vp, vp, vp, u32, C.POINTER(vp)]
     L.gn_sketches_free.argtypes = [vp]
     L.gn_sketches_download.argtypes = [vp, u32, u32, vp]
     L.gn_sketches_union_table.argtypes = [vp, vp, u32, u32, u32, u32, vp]
@@ -521,6 +525,44 @@ def hashes_union(sets: Sequence[np.ndarray], device: int = 0, size_only: bool = 
     return out[: nu.value].copy()
 
 
+def _packed_runs(runs):
+    """runs[r] = (blocks, payload) as the calls for packed runs take them -> (kept arrays, block pointers, n_blocks, payload pointers);
+    a payload of None goes in as a null pointer"""
+    blocks = [np.ascontiguousarray(b, dtype=PACKED_BLOCK_DTYPE) for b, _ in runs]
+    words = [None if w is None else np.ascontiguousarray(w, dtype=np.uint64) for _, w in runs]
+    bptr = (C.c_void_p * max(len(runs), 1))(*[a.ctypes.data for a in blocks])
+    wptr = (C.c_void_p * max(len(runs), 1))(*[None if a is None else a.ctypes.data for a in words])
+    n_blocks = np.array([len(a) for a in blocks], dtype=np.uint64)
+    return (blocks, words), bptr, n_blocks, wptr
+
+
+def packed_union(runs, device: int = 0, size_only: bool = False, cap_blocks: Optional[int] = None, cap_words: Optional[int] = None):
+    """gn_packed_union: the ascending union of the hashes of packed runs (runs[r] = (blocks, payload), PACKED_BLOCK_DTYPE records whose
+    word_at count from payload[0]) packed as one set -> (hashes, blocks, payload words); size_only -> (hashes, blocks, words) as counts.
+    cap_blocks / cap_words: the buffers' sizes when the bounds of the format are not wanted; a GanonHipError of GN_EOVERFLOW carries the
+    three sizes as .sizes"""
+    keep, bptr, n_blocks, wptr = _packed_runs(runs)
+    n, nb, nw = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    L = load_library()
+    if size_only:
+        _check(L.gn_packed_union(device, bptr, _p(n_blocks), wptr, len(runs), None, 0, None, 0, C.byref(n), C.byref(nb), C.byref(nw)))
+        return int(n.value), int(nb.value), int(nw.value)
+    total = int(sum(int(b["cnt"].sum()) for b in keep[0]))
+    most = (total + 511) // 512  # gn_packed_max_blocks, gn_packed_max_words
+    cap_blocks = most if cap_blocks is None else cap_blocks
+    cap_words = total - most if cap_words is None else cap_words
+    blocks = np.zeros(max(cap_blocks, 1), dtype=PACKED_BLOCK_DTYPE)
+    words = np.zeros(max(cap_words, 1), dtype=np.uint64)
+    try:
+        _check(L.gn_packed_union(device, bptr, _p(n_blocks), wptr, len(runs), blocks.ctypes.data_as(C.c_void_p), cap_blocks, _p(words), cap_words, C.byref(n),
+                                 C.byref(nb), C.byref(nw)))
+    except GanonHipError as e:
+        e.sizes = (int(n.value), int(nb.value), int(nw.value))
+        e.written = bool(blocks.view(np.uint8).any() or words.any())
+        raise
+    return int(n.value), blocks[: int(nb.value)], words[: int(nw.value)]
+
+
 SKETCH_M = 4096                # GN_SKETCH_M
 SKETCH_TABLE_MAX = 1 << 24     # GN_SKETCH_TABLE_MAX
 
@@ -535,6 +577,16 @@ class HipSketches:
         sizes = np.array([len(a) for a in sets], dtype=np.uint64)
         self._h = C.c_void_p()
         _check(load_library().gn_sketches_create(device, ptrs, _p(sizes), self.n, C.byref(self._h)))
+
+    @classmethod
+    def from_packed(cls, runs, device: int = 0) -> "HipSketches":
+        """gn_sketches_create_packed: one sketch per packed run (runs[r] = (blocks, payload), as packed_union takes them)"""
+        keep, bptr, n_blocks, wptr = _packed_runs(runs)
+        self = cls.__new__(cls)
+        self.n = len(runs)
+        self._h = C.c_void_p()
+        _check(load_library().gn_sketches_create_packed(device, bptr, _p(n_blocks), wptr, self.n, C.byref(self._h)))
+        return self
 
     def download(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """registers of sketches first .. first + n - 1, uint8 [n, SKETCH_M]"""
@@ -686,6 +738,18 @@ class HipFilter:
         assert len(total) == len(begin) == len(self._bins)
         _check(load_library().gn_filter_emplace_path_window(self._h, ptrs, _p(sizes), len(sets), paths.ctypes.data_as(C.c_void_p), paths.shape[1],
                                                             _p(total), _p(begin), chunk_hashes))
+
+    def emplace_path_packed_window(self, runs, paths: np.ndarray, total_rows, row_begin, chunk_words: int = 0) -> None:
+        """gn_filter_emplace_path_packed_window: emplace_path_window for packed sets.  runs[s] = (blocks, payload): PACKED_BLOCK_DTYPE records
+        whose word_at count from payload[0], and the uint64 payload words (None: a null pointer)"""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        assert paths.ndim == 2 and paths.shape[0] == len(runs)
+        keep, bptr, n_blocks, wptr = _packed_runs(runs)
+        total = np.ascontiguousarray(total_rows, dtype=np.uint64)
+        begin = np.ascontiguousarray(row_begin, dtype=np.uint64)
+        assert len(total) == len(begin) == len(self._bins)
+        _check(load_library().gn_filter_emplace_path_packed_window(self._h, bptr, _p(n_blocks), wptr, len(runs), paths.ctypes.data_as(C.c_void_p), paths.shape[1],
+                                                                   _p(total), _p(begin), chunk_words))
 
     def extend_path(self, sets: Sequence[np.ndarray], paths: np.ndarray, quotas: Sequence[np.ndarray]) -> None:
         """gn_filter_extend_path: sets[s] (strictly ascending uint64) along paths[s] (PATH_DTYPE, [len(sets), depth]) of an HIBF that holds

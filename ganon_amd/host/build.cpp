@@ -16,7 +16,8 @@
 // (csrc/gn_packed_set.h) in RAM (packed) or in files of --tmp-output-folder that live as long as the command (spilled).
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
 //
-// The hierarchical modes (this project's extensions, like --device) take the same hash sets: --hibf (build_hibf.cpp),
+// The hierarchical modes (this project's extensions, like --device) take the same hash sets: --hibf (build_hibf.cpp; with --hibf-hash-sets
+// packed|spilled it takes them packed, from the same arenas),
 // --hibf --verify-index (build_verify.cpp; in parts build_verify_parts.cpp), --hibf --update (build_update.cpp).  The files are written by build_write.cpp.
 //
 // Differences from the reference that cannot be avoided here: targets are laid out in the order of
@@ -107,7 +108,17 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
         return say("--hash-sets has to be raw, packed or spilled");
     for (const auto& [on, mode] : { std::pair<bool, const char*>{ c.update_given, "--update" }, { c.verify_given, "--verify-index" }, { c.hibf, "--hibf" } })
         if (on && c.hash_sets != "raw")
-            return say(std::string("--hash-sets ") + c.hash_sets + " cannot be used with " + mode + " (unions, sketches and probes read raw sets; only a flat .ibf is built from packed ones)");
+            return say(std::string("--hash-sets ") + c.hash_sets + " cannot be used with " + mode + " (unions, sketches and probes read raw sets; only a flat .ibf is built from packed ones)" +
+                       (c.update_given || c.verify_given ? "" : "; use --hibf-hash-sets"));
+    // the hierarchical build keeps packed sets by a switch of its own (its unions, sketches and insert have packed twins; the probes and
+    // deals of --update and --verify-index read raw sets)
+    if (c.hibf_hash_sets != "raw" && c.hibf_hash_sets != "packed" && c.hibf_hash_sets != "spilled")
+        return say("--hibf-hash-sets has to be raw, packed or spilled");
+    if (c.hibf_hash_sets_given && !c.hibf)
+        return say("--hibf-hash-sets needs --hibf (a flat .ibf is built from packed sets with --hash-sets)");
+    for (const auto& [on, mode] : { std::pair<bool, const char*>{ c.update_given, "--update" }, { c.verify_given, "--verify-index" } })
+        if (on && c.hibf_hash_sets_given)
+            return say(std::string("--hibf-hash-sets ") + c.hibf_hash_sets + " cannot be used with " + mode + " (its probes and deals read raw sets)");
     if (c.device_memory_given && c.device_memory == 0)
         return say("--device-memory has to be > 0");
     // the hierarchical build in parts has switches of its own (a tree is cut by IBF and by padded device rows, not by file rows)
@@ -250,6 +261,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--hash-sets         " << c.hash_sets << '\n';
     if (c.hibf)
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
+    if (c.hibf_hash_sets_given)
+        std::cerr << "--hibf-hash-sets    " << c.hibf_hash_sets << '\n';
     if (c.hibf_memory_given)
         std::cerr << "--hibf-memory       " << c.hibf_memory << '\n';
     if (c.hibf_devices_given)
@@ -326,6 +339,12 @@ const char* kHelp =
     "                               each.  Default: the single --device, where hashing, unions and sketches stay.  Two families of\n"
     "                               switches because --device-memory counts file rows of one matrix and a --device list also deals\n"
     "                               the hashing threads; with --hibf both stay refused.  Not with --update or --verify-index\n"
+    "      --hibf-hash-sets arg     [--hibf] how the hierarchical build keeps the targets' hash sets: raw, packed or spilled, as\n"
+    "                               --hash-sets keeps a flat build's.  Packed sets stay packed from hashing to the insert: a target\n"
+    "                               of several files is united on the packed bytes (into one more arena, or one more file\n"
+    "                               <output>.hashsets.<pid>.united), the sketches and the merged bins' sizes are taken from them, and\n"
+    "                               the insert decodes a block in registers.  The same file.  Two families here too: --hash-sets\n"
+    "                               stays refused with --hibf.  Default: raw.  Not with --update or --verify-index\n"
     "      --layout arg             [--hibf] how the tree is chosen: rule (from the targets' hash counts alone), sketch (by size,\n"
     "                               from HyperLogLog estimates of the unions of neighbouring targets) or similarity (as sketch,\n"
     "                               with targets of comparable size reordered so that related ones are neighbours; the\n"
@@ -421,7 +440,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--verify-memory", "--verify-devices", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--verify-memory", "--verify-devices", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -524,6 +543,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.device_memory = u("--device-memory", ~0ull), c.device_memory_given = true;
         if (vals.count("--hash-sets"))
             c.hash_sets = vals["--hash-sets"];
+        if (vals.count("--hibf-hash-sets"))
+            c.hibf_hash_sets = vals["--hibf-hash-sets"], c.hibf_hash_sets_given = true;
         if (vals.count("--hibf-devices"))
             c.hibf_devices = device_list("--hibf-devices"), c.hibf_devices_given = true;
         if (vals.count("--hibf-memory"))
@@ -603,7 +624,7 @@ std::vector<Target> read_input_file(const Config& c, Totals& totals)
 }
 
 // count_hashes (:184-249) for the targets this thread draws from the shared cursor
-// (arena: --hash-sets packed|spilled -- this thread's, number arena_no; the files' sets are packed and their payload goes there)
+// (arena: --hash-sets / --hibf-hash-sets packed|spilled -- this thread's, number arena_no; the files' sets are packed and their payload goes there)
 void hash_targets(const Config& c, int device, std::vector<Target>& targets, std::atomic<size_t>& next, Totals& totals, std::string& fatal,
                   std::mutex& log_mutex, SetArena* arena, uint32_t arena_no)
 {
@@ -724,8 +745,10 @@ bool run(Config c)
     if (targets.empty() && !remove_only)
         return fail("No valid input files");
 
-    // --hash-sets packed|spilled: one arena per hashing thread; they live until the command ends (a spilled one's file goes with it)
-    const bool                             packed_sets = c.hash_sets != "raw";
+    // --hash-sets packed|spilled, and --hibf-hash-sets with --hibf: one arena per hashing thread; they live until the command ends (a
+    // spilled one's file goes with it)
+    const std::string&                     sets_mode   = c.hibf ? c.hibf_hash_sets : c.hash_sets;
+    const bool                             packed_sets = sets_mode != "raw";
     std::vector<std::unique_ptr<SetArena>> arenas;
 
     counting.start();
@@ -742,7 +765,7 @@ bool run(Config c)
         try
         {
             for (unsigned i = 0; packed_sets && i < nt; ++i)
-                arenas.emplace_back(c.hash_sets == "spilled" ? new SetArena((fs::path(output_folder(c)) / (fs::path(c.output_file).filename().string() + ".hashsets." +
+                arenas.emplace_back(sets_mode == "spilled" ? new SetArena((fs::path(output_folder(c)) / (fs::path(c.output_file).filename().string() + ".hashsets." +
                                                                                                          std::to_string(::getpid()) + "." + std::to_string(i) + ".tmp"))
                                                                                 .string())
                                                              : new SetArena());
@@ -772,7 +795,7 @@ bool run(Config c)
     if (c.update_given)
         return run_update(c, targets, counting);
     if (c.hibf)
-        return run_hibf(c, targets, totals, whole, counting);
+        return run_hibf(c, targets, totals, whole, counting, arenas);
 
     std::vector<const uint64_t*> arena_words;
     if (c.verbose || packed_sets)

@@ -19,6 +19,7 @@
 #include <ctime>
 #include <filesystem>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -46,6 +47,9 @@ struct Config // Config.hpp:10-27
     bool        device_memory_given = false;
     std::string hash_sets = "raw";    // (--hash-sets: how the flat build keeps the hash sets between hashing and filling -- raw: 8 bytes a hash in
                                       //  memory; packed: csrc/gn_packed_set.h in memory; spilled: the same in files of output_folder())
+    std::string hibf_hash_sets = "raw"; // (--hibf-hash-sets: the same three ways for the hash sets of a --hibf build -- its unions, sketches and
+                                        //  insert have packed twins; --update and --verify-index read raw sets)
+    bool        hibf_hash_sets_given = false;
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    hibf_memory = 0; // (--hibf-memory: most device bytes of IBF rows on an entry of hibf_devices at one time; 0 = from what is free)
     bool        hibf_memory_given = false, hibf_devices_given = false;
@@ -75,8 +79,9 @@ struct Target
     std::vector<std::string> files;
     std::vector<uint64_t>    hashes; // per file: its distinct hashes, ascending; files behind each other (:236-238)
     std::vector<uint64_t>    file_ends; // where each file's hashes end in `hashes` (--hibf unites the files of a target)
-    // --hash-sets packed|spilled: `hashes` stays empty; the target keeps its count and the blocks of its files' packed sets behind each
-    // other, whose word_at count from the start of arena `arena` (the one of the thread that hashed the target)
+    // --hash-sets / --hibf-hash-sets packed|spilled: `hashes` stays empty; the target keeps its count and the blocks of its files' packed sets behind each
+    // other, whose word_at count from the start of arena `arena` (the one of the thread that hashed the target; --hibf moves a target of
+    // several files to the arena of the unions, build_hibf.cpp)
     uint64_t                   count = 0;
     std::vector<GnPackedBlock> blocks;
     uint32_t                   arena = 0;
@@ -249,6 +254,23 @@ int  open_hibf(const Config& c, const std::vector<HibfShape>& ibfs, uint8_t hash
                const std::vector<std::string>& user_files, std::vector<uint64_t>& payload_at, std::string& err);
 bool save_piece(int fd, gn_filter* flt, uint32_t ibf, uint64_t n_rows, uint64_t row_bytes, uint64_t at, gnhost::PinnedBlock& stage, std::string& err);
 
+// the user bins' sets of a --hibf build from packed sets, as the library's calls for packed runs take them: per user bin its blocks and
+// the words of the arena their word_at count in; `bytes` is what one pass over all of them uploads (payload words and block tables)
+struct PackedSets
+{
+    std::vector<const gn_packed_block*> blocks;
+    std::vector<uint64_t>               n_blocks;
+    std::vector<const uint64_t*>        payload;
+    std::vector<uint64_t>               bytes; // per user bin
+};
+inline uint64_t packed_pass_bytes(const std::vector<GnPackedBlock>& blocks)
+{
+    uint64_t b = 0;
+    for (const GnPackedBlock& x : blocks)
+        b += 8ull * gn_packed_words(x.cnt, x.width) + sizeof(GnPackedItem);
+    return b;
+}
+
 // build_hibf_parts.cpp: the tree of a hierarchical filter, filled part by part over `devices` (one worker an entry) and written as it
 // goes; any failure removes the output file.  hash_bytes_uploaded: what the parts' passes over the hash sets sent to the devices.
 struct HibfPartsFill
@@ -259,14 +281,17 @@ struct HibfPartsFill
     const HibfPartPlan&                                  plan;
     const std::vector<int>&                              devices;
     const gnhibf::Paths&                                 paths;
-    const std::vector<std::pair<const uint64_t*, uint64_t>>& sets; // per user bin
+    const std::vector<std::pair<const uint64_t*, uint64_t>>& sets; // per user bin (packed: no pointer, the size alone)
     const std::vector<std::vector<std::string>>&         bin_path;
     const std::vector<std::string>&                      user_files;
+    const PackedSets*                                    packed = nullptr; // --hibf-hash-sets packed|spilled: the sets; null: raw sets
 };
 bool fill_and_save_hibf_parts(const HibfPartsFill& w, uint64_t& hash_bytes_uploaded);
 
 // the modes, after the inputs are hashed (build.cpp: run)
-bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting);   // build_hibf.cpp
+// (arenas: --hibf-hash-sets packed|spilled -- the hashing threads' arenas, by Target::arena; empty: raw sets)
+bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting,
+              const std::vector<std::unique_ptr<SetArena>>& arenas);                                                   // build_hibf.cpp
 // build_verify_parts.cpp: the same check of an index that does not fit what an entry of `devices` may hold at one time, part by part
 // (hibf_build_parts.hpp: the plan; hibf_verify_parts.hpp: what is carried from part to part); the same report on stdout
 bool run_verify_parts(const Config& c, std::vector<Target>& targets, const gnhost::FilterMeta& meta, const std::vector<uint64_t>& payload_at,

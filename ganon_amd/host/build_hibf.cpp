@@ -6,6 +6,10 @@
 //   (gn_filter_emplace_path) -> IBF after IBF streamed into the file (save_hibf: the twin of ganon_amd/ibf_file.py:save_hibf).
 // A tree that does not fit what a device may hold at one time (--hibf-memory, or what is free) is filled in parts over --hibf-devices
 // instead (hibf_build_parts.hpp: the plan; build_hibf_parts.cpp: the workers) and gives the same file.
+// --hibf-hash-sets packed|spilled: the targets' sets stay packed (csrc/gn_packed_set.h) from hashing to the insert, in the hashing
+// threads' arenas and one more for the unions of targets of several files; the unions (gn_packed_union), the sketches
+// (gn_sketches_create_packed) and the insert (gn_filter_emplace_path_packed_window) take packed runs: the same tree, rows and bits, so
+// the same file.
 #include "build_common.hpp"
 #include "hibf_layout.hpp"
 #include "hibf_layout_similarity.hpp"
@@ -16,6 +20,7 @@
 #include <cmath>
 #include <iomanip>
 #include <memory>
+#include <unistd.h>
 
 namespace gnbuild
 {
@@ -33,7 +38,7 @@ struct SketchLaps // seconds inside the `layout` lap: the rest of it is the host
 };
 
 bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, const std::vector<uint32_t>& user_target, const std::vector<uint64_t>& counts,
-                         uint32_t tmax, uint8_t h, gnhibf::Layout& lay, SketchLaps& laps, std::string& err)
+                         const PackedSets* packed, uint32_t tmax, uint8_t h, gnhibf::Layout& lay, SketchLaps& laps, std::string& err)
 {
     constexpr uint64_t kTableBytes = 4ull << 30; // the most host memory a union table may take
     const uint64_t     n = counts.size(), width = gnhibf::sketch_width(n, tmax);
@@ -52,7 +57,9 @@ bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, co
         std::vector<const uint64_t*> sets(n);
         for (uint64_t u = 0; u < n; ++u)
             sets[u] = targets[user_target[u]].hashes.data();
-        if (gn_sketches_create(c.device, sets.data(), counts.data(), (uint32_t)n, &sk) != GN_OK)
+        const int rc = packed ? gn_sketches_create_packed(c.device, packed->blocks.data(), packed->n_blocks.data(), packed->payload.data(), (uint32_t)n, &sk)
+                              : gn_sketches_create(c.device, sets.data(), counts.data(), (uint32_t)n, &sk);
+        if (rc != GN_OK)
         {
             err = gn_last_error();
             return false;
@@ -114,7 +121,37 @@ bool lay_out_by_sketches(const Config& c, const std::vector<Target>& targets, co
 
 } // namespace
 
-bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting)
+namespace
+{
+
+// --hibf-hash-sets packed|spilled: a target of several files becomes one packed set, the union of its files' sets, whose payload goes
+// behind the words of `united` (the hashing arena keeps the files' words: they are dead from here on, and not reclaimed)
+bool unite_files_packed(const Config& c, Target& tg, const uint64_t* words, SetArena& united, uint32_t united_no)
+{
+    const gn_packed_block*     run = reinterpret_cast<const gn_packed_block*>(tg.blocks.data());
+    const uint64_t             n_blocks = tg.blocks.size();
+    std::vector<GnPackedBlock> out(gn_packed_max_blocks(tg.count));
+    std::vector<uint64_t>      payload(gn_packed_max_words(tg.count));
+    uint64_t                   n = 0, nb = 0, nw = 0;
+    if (gn_packed_union(c.device, &run, &n_blocks, &words, 1, reinterpret_cast<gn_packed_block*>(out.data()), out.size(), payload.data(), payload.size(), &n,
+                        &nb, &nw) != GN_OK)
+        return false;
+    out.resize(nb);
+    const uint64_t base = united.words();
+    united.append(payload.data(), nw);
+    for (GnPackedBlock& b : out)
+        b.word_at += base;
+    tg.blocks.swap(out);
+    tg.count = n;
+    tg.arena = united_no;
+    tg.file_ends.assign(1, n);
+    return true;
+}
+
+} // namespace
+
+bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& totals, Lap& whole, const Lap& counting,
+              const std::vector<std::unique_ptr<SetArena>>& arenas)
 {
     Lap            uniting, laying, filling, writing;
     const uint8_t  h = c.hash_functions == 0 ? 4 : c.hash_functions; // (what `ganon build` passes to raptor, config.py:138-145)
@@ -125,20 +162,65 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     std::vector<uint64_t>    counts;
     std::vector<std::string> files;
     const std::string        dir = output_folder(c);
-    for (uint32_t t = 0; t < targets.size(); ++t)
+    const bool               packed_sets = c.hibf_hash_sets != "raw";
+    // packed sets: the words of every arena by Target::arena -- the hashing threads' (complete: they may be mapped) and, behind them, the
+    // one the unions are appended to, which is mapped only when the last union is in it; it goes, with its file, when this function returns
+    std::vector<const uint64_t*> arena_words;
+    std::unique_ptr<SetArena>    united;
+    uint64_t                     n_united = 0;
+    try
     {
-        Target& tg = targets[t];
-        if (tg.hashes.empty())
-            continue;
-        if (!unite_files(c, tg))
-            return fail(gn_last_error());
-        user_target.push_back(t);
-        counts.push_back(tg.hashes.size());
-        files.push_back(dir + "/" + user_bin_file_name(tg.name) + ".minimiser");
+        if (packed_sets)
+        {
+            for (const auto& a : arenas)
+                arena_words.push_back(a->data());
+            united.reset(c.hibf_hash_sets == "spilled"
+                             ? new SetArena((fs::path(dir) / (fs::path(c.output_file).filename().string() + ".hashsets." + std::to_string(::getpid()) + ".united")).string())
+                             : new SetArena());
+        }
+        for (uint32_t t = 0; t < targets.size(); ++t)
+        {
+            Target& tg = targets[t];
+            if (n_hashes(tg) == 0)
+                continue;
+            if (packed_sets && tg.file_ends.size() > 1)
+            {
+                if (!unite_files_packed(c, tg, arena_words[tg.arena], *united, (uint32_t)arenas.size()))
+                    return fail(gn_last_error());
+                ++n_united;
+            }
+            else if (!packed_sets && !unite_files(c, tg))
+                return fail(gn_last_error());
+            user_target.push_back(t);
+            counts.push_back(n_hashes(tg));
+            files.push_back(dir + "/" + user_bin_file_name(tg.name) + ".minimiser");
+        }
+        if (packed_sets)
+            arena_words.push_back(united->data());
+    }
+    catch (const std::exception& e) // (an arena: a file that cannot be created, written or mapped)
+    {
+        return fail(e.what());
     }
     if (counts.empty())
         return fail("No valid sequences to build");
     const uint64_t n_user = counts.size();
+    PackedSets     packed;
+    uint64_t       one_pass_bytes = 0; // what the one-pass build uploads: every user bin's set once
+    for (uint64_t u = 0; packed_sets && u < n_user; ++u)
+    {
+        const Target& tg = targets[user_target[u]];
+        packed.blocks.push_back(reinterpret_cast<const gn_packed_block*>(tg.blocks.data())), packed.n_blocks.push_back(tg.blocks.size());
+        packed.payload.push_back(arena_words[tg.arena]), packed.bytes.push_back(packed_pass_bytes(tg.blocks));
+        one_pass_bytes += packed.bytes.back();
+    }
+    if (packed_sets && (c.verbose || !c.quiet))
+    {
+        uint64_t hashes = 0, held = 0;
+        for (uint64_t u = 0; u < n_user; ++u)
+            hashes += counts[u], held += packed.bytes[u] - packed.n_blocks[u] * (sizeof(GnPackedItem) - sizeof(GnPackedBlock));
+        std::cerr << "hibf hash sets: " << hashes << " hashes held " << c.hibf_hash_sets << " in " << held << " bytes, " << n_united << " targets united" << std::endl;
+    }
     uint64_t       tmax   = c.tmax;
     if (!c.tmax_given)
         tmax = (uint64_t)std::ceil(std::sqrt((double)n_user) / 64.0) * 64; // build_update.py:487
@@ -148,7 +230,7 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     if (c.layout == "sketch" || c.layout == "similarity")
     {
         std::string err;
-        if (!lay_out_by_sketches(c, targets, user_target, counts, (uint32_t)tmax, h, lay, sketch_laps, err))
+        if (!lay_out_by_sketches(c, targets, user_target, counts, packed_sets ? &packed : nullptr, (uint32_t)tmax, h, lay, sketch_laps, err))
             return fail(err);
     }
     else
@@ -171,12 +253,18 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
             {
                 std::vector<const uint64_t*> sets;
                 std::vector<uint64_t>        sizes;
+                std::vector<const gn_packed_block*> blocks;
                 for (uint32_t u : lay.ibfs[r.child].members)
                 {
-                    sets.push_back(targets[user_target[u]].hashes.data());
-                    sizes.push_back(counts[u]);
+                    sets.push_back(packed_sets ? packed.payload[u] : targets[user_target[u]].hashes.data());
+                    sizes.push_back(packed_sets ? packed.n_blocks[u] : counts[u]);
+                    if (packed_sets)
+                        blocks.push_back(packed.blocks[u]);
                 }
-                if (gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), nullptr, 0, &n) != GN_OK)
+                uint64_t  nb = 0, nw = 0;
+                const int rc = packed_sets ? gn_packed_union(c.device, blocks.data(), sizes.data(), sets.data(), (uint32_t)sets.size(), nullptr, 0, nullptr, 0, &n, &nb, &nw)
+                                           : gn_hashes_union(c.device, sets.data(), sizes.data(), (uint32_t)sets.size(), nullptr, 0, &n);
+                if (rc != GN_OK)
                     return fail(gn_last_error());
             }
             rows = std::max(rows, gnbuild::hibf_run_bits(n, r.n_bins, c.max_fp, h));
@@ -246,9 +334,9 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     std::vector<std::vector<std::string>> bin_path; // one file per user bin
     for (const std::string& f : files)
         bin_path.push_back({ f });
-    uint64_t one_pass_bytes = 0; // what the one-pass build uploads: every user bin's set once
     for (uint64_t n : counts)
-        one_pass_bytes += n * 8;
+        if (!packed_sets)
+            one_pass_bytes += n * 8;
     if (c.verbose && plan.n_parts <= 100000) // (a plan is a rule: a budget of a few rows makes more parts than anyone reads)
         for (uint64_t p = 0; p < plan.n_parts; ++p)
             for (const HibfPiece& x : plan.part(p))
@@ -258,9 +346,9 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
     {
         std::vector<std::pair<const uint64_t*, uint64_t>> sets;
         for (uint64_t u = 0; u < n_user; ++u)
-            sets.push_back(hash_set(targets[user_target[u]]));
+            sets.push_back(packed_sets ? std::pair<const uint64_t*, uint64_t>{ nullptr, counts[u] } : hash_set(targets[user_target[u]]));
         uint64_t uploaded = 0;
-        if (!fill_and_save_hibf_parts(HibfPartsFill{ c, ibfs, h, plan, entries, paths, sets, bin_path, files }, uploaded))
+        if (!fill_and_save_hibf_parts(HibfPartsFill{ c, ibfs, h, plan, entries, paths, sets, bin_path, files, packed_sets ? &packed : nullptr }, uploaded))
             return false;
         filling.stop();
         writing.start(), writing.stop(); // (the rows went out piece by piece, inside the fill)
@@ -277,14 +365,24 @@ bool run_hibf(const Config& c, std::vector<Target>& targets, const Totals& total
         return fail(gn_last_error());
     try
     {
-        gnhibf::for_each_pooled(
-            n_user,
-            [&](size_t u) { return hash_set(targets[user_target[u]]); },
-            [&](size_t u) { return &paths.entries[u * paths.depth]; }, paths.depth,
-            [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>&) {
-                if (gn_filter_emplace_path(flt.get(), hashes, off, (uint32_t)n, p, paths.depth) != GN_OK)
-                    throw std::runtime_error(gn_last_error());
-            });
+        if (packed_sets) // one call over all user bins: it streams, nothing is pooled
+        {
+            std::vector<uint64_t> total_rows, row_begin(ibfs.size(), 0);
+            for (const HibfShape& s : ibfs)
+                total_rows.push_back(s.rows);
+            if (gn_filter_emplace_path_packed_window(flt.get(), packed.blocks.data(), packed.n_blocks.data(), packed.payload.data(), (uint32_t)n_user,
+                                                     paths.entries.data(), paths.depth, total_rows.data(), row_begin.data(), 0) != GN_OK)
+                throw std::runtime_error(gn_last_error());
+        }
+        else
+            gnhibf::for_each_pooled(
+                n_user,
+                [&](size_t u) { return hash_set(targets[user_target[u]]); },
+                [&](size_t u) { return &paths.entries[u * paths.depth]; }, paths.depth,
+                [&](const uint64_t* hashes, const uint64_t* off, size_t n, const gn_path_entry* p, const std::vector<size_t>&) {
+                    if (gn_filter_emplace_path(flt.get(), hashes, off, (uint32_t)n, p, paths.depth) != GN_OK)
+                        throw std::runtime_error(gn_last_error());
+                });
     }
     catch (const std::exception& e)
     {

@@ -2,7 +2,8 @@
 // hold at one time: the file is laid out first (open_hibf), then one worker thread per entry of --hibf-devices takes its parts in ascending
 // order -- an empty storage-only filter of the part's pieces, the user bins with a path entry in one of the part's IBFs through the
 // windowed insert (gn_filter_emplace_path_window: the rows are those of the whole IBF, a piece takes the bits of the rows it holds), every
-// piece streamed to its place in the file, the filter freed.  The hash sets stay in host memory and are read by all workers.  The file is
+// piece streamed to its place in the file, the filter freed.  The hash sets stay in host memory and are read by all workers -- raw, or
+// packed (--hibf-hash-sets packed|spilled: blocks and arena words through gn_filter_emplace_path_packed_window).  The file is
 // byte for byte the one-pass build's.  Modelled on build_slabs.cpp, the flat build in row slabs.
 #include "build_common.hpp"
 
@@ -30,7 +31,10 @@ struct PartInput
     std::vector<uint64_t>        total_rows, row_begin, set_sizes;
     std::vector<const uint64_t*> sets;
     std::vector<gn_path_entry>   paths;
-    uint64_t                     hashes = 0;
+    // packed sets: per user bin taken its blocks and the words of its arena instead of pointer and size
+    std::vector<const gn_packed_block*> blocks;
+    std::vector<uint64_t>               n_blocks;
+    uint64_t                     bytes = 0; // what the part's pass uploads
     PartInput(const HibfPartsFill& w, uint64_t p) : pieces(w.plan.part(p))
     {
         std::vector<int64_t> local(w.ibfs.size(), -1);
@@ -47,9 +51,13 @@ struct PartInput
         {
             if (compact_path(&w.paths.entries[u * depth], depth, local, cut.data()) == 0)
                 continue;
-            sets.push_back(w.sets[u].first), set_sizes.push_back(w.sets[u].second);
+            if (w.packed)
+                sets.push_back(w.packed->payload[u]), blocks.push_back(w.packed->blocks[u]), n_blocks.push_back(w.packed->n_blocks[u]);
+            else
+                sets.push_back(w.sets[u].first);
+            set_sizes.push_back(w.sets[u].second);
             paths.insert(paths.end(), cut.begin(), cut.end());
-            hashes += w.sets[u].second;
+            bytes += w.packed ? w.packed->bytes[u] : w.sets[u].second * 8;
         }
     }
 };
@@ -86,8 +94,11 @@ bool fill_and_save_hibf_parts(const HibfPartsFill& w, uint64_t& hash_bytes_uploa
                 if (gn_filter_create_hibf_storage(w.devices[e], (uint32_t)in.descs.size(), in.descs.data(), &raw) != GN_OK)
                     return give_up(gn_last_error());
                 gnhost::OwnedFilter flt(raw);
-                if (gn_filter_emplace_path_window(flt.get(), in.sets.data(), in.set_sizes.data(), (uint32_t)in.sets.size(), in.paths.data(), w.paths.depth,
-                                                  in.total_rows.data(), in.row_begin.data(), 0) != GN_OK)
+                const int rc = w.packed ? gn_filter_emplace_path_packed_window(flt.get(), in.blocks.data(), in.n_blocks.data(), in.sets.data(), (uint32_t)in.sets.size(),
+                                                                               in.paths.data(), w.paths.depth, in.total_rows.data(), in.row_begin.data(), 0)
+                                        : gn_filter_emplace_path_window(flt.get(), in.sets.data(), in.set_sizes.data(), (uint32_t)in.sets.size(), in.paths.data(),
+                                                                        w.paths.depth, in.total_rows.data(), in.row_begin.data(), 0);
+                if (rc != GN_OK)
                     return give_up(gn_last_error());
                 const double fill_s = since(t0);
                 t0                  = std::chrono::steady_clock::now();
@@ -100,7 +111,7 @@ bool fill_and_save_hibf_parts(const HibfPartsFill& w, uint64_t& hash_bytes_uploa
                         return give_up(why == "write error on the output file" ? "write error on " + c.output_file : why);
                 }
                 const double write_s = since(t0);
-                uploaded += in.hashes * 8;
+                uploaded += in.bytes;
                 if (c.verbose)
                 {
                     std::lock_guard<std::mutex> lk(mu);

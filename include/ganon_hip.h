@@ -488,6 +488,31 @@ int gn_filter_emplace_path(gn_filter* f, const uint64_t* hashes, const uint64_t*
 int gn_filter_create_hibf_storage(int device, uint32_t n_ibf, const gn_ibf_desc* ibfs, gn_filter** out);
 int gn_filter_emplace_path_window(gn_filter* f, const uint64_t* const* sets, const uint64_t* set_sizes, uint32_t n_sets, const gn_path_entry* paths,
                                   uint32_t depth, const uint64_t* total_rows, const uint64_t* row_begin, uint64_t chunk_hashes);
+/* The hierarchical build from packed sets (`ganon-build --hibf --hibf-hash-sets packed|spilled`; no counterpart in the reference).  All
+ * three take runs as gn_filter_emplace_packed_window takes them: run r is blocks[r][0 .. n_blocks[r]) with word_at counting from
+ * payload[r][0], its hashes are those of its blocks behind each other, and a short block may lie in the middle (a target's files' sets).
+ * A block with cnt of 0 or over 512, width over 64, or payload words without a payload is GN_EINVAL in each of them.  Only packed bytes
+ * cross the link: blocks and payload words go up, a kernel decodes a block per wave.
+ * gn_packed_union: the ascending union of all hashes of all runs, packed as ONE set -- word for word what gn_packed_encode makes of
+ * gn_hashes_union over the decoded runs (a set is cut every 512 hashes; word_at counts from out_payload[0]).  The runs need not be
+ * ascending across blocks (a sort follows): a target of several files goes in as the one run it is.  With out_blocks and out_payload
+ * NULL the call answers *n_union, *n_out_blocks and *n_out_words alone (the cardinality of a merged bin).  A result of n hashes has at
+ * most ceil(n / 512) blocks and n - ceil(n / 512) words, and n is at most the runs' hashes: buffers can be sized without a first call.
+ * GN_EOVERFLOW, with the three sizes set and nothing written, when a buffer is too small; GN_ERANGE beyond 2^31 - 1 hashes in one call, as
+ * gn_hashes_union.
+ * gn_sketches_create_packed: the handle gn_sketches_create returns, every register equal to that of gn_sketches_create on the decoded
+ * runs (sketch r of run r; a run without a block is all zeros).
+ * gn_filter_emplace_path_packed_window: gn_filter_emplace_path_window for packed sets -- the same filter kinds, paths, total_rows /
+ * row_begin, checks and bits; a set's size is the sum of its blocks' cnt, and hash i of the set is hash i of the run.  With row_begin all 0
+ * and total_rows equal to f's rows it sets exactly the bits gn_filter_emplace_path sets.  The two staging chunks hold chunk_words payload
+ * words (0: 1 Mi words; at least the 511 words a block can have) and the tables of their blocks.  Everything is checked before anything
+ * is launched and a refused call writes nothing. */
+int gn_packed_union(int device, const gn_packed_block* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload, uint32_t n_runs,
+                    gn_packed_block* out_blocks, uint64_t cap_blocks, uint64_t* out_payload, uint64_t cap_words, uint64_t* n_union,
+                    uint64_t* n_out_blocks, uint64_t* n_out_words);
+int gn_filter_emplace_path_packed_window(gn_filter* f, const gn_packed_block* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload,
+                                         uint32_t n_sets, const gn_path_entry* paths, uint32_t depth, const uint64_t* total_rows,
+                                         const uint64_t* row_begin, uint64_t chunk_words);
 
 /* `ganon-build --hibf --verify-index`: the insert read back.  Same sets, same paths, same hashes; loads where gn_filter_emplace_path ORs.
  * set s = hashes[set_off[s] .. set_off[s+1]) (host memory; any order, repeats allowed).  A hash is CONTAINED in an entry when, for at
@@ -647,6 +672,9 @@ int gn_filter_fold_ibf(gn_filter* dst, uint32_t dst_ibf, uint32_t dst_first, uin
 #define GN_SKETCH_TABLE_MAX (1ull << 24)
 typedef struct gn_sketches gn_sketches;
 int gn_sketches_create(int device, const uint64_t* const* sets, const uint64_t* sizes, uint32_t n_sets, gn_sketches** out);
+/* (from packed runs: see gn_packed_union above) */
+int gn_sketches_create_packed(int device, const gn_packed_block* const* blocks, const uint64_t* n_blocks, const uint64_t* const* payload, uint32_t n_runs,
+                              gn_sketches** out);
 int gn_sketches_free(gn_sketches* s);
 int gn_sketches_download(gn_sketches* s, uint32_t first, uint32_t n, uint8_t* out);
 int gn_sketches_union_table(gn_sketches* s, const uint32_t* order, uint32_t n, uint32_t j0, uint32_t j1, uint32_t width, uint64_t* out);

@@ -38,7 +38,10 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
                   sets hold, beside 8 x hashes) and "rss_anon_kb", the process's anonymous memory when hashing ends
   --hibf-memory BYTES / --hibf-devices LIST  [--hibf] passed on to the hierarchical build: the tree is filled in parts when it is larger
                   than BYTES of device rows, the parts dealt to the entries of LIST; the run reports "parts", "hash_bytes_uploaded"
-                  beside "one_pass_hash_bytes", and per part its device bytes, the sets it took and its fill and write seconds"""
+                  beside "one_pass_hash_bytes", and per part its device bytes, the sets it took and its fill and write seconds
+  --hibf-hash-sets MODE  [--hibf] passed on to the hierarchical build (raw | packed | spilled): the run reports "hash_sets", "hashes",
+                  "hash_set_bytes" and "united" (the `hibf hash sets:` line); every hierarchical build reports "peak_rss_kb", the
+                  process's largest resident set, and the median run "laps_s", the four laps of every run"""
 import json
 import math
 import os
@@ -50,7 +53,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hash-sets": "", "--hibf-memory": "", "--hibf-devices": ""}
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hash-sets": "", "--hibf-memory": "", "--hibf-devices": "", "--hibf-hash-sets": ""}
 pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
@@ -113,6 +116,7 @@ device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["
               (["--hash-sets", opts["--hash-sets"]] if opts["--hash-sets"] else [])
 device_hibf = ["--device", opts["--device"]] if opts["--device"] else []
 parts_hibf = (["--hibf-memory", opts["--hibf-memory"]] if opts["--hibf-memory"] else []) + (["--hibf-devices", opts["--hibf-devices"]] if opts["--hibf-devices"] else [])
+sets_hibf = ["--hibf-hash-sets", opts["--hibf-hash-sets"]] if opts["--hibf-hash-sets"] else []
 
 
 def flat_run(max_fp="0.05", extra=()):
@@ -153,13 +157,28 @@ def flat_run(max_fp="0.05", extra=()):
     return res
 
 
+def run_with_rusage(cmd, res):
+    """subprocess.run(cmd, capture_output=True, text=True) that also notes the child's largest resident set in res["peak_rss_kb"]: the
+    output goes through files, so that the child can be waited for with wait4"""
+    with open(os.path.join(d, "stdout.txt"), "w+") as so, open(os.path.join(d, "stderr.txt"), "w+") as se:
+        child = subprocess.Popen(cmd, stdout=so, stderr=se)
+        _, status, usage = os.wait4(child.pid, 0)
+        child.returncode = os.waitstatus_to_exitcode(status)
+        so.seek(0), se.seek(0)
+        res["peak_rss_kb"] = usage.ru_maxrss
+        return subprocess.CompletedProcess(cmd, child.returncode, so.read(), se.read())
+
+
 def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     res = {}
     t0 = time.time()
     cmd = [exe, "-i", os.path.join(d, tsv), "-o", os.path.join(d, db), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
-           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf + (parts_hibf if db == "db.hibf" else [])
-    p = subprocess.run(cmd, capture_output=True, text=True)
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf + (parts_hibf if db == "db.hibf" else []) + sets_hibf
+    p = run_with_rusage(cmd, res)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    m = re.search(r"^hibf hash sets: (\d+) hashes held (\w+) in (\d+) bytes, (\d+) targets united$", p.stderr, re.M)
+    if m:
+        res["hashes"], res["hash_sets"], res["hash_set_bytes"], res["united"] = int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4))
     m = re.search(r"filled in (\d+) parts?, (\d+) hash bytes uploaded(?: \(one pass: (\d+)\))?", p.stderr)
     if m:
         res["parts"], res["hash_bytes_uploaded"], res["one_pass_hash_bytes"] = int(m.group(1)), int(m.group(2)), int(m.group(3) or m.group(2))
@@ -293,6 +312,8 @@ def median_of(runs):
         return runs[-1]
     mid = dict(good[len(good) // 2])
     mid["totals_s"] = [r.get("total_s", r["wall_s"]) for r in runs]
+    if all("emplace_s" in r for r in runs):
+        mid["laps_s"] = [(r["hash_s"], r["union_s"], r["emplace_s"], r["write_s"]) for r in runs]
     return mid
 
 
