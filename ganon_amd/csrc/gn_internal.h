@@ -414,6 +414,29 @@ struct GnFastqHdrBufs // gn_stream_fastq_headers
     size_t          scan_bytes = 0;
 };
 
+// wrapped multi-record FASTA tokenised on the device (gn_genome.hip); allocated by the first gn_stream_upload_genome_text
+struct GnGenomeBufs
+{
+    bool                      ready = false;
+    GnDev<uint8_t>            d_text;
+    GnDev<uint8_t>            d_letters;   // the kept letters back to back, behind a pad that takes the carried tail
+    GnDev<uint8_t>            d_tail;      // last w - 1 letters of the record a text left open
+    GnDev<uint64_t>           d_carry;     // [0] letters in d_tail [1] letters of the open record so far [2,3] the next values
+    GnDev<uint8_t>            d_sum;       // per 4 KiB tile its summary, then the exclusive scan (GnGxTile)
+    GnDev<uint64_t>           d_bad;       // per tile: smallest illegal offset before / behind its first line start (uint2)
+    GnDev<uint64_t>           d_rec_at, d_rec_l0, d_rec_len; // per slot: offset of its header, rank of its first letter, its letters
+    GnDev<uint8_t>            d_rec_state;
+    GnDev<uint32_t>           d_pieces;    // per slot: pieces, their bytes; then the exclusive scans
+    GnDev<uint64_t>           d_bytes, d_piece_off, d_byte_off;
+    GnDev<unsigned long long> d_ctl;       // see gn_genome.hip
+    GnPinned<unsigned long long> h_ctl;
+    GnDev<uint8_t>            d_scan;
+    size_t                    scan_bytes = 0;
+    uint32_t                  tiles_cap = 0, slot_cap = 0;
+    bool                      pending = false, continues = false; // text uploaded and not indexed yet; it continued a record
+    uint32_t                  n_records = 0;
+};
+
 struct gn_stream
 {
     gn_filter*  f  = nullptr;
@@ -502,6 +525,7 @@ struct gn_stream
     bool                fq_pair = false; // the resident text batch is a pair of texts (gn_stream_upload_text_pair)
     double              fq_probe[4]{}; // $GANON_HIP_CALL_TIMING: seconds in the calls of gn_stream_upload_fastq, batches
     bool                fq_pending = false;  // text uploaded, gn_stream_fastq_index not yet called
+    GnGenomeBufs        gx;                  // genome text tokenised on the device (gn_genome.hip)
     // pinned host
     GnPinned<unsigned long long> h_ctr;
     // state

@@ -39,7 +39,12 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_filter_emplace_runs_window", "gn_filter_create_hibf_storage", "gn_filter_emplace_path_window",
                "gn_stream_distinct_hashes_packed", "gn_filter_emplace_packed_window",
                "gn_packed_union", "gn_sketches_create_packed", "gn_filter_emplace_path_packed_window",
-               "gn_filter_probe_path_window", "gn_filter_probe_paths_shared_window"]
+               "gn_filter_probe_path_window", "gn_filter_probe_paths_shared_window",
+               "gn_stream_upload_genome_text", "gn_stream_genome_index", "gn_stream_genome_records"]
+
+
+GENOME_CONTINUES, GENOME_OPEN_END = 1, 2  # flags of gn_stream_upload_genome_text
+GENOME_BAD_LETTER, GENOME_NO_HEADER = 1, 2  # status of gn_stream_genome_index
 
 
 class PostFilter(C.Structure):  # gn_postfilter
@@ -234,6 +239,9 @@ def load_library():
     L.gn_stream_fetch_letters.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
     L.gn_stream_upload_text_device.argtypes = [vp, vp, u64, i32, i32]
     L.gn_stream_fastq_headers.argtypes = [vp, vp, u64, vp, C.POINTER(u64)]
+    L.gn_stream_upload_genome_text.argtypes = [vp, vp, u64, u32, u32, u64, u32]
+    L.gn_stream_genome_index.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64), C.POINTER(u64)]
+    L.gn_stream_genome_records.argtypes = [vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gn_last_error", "gn_hibf_row_stride_words"):   # (const char* and uint64_t returns, set above)
             getattr(L, name).restype = i32
@@ -1025,6 +1033,32 @@ class HipStream:
         out = [np.empty(self.n_reads, dtype=np.uint32) for _ in range(3)]
         _check(load_library().gn_stream_fastq_records(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
         return tuple(out)
+
+    def upload_genome_text(self, text, w: int, stride: int, min_length: int = 0, continues: bool = False, open_end: bool = False) -> None:
+        """wrapped multi-record FASTA text, tokenised and cut into pieces on the device (gn_stream_upload_genome_text; asynchronous).
+        continues: text[0] goes on with the record the previous text left open; open_end: the text ends inside its last record"""
+        text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        self._keep = (text,)
+        flags = (GENOME_CONTINUES if continues else 0) | (GENOME_OPEN_END if open_end else 0)
+        _check(load_library().gn_stream_upload_genome_text(self._h, _p(text), text.size, w, stride, min_length, flags))
+
+    def genome_index(self) -> dict:
+        """waits for the tokeniser (gn_stream_genome_index): n_records, n_pieces, n_bases, parsed_bytes, status (0, GENOME_BAD_LETTER,
+        GENOME_NO_HEADER), bad_at, open_letters.  The stream then holds the pieces like reads after upload()"""
+        nr, npc, st = C.c_uint32(), C.c_uint32(), C.c_int()
+        nb, pb, bad, op = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(load_library().gn_stream_genome_index(self._h, C.byref(nr), C.byref(npc), C.byref(nb), C.byref(pb), C.byref(st), C.byref(bad), C.byref(op)))
+        self.n_reads = npc.value
+        self._genome_records = nr.value
+        return dict(n_records=nr.value, n_pieces=npc.value, n_bases=nb.value, parsed_bytes=pb.value, status=st.value, bad_at=bad.value,
+                    open_letters=op.value)
+
+    def genome_records(self):
+        """(rec_at u64, rec_letters u64, rec_state u8) per record of the tokenised genome text (gn_stream_genome_records)"""
+        n = self._genome_records
+        out = (np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint8))
+        _check(load_library().gn_stream_genome_records(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
+        return out
 
     def sync(self) -> None:
         _check(load_library().gn_stream_sync(self._h))

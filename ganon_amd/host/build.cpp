@@ -11,7 +11,8 @@
 // piece), the classify-side minimiser kernels hash them, a radix sort + unique gives the file's hash SET
 // (gn_stream_distinct_hashes), the filter is created empty in HBM, filled by an atomic-OR scatter
 // (gn_filter_emplace_runs_window) and streamed to the file -- whole when it fits what a device may hold, otherwise in slabs of rows
-// over the entries of --device (build_slabs.cpp).  The host parses FASTA, keeps the hash sets and does the sizing arithmetic.  The sets
+// over the entries of --device (build_slabs.cpp).  The host parses FASTA (with --parse device the text travels and the device finds the
+// records and cuts the pieces, csrc/gn_genome.hip; the host reader stays the fallback), keeps the hash sets and does the sizing arithmetic.  The sets
 // are held in RAM at 8 bytes a hash (--hash-sets raw, the default; not `.min` files), or packed by the device as deltas of fixed width
 // (csrc/gn_packed_set.h) in RAM (packed) or in files of --tmp-output-folder that live as long as the command (spilled).
 // There is no CPU implementation of the hashing or the filter: without a HIP device the program fails.
@@ -89,6 +90,11 @@ bool take_from_index(Config& c, const char* opt, const std::string& path, bool w
     }
 }
 
+bool parse_mode_ok(const Config& c)
+{
+    return c.parse == "host" || c.parse == "device";
+}
+
 bool validate(Config& c) // Config.hpp:29-107, same messages
 {
     auto say = [&](const std::string& m) {
@@ -119,6 +125,8 @@ bool validate(Config& c) // Config.hpp:29-107, same messages
     for (const auto& [on, mode] : { std::pair<bool, const char*>{ c.update_given, "--update" }, { c.verify_given, "--verify-index" } })
         if (on && c.hibf_hash_sets_given)
             return say(std::string("--hibf-hash-sets ") + c.hibf_hash_sets + " cannot be used with " + mode + " (its probes and deals read raw sets)");
+    if (!parse_mode_ok(c))
+        return say("--parse has to be host or device");
     if (c.device_memory_given && c.device_memory == 0)
         return say("--device-memory has to be > 0");
     // the hierarchical build in parts has switches of its own (a tree is cut by IBF and by padded device rows, not by file rows)
@@ -263,6 +271,8 @@ void print_config(const Config& c) // Config.hpp:110-133
         std::cerr << "--hibf              " << c.hibf << '\n' << "--tmax              " << c.tmax << '\n';
     if (c.hibf_hash_sets_given)
         std::cerr << "--hibf-hash-sets    " << c.hibf_hash_sets << '\n';
+    if (c.parse != "host")
+        std::cerr << "--parse             " << c.parse << '\n';
     if (c.hibf_memory_given)
         std::cerr << "--hibf-memory       " << c.hibf_memory << '\n';
     if (c.hibf_devices_given)
@@ -325,6 +335,13 @@ const char* kHelp =
     "                               hashing thread in --tmp-output-folder, else the output's folder: appended to while hashing,\n"
     "                               mapped for the passes, removed when the command ends).  The same file.  Default: raw; not with\n"
     "                               --hibf, --update or --verify-index\n"
+    "      --parse arg              who finds the records of the input genomes: host (the sequential reader, on the hashing threads) or\n"
+    "                               device (a FASTA file, plain or .gz, travels as text in large chunks and is tokenised and cut into\n"
+    "                               pieces there; .bz2, blocked gzip and FASTQ names stay with the host reader, and so does any file\n"
+    "                               the device does not take whole: an illegal letter, a missing header, a record cut too short --\n"
+    "                               it is read again from its start, so messages, totals and the file written are those of host).\n"
+    "                               Applies wherever inputs are hashed: the flat build, --hibf, --update, --verify-index.  Default:\n"
+    "                               host.  $GANON_BUILD_PARSE_CHUNK: bytes of text per device chunk (default: what fills a batch)\n"
     "      --hibf                   Write a hierarchical filter (raptor 3.0.1 index, one user bin per target) sized from\n"
     "                               --max-fp; --hash-functions 0 means 4. Not with --filter-size or a --mode other than avg\n"
     "      --tmax arg               [--hibf] most technical bins of one IBF of the tree (>= 2).\n"
@@ -440,7 +457,7 @@ int parse_args(int argc, char** argv, Config& c)
         }
         static const std::set<std::string> known = { "--input-file", "--output-file", "--kmer-size", "--window-size",
                                                      "--hash-functions", "--max-fp", "--filter-size", "--mode", "--min-length",
-                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-hash-sets", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--verify-memory", "--verify-devices", "--update", "--remove", "--fold" };
+                                                     "--tmp-output-folder", "--threads", "--device", "--device-memory", "--hash-sets", "--hibf-hash-sets", "--parse", "--hibf-memory", "--hibf-devices", "--tmax", "--layout", "--verify-index", "--verify-memory", "--verify-devices", "--update", "--remove", "--fold" };
         if (!known.count(a))
         {
             std::cerr << "Option '" << a << "' does not exist" << std::endl;
@@ -545,6 +562,8 @@ int parse_args(int argc, char** argv, Config& c)
             c.hash_sets = vals["--hash-sets"];
         if (vals.count("--hibf-hash-sets"))
             c.hibf_hash_sets = vals["--hibf-hash-sets"], c.hibf_hash_sets_given = true;
+        if (vals.count("--parse"))
+            c.parse = vals["--parse"];
         if (vals.count("--hibf-devices"))
             c.hibf_devices = device_list("--hibf-devices"), c.hibf_devices_given = true;
         if (vals.count("--hibf-memory"))
@@ -623,6 +642,13 @@ std::vector<Target> read_input_file(const Config& c, Totals& totals)
     return targets;
 }
 
+// --parse device, over all hashing threads: files tokenised on the device, files it did not take whole (read again by the host reader),
+// files that never travel as text (.bz2, blocked gzip, FASTQ names), text bytes uploaded
+struct ParseCounters
+{
+    std::atomic<uint64_t> device{ 0 }, fell_back{ 0 }, host_only{ 0 }, bytes{ 0 };
+} g_parse;
+
 // count_hashes (:184-249) for the targets this thread draws from the shared cursor
 // (arena: --hash-sets / --hibf-hash-sets packed|spilled -- this thread's, number arena_no; the files' sets are packed and their payload goes there)
 void hash_targets(const Config& c, int device, std::vector<Target>& targets, std::atomic<size_t>& next, Totals& totals, std::string& fatal,
@@ -647,14 +673,39 @@ void hash_targets(const Config& c, int device, std::vector<Target>& targets, std
                     packed.clear();
                 std::vector<uint64_t> file_hashes;
                 unsigned              flushes = 0;
+                // --parse device: the file's text goes to the device; the totals of a file are committed only when it finished there,
+                // and a file the device does not take whole is read again from its start by the sequential reader, as with --parse host
+                bool on_device = false;
+                if (c.parse == "device")
+                {
+                    gnhost::Hasher::TextTotals tt;
+                    if (!gnhost::genome_text_eligible(file))
+                        g_parse.host_only++;
+                    else if (arena ? hasher.hash_text_file(file, c.min_length, packed, tt) : hasher.hash_text_file(file, c.min_length, file_hashes, flushes, tt))
+                    {
+                        on_device = true;
+                        totals.sequences += tt.sequences;
+                        totals.skipped_sequences += tt.skipped;
+                        totals.length_bp += tt.length_bp;
+                        g_parse.device++;
+                        g_parse.bytes += tt.bytes;
+                    }
+                    else
+                    {
+                        g_parse.fell_back++;
+                        hasher.discard();
+                        packed.clear();
+                        file_hashes.clear();
+                        flushes = 0;
+                    }
+                }
                 try
                 {
-                    gnhost::SeqReader reader(file);
-                    for (;;)
+                    for (std::unique_ptr<gnhost::SeqReader> reader(on_device ? nullptr : new gnhost::SeqReader(file)); reader;)
                     {
                         ids.clear();
                         seq.clear();
-                        if (!reader.next(ids, seq))
+                        if (!reader->next(ids, seq))
                             break;
                         if (seq.size() < c.min_length)
                         {
@@ -789,6 +840,9 @@ bool run(Config c)
         }
     }
     counting.stop();
+    if (c.verbose && c.parse == "device")
+        std::cerr << "parse device: " << g_parse.device << " files tokenised on the device, " << g_parse.fell_back << " fell back to the host reader, "
+                  << g_parse.host_only << " not eligible, " << g_parse.bytes << " text bytes uploaded" << std::endl;
 
     if (c.verify_given)
         return run_verify(c, targets, counting);
@@ -894,5 +948,7 @@ int main(int argc, char** argv)
         return EXIT_SUCCESS;
     if (r == 2)
         return EXIT_FAILURE;
-    return run(c) ? EXIT_SUCCESS : EXIT_FAILURE;
+    if (run(c))
+        return EXIT_SUCCESS;
+    return parse_mode_ok(c) ? EXIT_FAILURE : 2; // (an unusable --parse is refused like a usage error, with status 2)
 }

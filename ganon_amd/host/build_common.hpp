@@ -50,6 +50,8 @@ struct Config // Config.hpp:10-27
     std::string hibf_hash_sets = "raw"; // (--hibf-hash-sets: the same three ways for the hash sets of a --hibf build -- its unions, sketches and
                                         //  insert have packed twins; --update and --verify-index read raw sets)
     bool        hibf_hash_sets_given = false;
+    std::string parse = "host";       // (--parse: who finds the records of the input genomes -- host: the sequential reader; device: FASTA files travel
+                                      //  as text and are tokenised there, hasher.hpp hash_text_file, with the host reader as the fallback)
     bool        hibf = false;   // (not in the reference: write a raptor 3.0.1 HIBF index instead of a flat .ibf)
     uint64_t    hibf_memory = 0; // (--hibf-memory: most device bytes of IBF rows on an entry of hibf_devices at one time; 0 = from what is free)
     bool        hibf_memory_given = false, hibf_devices_given = false;

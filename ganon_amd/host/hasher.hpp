@@ -5,7 +5,12 @@
 
 #include "ganon_hip.h"
 
+#include "genome_chunks.hpp"
+#include "tunables.hpp"
+
 #include "../csrc/gn_packed_set.h"
+
+#include <zlib.h>
 
 #include <algorithm>
 #include <cstdint>
@@ -94,6 +99,33 @@ public:
     void flush(PackedFile& out) { flush(Sink{ &out.raw, &out.flushes, &out }); }
     void flush_short(PackedFile& out) { flush_short(Sink{ &out.raw, &out.flushes, &out }); }
 
+    // `--parse device`: what a file that went through hash_text_file adds to the build's totals
+    struct TextTotals
+    {
+        uint64_t sequences = 0, skipped = 0, length_bp = 0, bytes = 0; // bytes: text uploaded
+    };
+    // A whole FASTA file as text: read in large blocks into the pinned buffer (gzopen serves plain and .gz alike), cut into chunks at
+    // record or line boundaries (genome_chunks.hpp), tokenised and cut into pieces on the device (gn_stream_upload_genome_text), hashed as
+    // after add().  Every chunk is one flush; records shorter than the window go to flush_short, so call it (and flush) behind the file as
+    // after add().  false: the file is the sequential reader's -- an illegal letter, a line that is no header before the first one, no
+    // newline in a buffer, a read error, or a record cut with fewer than max(w, min_length) letters so far; what went into `out` by then
+    // is the caller's to discard, `tot` is only to be used after a true.
+    bool hash_text_file(const std::string& path, uint64_t min_length, std::vector<uint64_t>& out, unsigned& flushes, TextTotals& tot)
+    {
+        return hash_text_file(path, min_length, Sink{ &out, &flushes, nullptr }, tot);
+    }
+    bool hash_text_file(const std::string& path, uint64_t min_length, PackedFile& out, TextTotals& tot)
+    {
+        return hash_text_file(path, min_length, Sink{ &out.raw, &out.flushes, &out }, tot);
+    }
+    // forget what add() and hash_text_file() have queued (a file that is read again from its start)
+    void discard()
+    {
+        short_.clear();
+        fill_ = 0;
+        off_.assign(1, 0);
+    }
+
 private:
     struct Sink // where a device batch's set goes: appended to *raw, or -- a packed file's first batch -- into *packed
     {
@@ -157,11 +189,115 @@ private:
     static constexpr uint64_t kMaxBases  = 64ull << 20;
     static constexpr uint32_t kMaxPieces = 1u << 18;
 
+    bool hash_text_file(const std::string& path, uint64_t min_length, const Sink& to, TextTotals& tot)
+    {
+        struct Gz
+        {
+            gzFile f;
+            ~Gz()
+            {
+                if (f)
+                    gzclose(f);
+            }
+        } gz{ gzopen(path.c_str(), "rb") };
+        if (!gz.f)
+            return false;
+        gzbuffer(gz.f, 1 << 20);
+        // a chunk's pieces repeat w - 1 letters every stride: chunk x (1 + (w - 1) / stride) plus slack has to fit a batch (where it does
+        // not after all -- many short records -- the device takes a prefix and the rest is sent again)
+        const uint64_t fit   = (kMaxBases - (1u << 20)) / (stride_ + w_ - 1) * stride_;
+        const uint64_t chunk = std::clamp<uint64_t>(tun().size(Knob::build_parse_chunk, fit), 64, fit);
+        tot                  = TextTotals{};
+        uint64_t              fill = 0;
+        bool                  eof = false, continues = false;
+        std::vector<uint64_t> rec_at, rec_letters;
+        std::vector<uint8_t>  rec_state;
+        std::string           letters;
+        while (!eof || fill)
+        {
+            while (!eof && fill < chunk)
+            {
+                const int n = gzread(gz.f, bases_ + fill, (unsigned)std::min<uint64_t>(chunk - fill, 1u << 30));
+                if (n < 0)
+                    return false;
+                if (n == 0)
+                    eof = true;
+                fill += (uint64_t)n;
+            }
+            if (fill == 0)
+                break;
+            const GenomeCut cut = genome_cut(bases_, fill, eof);
+            if (!cut.ok)
+                return false;
+            for (uint64_t at = 0; at < cut.cut;) // one upload, unless the device takes a prefix of the records
+            {
+                const uint32_t flags = (continues && at == 0 ? GN_GENOME_CONTINUES : 0u) | (cut.open ? GN_GENOME_OPEN_END : 0u);
+                uint32_t       n_rec = 0, n_pieces = 0;
+                uint64_t       n_bases = 0, parsed = 0, bad_at = 0, open_letters = 0;
+                int            status = 0;
+                if (gn_stream_upload_genome_text(st_, bases_ + at, cut.cut - at, w_, stride_, min_length, flags) != GN_OK)
+                    throw std::runtime_error(hip_error());
+                const int rc = gn_stream_genome_index(st_, &n_rec, &n_pieces, &n_bases, &parsed, &status, &bad_at, &open_letters);
+                if (rc == GN_ERANGE || (rc == GN_OK && (status != 0 || parsed == 0)))
+                    return false;
+                if (rc != GN_OK)
+                    throw std::runtime_error(hip_error());
+                tot.bytes += cut.cut - at;
+                rec_at.resize(n_rec), rec_letters.resize(n_rec), rec_state.resize(n_rec);
+                if (gn_stream_genome_records(st_, rec_at.data(), rec_letters.data(), rec_state.data()) != GN_OK)
+                    throw std::runtime_error(hip_error());
+                for (uint32_t r = 0; r < n_rec; ++r) // a record is counted where it ends
+                {
+                    if (rec_state[r] == 3)
+                    {
+                        // the host path is the authority on a record that may still turn out shorter than --min-length or the window
+                        if (open_letters < std::max<uint64_t>(w_, min_length))
+                            return false;
+                        continue;
+                    }
+                    if (rec_state[r] == 1)
+                    {
+                        tot.skipped++;
+                        continue;
+                    }
+                    tot.sequences++;
+                    tot.length_bp += rec_letters[r];
+                    if (rec_state[r] == 2) // shorter than the window: its letters from the text, hashed by flush_short
+                    {
+                        if (r == 0 && (flags & GN_GENOME_CONTINUES))
+                            return false; // (cannot be: an open record that short ended the device path at its cut)
+                        const uint64_t end = r + 1 < n_rec ? rec_at[r + 1] : parsed;
+                        if (!genome_record_letters(bases_ + at + rec_at[r], end - rec_at[r], letters))
+                            return false;
+                        add(reinterpret_cast<const uint8_t*>(letters.data()), letters.size(), to);
+                    }
+                }
+                if (n_pieces)
+                {
+                    if (gn_stream_minimisers(st_, k_, w_) != GN_OK)
+                        throw std::runtime_error(hip_error());
+                    collect(to);
+                }
+                at += parsed;
+            }
+            continues = cut.open;
+            std::memmove(bases_, bases_ + cut.cut, fill - cut.cut);
+            fill -= cut.cut;
+        }
+        return true;
+    }
+
     void run(uint32_t w, const Sink& to)
     {
         const uint32_t n = (uint32_t)off_.size() - 1;
         if (gn_stream_upload_reads(st_, bases_, fill_, off_.data(), nullptr, n) != GN_OK || gn_stream_minimisers(st_, k_, w) != GN_OK)
             throw std::runtime_error(hip_error());
+        collect(to);
+    }
+
+    // the distinct hashes of the batch the stream has just hashed, into the sink
+    void collect(const Sink& to)
+    {
         const unsigned before = (*to.flushes)++;
         if (to.packed && before == 0) // the file's first batch: packed where it lies, only the packed bytes come back
         {

@@ -50,6 +50,7 @@ enum class Knob
     device,
     hip_ablate,
     full_teardown,
+    build_parse_chunk,
     COUNT
 };
 
@@ -92,6 +93,7 @@ inline const KnobInfo& knob_info(Knob k)
         { "GANON_DEVICE", "default for --device" },
         { "GANON_HIP_ABLATE", "the library's switch list (include/ganon_hip.h); the host adds sync=block when it names no sync mode" },
         { "GANON_HOST_FULL_TEARDOWN", "return from main normally (destructors, atexit handlers) instead of _Exit after the outputs are closed" },
+        { "GANON_BUILD_PARSE_CHUNK", "ganon-build --parse device: bytes of genome text per device chunk (default: what fills a 64 MiB batch; tests force many chunks on small files)" },
     };
     return table[(size_t)k];
 }

@@ -241,6 +241,35 @@ int gn_stream_text_pair_records2(gn_stream* s, uint32_t* rec_at, uint32_t* seq_a
 int gn_stream_fastq_index(gn_stream* s, uint32_t* n_reads, uint64_t* n_bases, uint64_t* parsed_bytes);
 int gn_stream_fastq_keep(gn_stream* s, uint32_t n_reads);
 int gn_stream_fastq_records(gn_stream* s, uint32_t* rec_at, uint32_t* seq_at, uint32_t* seq_len);
+/* A genome as it comes: wrapped, multi-record FASTA text, tokenised on the device for the builder (gn_genome.hip).  `text` is host
+ * memory, n_bytes <= the stream's max_bases, and its first byte is the first byte of a line.  Asynchronous; gn_stream_genome_index waits.
+ * The record rules are those of the host's sequential reader: a line whose first byte is '>' or ';' begins a record and none of its
+ * bytes is a letter; blank lines are ignored everywhere; in any other line isspace bytes and the digits are ignored, the dna15 letters
+ * ABCDGHKMNRSTUVWY (either case) are kept and any other byte gives status GN_GENOME_BAD_LETTER with bad_at = its offset; a non-blank
+ * line before the first header (without GN_GENOME_CONTINUES) gives GN_GENOME_NO_HEADER.  The text may end without a newline.
+ * A record is kept when it has >= min_length letters; a kept record with >= w letters is cut into pieces that begin every `stride`
+ * letters while a whole window fits, each of min(letters left, stride + w - 1) letters, written back to back into the stream's base
+ * buffer with off1: after gn_stream_genome_index the stream holds the batch as after gn_stream_upload_reads (read i = piece i), and
+ * gn_stream_minimisers, gn_stream_distinct_hashes and gn_stream_distinct_hashes_packed apply unchanged (with no piece there is
+ * nothing to hash).  Whole records are taken while their number and their pieces are <= max_reads and their bytes <= max_bases:
+ * parsed_bytes = offset of the first record not taken (== n_bytes: all were); a first record that alone is too large is GN_ERANGE.
+ *   GN_GENOME_OPEN_END   the text ends inside its last record: that record is hashed whatever its length so far (state 3),
+ *                        open_letters = its letters including what earlier texts carried, and the stream keeps its last
+ *                        min(letters, w - 1) letters and its length on the device
+ *   GN_GENOME_CONTINUES  text[0] continues the record the previous text on this stream left open: the carried letters are the
+ *                        head of its first piece, so every window across the cut is hashed exactly once.  It is record 0, with
+ *                        rec_at 0 and rec_letters counting the carried letters as well
+ *   gn_stream_genome_records  per record (any may be NULL): offset of its header in the text, its letters, and its state --
+ *                        0 hashed, 1 below min_length, 2 kept but with fewer than w letters (not hashed here: the caller takes the
+ *                        letters from its own text, rec_at[r] up to the next record, and hashes them as a whole), 3 open at the end */
+#define GN_GENOME_CONTINUES 1u  /* text[0] continues the record the previous call on this stream left open */
+#define GN_GENOME_OPEN_END  2u  /* the text ends inside its last record (the caller cut at a newline, not at a header) */
+#define GN_GENOME_BAD_LETTER 1
+#define GN_GENOME_NO_HEADER 2
+int gn_stream_upload_genome_text(gn_stream* s, const uint8_t* text, uint64_t n_bytes, uint32_t w, uint32_t stride, uint64_t min_length, uint32_t flags);
+int gn_stream_genome_index(gn_stream* s, uint32_t* n_records, uint32_t* n_pieces, uint64_t* n_bases, uint64_t* parsed_bytes, int* status,
+                           uint64_t* bad_at, uint64_t* open_letters);
+int gn_stream_genome_records(gn_stream* s, uint64_t* rec_at, uint64_t* rec_letters, uint8_t* rec_state);
 int gn_stream_sync(gn_stream* s);
 
 /* Wait for the batch and copy results out.  n_hashes[n_reads], status[n_reads], match_off[n_reads+1]

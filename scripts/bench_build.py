@@ -41,7 +41,15 @@ insert -> .ibf written).  Prints one JSON object.   usage: bench_build.py [n_fil
                   beside "one_pass_hash_bytes", and per part its device bytes, the sets it took and its fill and write seconds
   --hibf-hash-sets MODE  [--hibf] passed on to the hierarchical build (raw | packed | spilled): the run reports "hash_sets", "hashes",
                   "hash_set_bytes" and "united" (the `hibf hash sets:` line); every hierarchical build reports "peak_rss_kb", the
-                  process's largest resident set, and the median run "laps_s", the four laps of every run"""
+                  process's largest resident set, and the median run "laps_s", the four laps of every run
+  --parse MODE    passed on as `--parse MODE` to every build and check (host | device).  A comma list (host,device) builds with every
+                  mode in turn in each round, alternating, one run each to warm up and then --runs (5) each, and prints "parse": per
+                  mode the flat build of the median total (with --hibf the hierarchical build beside it) and "hash_lap_s" / "total_runs_s",
+                  the hash lap and the total of every run as min / median / max; the device builds also report "parse_device", the
+                  files tokenised on the device, those that fell back, those not eligible and the text bytes uploaded
+  --gz            the synthetic genomes are written through Python's gzip (g<i>.fna.gz, level 1: the input side is measured, not
+                  the compressor)"""
+import gzip
 import json
 import math
 import os
@@ -53,8 +61,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hash-sets": "", "--hibf-memory": "", "--hibf-devices": "", "--hibf-hash-sets": ""}
-pos, hibf, check, extend, argv = [], False, False, False, sys.argv[1:]
+opts = {"--runs": "5", "--max-fp": "0.05", "--hash-functions": "4", "--tmax": "", "--layout": "", "--lognormal": "", "--families": "", "--update": "", "--remove": "", "--fold": "", "--device": "", "--device-memory": "", "--hash-sets": "", "--hibf-memory": "", "--hibf-devices": "", "--hibf-hash-sets": "", "--parse": ""}
+pos, hibf, check, extend, gz, argv = [], False, False, False, False, sys.argv[1:]
 while argv:
     a = argv.pop(0)
     if a == "--hibf":
@@ -63,6 +71,8 @@ while argv:
         extend = True
     elif a == "--verify":
         check = True
+    elif a == "--gz":
+        gz = True
     elif a in opts:
         opts[a] = argv.pop(0)
     else:
@@ -100,8 +110,8 @@ with open(os.path.join(d, "in.tsv"), "w") as tsv:
             body.reshape(-1)[np.arange(L) + np.arange(L) // cols] = lut[ranks]
         else:
             body[:, :cols] = lut[rng.integers(0, 4, size=(rows, cols), dtype=np.uint8)]
-        f = os.path.join(d, f"g{i}.fna")
-        with open(f, "wb") as o:
+        f = os.path.join(d, f"g{i}.fna" + (".gz" if gz else ""))
+        with (gzip.open(f, "wb", compresslevel=1) if gz else open(f, "wb")) as o:
             o.write(f">genome{i} synthetic\n".encode())
             o.write(body.tobytes()[: L + L // cols + 1])
         tsv.write(f"{f}\tT{i}\n")
@@ -117,14 +127,29 @@ device_flat = (["--device", opts["--device"]] if opts["--device"] else []) + (["
 device_hibf = ["--device", opts["--device"]] if opts["--device"] else []
 parts_hibf = (["--hibf-memory", opts["--hibf-memory"]] if opts["--hibf-memory"] else []) + (["--hibf-devices", opts["--hibf-devices"]] if opts["--hibf-devices"] else [])
 sets_hibf = ["--hibf-hash-sets", opts["--hibf-hash-sets"]] if opts["--hibf-hash-sets"] else []
+parse_modes = [m for m in opts["--parse"].split(",") if m]
+parse_mode = parse_modes[0] if len(parse_modes) == 1 else ""  # (a list: set in turn by the rounds at the end)
+if gz:
+    out["gz"] = True
+
+
+def parse_extra():
+    return ["--parse", parse_mode] if parse_mode else []
+
+
+def parse_counters(stderr, res):
+    m = re.search(r"^parse device: (\d+) files tokenised on the device, (\d+) fell back to the host reader, (\d+) not eligible, (\d+) text bytes uploaded", stderr, re.M)
+    if m:
+        res["parse_device"] = dict(zip(("device", "fell_back", "not_eligible", "text_bytes"), (int(x) for x in m.groups())))
 
 
 def flat_run(max_fp="0.05", extra=()):
     res = {}
     t0 = time.time()
-    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", max_fp] + list(extra) + device_flat,
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "-o", os.path.join(d, "db.ibf"), "-t", str(threads), "--verbose", "-p", max_fp] + list(extra) + device_flat + parse_extra(),
                        capture_output=True, text=True)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    parse_counters(p.stderr, res)
     m = re.search(r"filled in (\d+) pass(?:es)? over the hash sets, (\d+) hash bytes uploaded", p.stderr)
     if m:
         res["passes"], res["hash_bytes_uploaded"] = int(m.group(1)), int(m.group(2))
@@ -173,9 +198,10 @@ def hibf_run(layout="", tsv="in.tsv", db="db.hibf"):
     res = {}
     t0 = time.time()
     cmd = [exe, "-i", os.path.join(d, tsv), "-o", os.path.join(d, db), "-t", str(threads), "--verbose", "-p", opts["--max-fp"],
-           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf + (parts_hibf if db == "db.hibf" else []) + sets_hibf
+           "-s", opts["--hash-functions"], "--hibf"] + (["--tmax", opts["--tmax"]] if opts["--tmax"] else []) + (["--layout", layout] if layout else []) + device_hibf + (parts_hibf if db == "db.hibf" else []) + sets_hibf + parse_extra()
     p = run_with_rusage(cmd, res)
     res["rc"], res["wall_s"] = p.returncode, round(time.time() - t0, 2)
+    parse_counters(p.stderr, res)
     m = re.search(r"^hibf hash sets: (\d+) hashes held (\w+) in (\d+) bytes, (\d+) targets united$", p.stderr, re.M)
     if m:
         res["hashes"], res["hash_sets"], res["hash_set_bytes"], res["united"] = int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4))
@@ -225,7 +251,7 @@ def update_run(layout, m):
     open(os.path.join(d, "new.tsv"), "w").writelines(lines[-m:])
     res = {"base": hibf_run(layout, "old.tsv", "old.hibf")}
     cmd = [exe, "-i", os.path.join(d, "new.tsv"), "--hibf", "--update", os.path.join(d, "old.hibf"), "-o", os.path.join(d, "upd.hibf"), "-t", str(threads),
-           "--verbose"] + (["--extend"] if extend else [])
+           "--verbose"] + (["--extend"] if extend else []) + parse_extra()
     n_remove = int(opts["--remove"] or 0)
     lap = r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) count ([0-9.eE+-]+) plan ([0-9.eE+-]+) copy ([0-9.eE+-]+) emplace ([0-9.eE+-]+) write ([0-9.eE+-]+)"
     lap_keys = ("hash_s", "load_s", "count_s", "plan_s", "copy_s", "emplace_s", "write_s")
@@ -288,7 +314,7 @@ def verify_run(db="db.hibf"):
     """an index just written against all the inputs"""
     res = {}
     t0 = time.time()
-    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "--hibf", "--verify-index", os.path.join(d, db), "-t", str(threads), "--verbose"],
+    p = subprocess.run([exe, "-i", os.path.join(d, "in.tsv"), "--hibf", "--verify-index", os.path.join(d, db), "-t", str(threads), "--verbose"] + parse_extra(),
                        capture_output=True, text=True)
     res["verify_rc"], res["verify_wall_s"] = p.returncode, round(time.time() - t0, 2)
     m = re.search(r" - seconds: hash ([0-9.eE+-]+) load ([0-9.eE+-]+) membership ([0-9.eE+-]+) fp ([0-9.eE+-]+)", p.stderr)
@@ -317,7 +343,28 @@ def median_of(runs):
     return mid
 
 
-if not hibf:
+if len(parse_modes) > 1:  # every mode in turn in each round; the hash lap and the total of every run
+    flat_extra = ["-s", opts["--hash-functions"]]
+    layout = opts["--layout"].split(",")[0]
+    runs = {m: {"flat": [], "hibf": []} for m in parse_modes}
+    for r in range(int(opts["--runs"]) + 1):  # (round 0 warms up)
+        for parse_mode in parse_modes:
+            one = {"flat": flat_run(opts["--max-fp"], flat_extra)}
+            if hibf:
+                one["hibf"] = hibf_run(layout)
+            for kind, res in one.items():
+                if r:
+                    runs[parse_mode][kind].append(res)
+    out["max_fp"], out["hash_functions"], out["runs"], out["parse"] = float(opts["--max-fp"]), int(opts["--hash-functions"]), int(opts["--runs"]), {}
+    for m in parse_modes:
+        out["parse"][m] = {}
+        for kind, lap in (("flat", "count_hashes_s"), ("hibf", "hash_s")):
+            if runs[m][kind]:
+                mid = median_of(runs[m][kind])
+                mid["hash_lap_s"] = spread([x[lap] for x in runs[m][kind] if lap in x])
+                mid["total_runs_s"] = spread([x.get("total_s", x["wall_s"]) for x in runs[m][kind]])
+                out["parse"][m][kind] = mid
+elif not hibf:
     out.update(flat_run())
 elif opts["--update"]:
     out["max_fp"], out["hash_functions"], out["updated_with"] = float(opts["--max-fp"]), int(opts["--hash-functions"]), int(opts["--update"])
