@@ -40,6 +40,7 @@ extern "C" const char* gn_last_error(void)
 
 // ---- switches: $GANON_HIP_ABLATE, parsed once at load; gn_ablate() for in-process cross-checks (gn_internal.h) ----------------
 static GnSwitches g_sw;
+static uint64_t   g_stream_rows_min = GN_STREAM_ROWS_MIN_BYTES;
 
 static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_t bad_len)
 {
@@ -48,7 +49,7 @@ static int gn_parse_switches(const char* list, GnSwitches* out, char* bad, size_
     {
         const char* name;
         bool GnSwitches::* flag;
-    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"lean_screen", &GnSwitches::lean_screen},     {"stray_masks", &GnSwitches::stray_masks},     {"cand_select", &GnSwitches::cand_select},
+    } static const flags[] = {{"early_exit", &GnSwitches::early_exit},       {"row_screen", &GnSwitches::row_screen},       {"lean_screen", &GnSwitches::lean_screen},     {"stray_masks", &GnSwitches::stray_masks},     {"stream_rows", &GnSwitches::stream_rows},     {"cand_select", &GnSwitches::cand_select},
                               {"csr_identity", &GnSwitches::csr_identity},   {"uniform_select", &GnSwitches::uniform_select},
                               {"run_select", &GnSwitches::run_select},       {"max_first", &GnSwitches::max_first},
                               {"const_nb", &GnSwitches::const_nb},           {"split_kernel", &GnSwitches::split_kernel},
@@ -102,6 +103,15 @@ struct GnSwitchesInit
         char bad[64];
         if (gn_parse_switches(getenv("GANON_HIP_ABLATE"), &g_sw, bad, sizeof(bad)) != GN_OK)
             fprintf(stderr, "libganon_hip: $GANON_HIP_ABLATE names an unknown switch '%s' -- the whole list is ignored\n", bad);
+        if (const char* v = getenv("GANON_HIP_STREAM_ROWS_MIN_BYTES"))
+        {
+            char*                    end = nullptr;
+            const unsigned long long n   = strtoull(v, &end, 10);
+            if (end != v && *end == 0)
+                g_stream_rows_min = n;
+            else
+                fprintf(stderr, "libganon_hip: $GANON_HIP_STREAM_ROWS_MIN_BYTES is not a number of bytes ('%.60s') -- ignored\n", v);
+        }
     }
 } g_sw_init;
 } // namespace
@@ -109,6 +119,11 @@ struct GnSwitchesInit
 const GnSwitches& gn_sw()
 {
     return g_sw;
+}
+
+uint64_t gn_stream_rows_min_default()
+{
+    return g_stream_rows_min;
 }
 
 extern "C" int gn_ablate(const char* list)
@@ -1269,6 +1284,8 @@ __global__ void gn_fake_count_kernel(gn_match* matches, uint64_t* seg_begin, uin
 // count + select over reads [lo, hi) on the stream's main HIP stream (the match cursor is NOT reset here)
 static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
 {
+    if (lo == 0)
+        s->rows_streamed = false; // (set where the fast launch is made)
     gn_filter* f = s->f;
     GnCountParams p{};
     p.rows       = f->ibf.d_rows;
@@ -1392,7 +1409,14 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
                 // a grid for twice the last batch's list (four units a block)
                 p.max_blocks_list = (uint32_t)std::min<uint64_t>(p.max_blocks_list, std::max<uint64_t>((uint64_t)f->n_cu, s->prev_unit_deferred / 2 + 1));
         }
-        GN_HIP(gn_launch_count_fast(p, f->geom, f->ibf.h, s->st));
+        GnRowPolicy pol; // (gn_row_policy.h: non-temporal row loads for a filter far past the caches)
+        pol.flat       = !f->is_hibf;
+        pol.plain_only = gn_sw().stream_rows;
+        pol.row_bytes  = f->ibf.S * f->ibf.W * 8ull;
+        pol.min_bytes  = f->stream_rows_min_bytes;
+        bool streamed  = false;
+        GN_HIP(gn_launch_count_fast(p, f->geom, f->ibf.h, pol, s->st, &streamed));
+        s->rows_streamed = s->rows_streamed || streamed;
         p.unit_list_out = nullptr;
         p.grab       = nullptr; // (the generic kernel that takes the deferred reads hands out its rounds as before)
         p.work_list  = s->d_deferred;
@@ -1415,6 +1439,7 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
 static int gn_run_count(gn_stream* s)
 {
     GN_HIP(hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), s->st)); // cursor
+    s->rows_streamed = false;
     if (s->f->is_hibf)
         return gn_hibf_classify(s, s->f, s->st);
     return gn_run_count_range(s, 0, s->n_reads);
@@ -2020,6 +2045,22 @@ extern "C" int gn_stream_timings(gn_stream* s, gn_timings* t)
     if (s->cmp_timed && hipEventSynchronize(s->ev_cmp[1]) == hipSuccess)
         hipEventElapsedTime(&tm.ms_compact, s->ev_cmp[0], s->ev_cmp[1]);
     *t = tm;
+    return GN_OK;
+}
+
+extern "C" int gn_filter_set_stream_rows_min_bytes(gn_filter* f, uint64_t bytes)
+{
+    if (!f)
+        return gn_fail(GN_EINVAL, "null argument");
+    f->stream_rows_min_bytes = bytes;
+    return GN_OK;
+}
+
+extern "C" int gn_stream_rows_streamed(gn_stream* s, int* streamed)
+{
+    if (!s || !streamed)
+        return gn_fail(GN_EINVAL, "null argument");
+    *streamed = s->rows_streamed ? 1 : 0;
     return GN_OK;
 }
 

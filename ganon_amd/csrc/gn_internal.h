@@ -11,6 +11,7 @@
 #include "../../include/ganon_ibf_hash.h"
 #include "gn_devmem.h"
 #include "gn_packed_set.h"
+#include "gn_row_policy.h"
 
 #define GN_MAX_CHUNKS 64 // pipeline chunks per batch (minimiser on the side stream || count on the main stream)
 // candidate-driven select of the generic count kernel: targets with more bins than this are scanned from a list
@@ -25,7 +26,8 @@
 
 // ---- switches ---------------------------------------------------------------------------------
 // The ONE place the library reads its environment: $GANON_HIP_ABLATE, a comma list of the names below, parsed once when
-// the library is loaded into this struct (gn_capi.hip).  Everything is off by default = the product path.  Tests and
+// the library is loaded into this struct (gn_capi.hip) -- and, in the same place, $GANON_HIP_STREAM_ROWS_MIN_BYTES, the default of
+// gn_filter::stream_rows_min_bytes.  Everything is off by default = the product path.  Tests and
 // bench.py cross-check a fast path against the path it replaces by switching it off in-process with gn_ablate()
 // (include/ganon_hip.h); nothing else changes the struct, and no launch path calls getenv().
 struct GnSwitches
@@ -34,6 +36,7 @@ struct GnSwitches
     bool early_exit = false;      // fast kernel: fetch every row (no exact early exit)
     bool row_screen = false;      // fast kernel: no two-row screen in front of the exit (every read takes the unscreened flow)
     bool lean_screen = false;     // fast kernel: no screen-only kernel + launch over its list (the screening instance takes every unit, one launch)
+    bool stream_rows = false;     // fast kernel: plain row loads everywhere (no stream kernels with non-temporal row loads on filters past the caches: gn_row_policy.h)
     bool stray_masks = false;     // fast kernel: the finish probes a bin on rows 2 and 3 of every screened hash at once (2 ds words; no stage on the hashes known to have hit)
     bool cand_select = false;     // generic kernel: scan every target instead of the candidate-driven select
     bool csr_identity = false;    // split-bin kernel family: treat an ordered CSR map as a general one
@@ -69,6 +72,7 @@ struct GnSwitches
                                   // step costs next to nothing and what is left is what the host's reader, workers and post stage sustain
 };
 const GnSwitches& gn_sw();
+uint64_t          gn_stream_rows_min_default(); // GN_STREAM_ROWS_MIN_BYTES, or what $GANON_HIP_STREAM_ROWS_MIN_BYTES held when the library was loaded
 struct gn_stream;
 int             gn_result_compact(gn_stream* s);  // gn_capi.hip: the contiguous copy of a segmented result, queued on the stream (no-op otherwise)
 const gn_match* gn_result_matches(gn_stream* s);  // the batch's final matches, contiguous by read (after gn_result_compact / the pre-pass)
@@ -205,7 +209,8 @@ uint32_t gn_count_lds_index(const GnCountGeometry& g, uint32_t b);
 
 hipError_t gn_launch_minimiser(const GnMinimiserParams& p, int n_cu, hipStream_t st);
 hipError_t gn_launch_count(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st);
-hipError_t gn_launch_count_fast(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st);
+// (pol: gn_row_policy.h; *streamed: whether the launch took the stream kernels, i.e. non-temporal row loads)
+hipError_t gn_launch_count_fast(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, const GnRowPolicy& pol, hipStream_t st, bool* streamed);
 // split-bin maps, reads with <= 127 minimisers, rows of at least one wave (gn_split.hip)
 hipError_t gn_launch_count_long(const GnCountParams& p, uint32_t hash_funs, uint32_t* list, unsigned long long* count, uint32_t* scratch,
                                 uint32_t blocks, hipStream_t st);
@@ -303,6 +308,7 @@ struct gn_filter
     uint32_t        n_big      = 0;
     GnDev<uint32_t> d_sl_nbr;   // split kernel (GnCountParams::sl_nbr); nullptr = not applicable
     uint32_t        split_bpc  = 0;       // split kernel: resident blocks per CU
+    uint64_t        stream_rows_min_bytes = gn_stream_rows_min_default(); // row storage from which a launch takes the stream kernels (gn_row_policy.h)
     uint32_t        n_targets  = 0;
     bool            identity   = false;
     uint32_t        uniform_nb = 0;       // see GnCountParams::uniform_nb
@@ -537,6 +543,7 @@ struct gn_stream
     // reads the previous batch left to the deferred launches (count stage, minimiser stage): their lists are usually empty and a
     // chip-filling persistent grid that finds nothing costs 0.1-0.2 ms per launch; ~0: unknown
     uint64_t prev_count_deferred = ~0ull, prev_min_deferred = ~0ull, prev_unit_deferred = ~0ull;
+    bool     rows_streamed = false; // the last classify's fast launches took the stream kernels (gn_stream_rows_streamed)
     uint32_t k = 0, w = 0;
     double   rel_cutoff = 0;
     uint64_t n_matches = 0;

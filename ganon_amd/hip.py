@@ -24,7 +24,7 @@ ABI_SYMBOLS = ["gn_device_count", "gn_last_error", "gn_filter_upload_ibf", "gn_f
                "gn_stream_upload_reads", "gn_stream_minimisers", "gn_stream_classify", "gn_submit_batch", "gn_stream_sync", "gn_fetch_batch", "gn_stream_set_postfilter",
                "gn_fetch_postfilter", "gn_streams_postfilter_joint", "gn_stream_set_long_reads", "gn_stream_device_matches",
                "gn_stream_distinct_hashes", "gn_filter_emplace_split", "gn_stream_fetch_hashes", "gn_stream_dense_counts",
-               "gn_stream_timings", "gn_stream_screen_deferred", "gn_gather_create", "gn_gather_create_merged", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
+               "gn_stream_timings", "gn_stream_screen_deferred", "gn_filter_set_stream_rows_min_bytes", "gn_stream_rows_streamed", "gn_gather_create", "gn_gather_create_merged", "gn_gather_run", "gn_gather_fetch", "gn_gather_device_matches",
                "gn_gather_destroy", "gn_device_memory", "gn_hibf_row_stride_words", "gn_gather_run_buffers", "gn_stream_device_offsets", "gn_stream_hibf_levels", "gn_stream_hibf_level_lines", "gn_stream_classify_shared",
                "gn_stream_upload_fastq", "gn_stream_fastq_index", "gn_stream_fastq_keep", "gn_stream_fastq_records",
                "gn_peer_stats", "gn_stream_upload_text", "gn_stream_upload_text_pair", "gn_stream_text_pair_index", "gn_stream_text_pair_records2",
@@ -198,6 +198,8 @@ def load_library():
     L.gn_stream_dense_counts.argtypes = [vp, u32, u32, vp]
     L.gn_stream_timings.argtypes = [vp, C.POINTER(Timings)]
     L.gn_stream_screen_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.gn_filter_set_stream_rows_min_bytes.argtypes = [vp, u64]
+    L.gn_stream_rows_streamed.argtypes = [vp, C.POINTER(C.c_int)]
     L.gn_gather_create.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
     L.gn_gather_create_merged.argtypes = [i32, u32, C.POINTER(vp), vp, C.POINTER(vp)]
     L.gn_gather_run.argtypes = [vp, C.POINTER(vp), u32]
@@ -925,6 +927,11 @@ class HipFilter:
         _check(load_library().gn_filter_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(is_hibf=bool(a.value), n_ibf=b.value, n_targets=c.value, device_bytes=d.value)
 
+    def set_stream_rows_min_bytes(self, n_bytes: int) -> None:
+        """row storage from which this filter's fast count launches take the stream kernels, non-temporal row loads
+        (gn_filter_set_stream_rows_min_bytes; default 2 GiB or $GANON_HIP_STREAM_ROWS_MIN_BYTES, 0 = whenever an instance exists)"""
+        _check(load_library().gn_filter_set_stream_rows_min_bytes(self._h, int(n_bytes)))
+
     def free(self) -> None:
         if self._h:
             load_library().gn_filter_free(self._h)
@@ -1186,6 +1193,12 @@ class HipStream:
         n = C.c_uint64(0)
         _check(load_library().gn_stream_screen_deferred(self._h, C.byref(n)))
         return int(n.value)
+
+    def rows_streamed(self) -> bool:
+        """whether the fast count launches of the last classify took the stream kernels: non-temporal row loads (gn_stream_rows_streamed)"""
+        v = C.c_int(0)
+        _check(load_library().gn_stream_rows_streamed(self._h, C.byref(v)))
+        return bool(v.value)
 
     def hibf_levels(self):
         """per tree level of the last HIBF batch: [dict(ms, algo_bytes, table_bytes, row_bytes, line_bytes)] (gn_stream_hibf_levels / _level_lines)"""

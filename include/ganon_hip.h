@@ -383,9 +383,10 @@ int gn_gather_destroy(gn_gather* g);
 int gn_peer_stats(int dst, int src, int* state, uint64_t* bytes);
 
 /* Switches (test and measurement hook; no counterpart in the reference).  The library reads its environment in ONE place:
- * $GANON_HIP_ABLATE, a comma list parsed once when the library is loaded.  gn_ablate() replaces that list in-process so a
+ * $GANON_HIP_ABLATE, a comma list parsed once when the library is loaded (and, there too, $GANON_HIP_STREAM_ROWS_MIN_BYTES:
+ * gn_filter_set_stream_rows_min_bytes).  gn_ablate() replaces that list in-process so a
  * test can cross-check a fast path against the path it replaces (NULL or "" = the product path).  Call it only while no
- * launch is in flight.  Names that switch a path OFF: early_exit row_screen lean_screen stray_masks cand_select csr_identity uniform_select run_select
+ * launch is in flight.  Names that switch a path OFF: early_exit row_screen lean_screen stray_masks stream_rows cand_select csr_identity uniform_select run_select
  * max_first const_nb split_kernel predrop deferred_grids hibf_reg hibf_pack hibf_one_pack; test set-ups:
  * pinned_malloc gather_copy joint_apart inflate_ahead on_demand hibf_dense_rows chunk=N hibf_pair_limit=N; runtime: sync=spin|yield|block debug; measurement with WRONG results: fake_count (flat IBF: the count +
  * select kernels are not run, every second read gets one made-up match -- what is left is what the host around the device sustains).  Unknown name -> GN_EINVAL and
@@ -720,6 +721,14 @@ int gn_stream_timings(gn_stream* s, gn_timings* t);
 /* Flat IBF: units (read x column slice) of the last batch that the fast count kernel's screen-only launch left to the launch that
  * follows it -- reads without a screen in the launch's table, aborted screens.  0 where that kernel does not run. */
 int gn_stream_screen_deferred(gn_stream* s, uint64_t* units);
+/* Flat IBF, four hash functions: from `bytes` of row storage on, a filter's fast count launches take the stream kernels -- the same
+ * kernels with non-temporal row loads, for a filter far past the caches, whose lines are read once (csrc/gn_row_policy.h).  Default:
+ * 2 GiB, or $GANON_HIP_STREAM_ROWS_MIN_BYTES as it was when the library was loaded; 0 = every launch that has a stream instance.
+ * Results and the bytes requested do not depend on it.  Call it while no launch on the filter is in flight. */
+int gn_filter_set_stream_rows_min_bytes(gn_filter* f, uint64_t bytes);
+/* *streamed = 1 when the fast count launches of the last classify took the stream kernels, else 0 (plain row loads: a small filter,
+ * an HIBF, a shape without a stream instance, the switch stream_rows). */
+int gn_stream_rows_streamed(gn_stream* s, int* streamed);
 /* HIBF only: the last batch per tree level (level 0 = the top IBF) -- duration of the level's kernels, algorithmic row
  * bytes of the level (they add up to gn_timings.algo_bytes), bytes of the IBFs at that depth and their usual row width.
  * A level whose tables fit the 256 MiB Infinity Cache is not bound by HBM; the roofline is stated per level for that

@@ -9,13 +9,15 @@
 //     counter can be calibrated against the algorithmic bytes for this access pattern.
 //
 //   hipcc --offload-arch=gfx950 -O3 -o scripts/calib_gather scripts/calib_gather.hip
-//   scripts/calib_gather <table MiB> <row bytes: 8|16|32|64|128|256|512> <row requests (millions)> [loads in flight per lane = 8] [blocks per CU = 8]
-// prints one JSON line.
+//   scripts/calib_gather <table MiB> <row bytes: 8|16|32|64|128|256|512> <row requests (millions)> [loads in flight per lane = 8] [blocks per CU = 8] [policy: plain|nt = plain]
+// prints one JSON line.  policy = the cache policy of the row load, the only difference between the two kernels: `nt` is a
+// non-temporal load (global_load_dwordx2 ... nt), for rows that are read once (profiles/calib_gather_policy.json).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define CK(x)                                                                                         \
     do                                                                                                \
@@ -43,7 +45,7 @@ __global__ void fill_kernel(uint64_t* t, uint64_t n)
 
 // A group of LPR lanes (8 bytes each) fetches one row per request; a wave issues 64/LPR different rows per load instruction.
 // Every lane keeps U loads in flight (U independent row indices per trip).
-template <int LPR, int U>
+template <int LPR, int U, bool NT>
 __global__ __launch_bounds__(256) void gather_kernel(const uint64_t* __restrict__ table, uint64_t n_rows, uint64_t trips, uint64_t seed,
                                                      uint64_t* __restrict__ sink)
 {
@@ -59,7 +61,10 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint64_t* __restrict_
         {
             const uint64_t x   = mix64(seed + (group * trips + it) * U + u);
             const uint64_t row = (uint64_t)(((unsigned __int128)x * n_rows) >> 64);
-            v[u]               = table[row * LPR + sub];
+            if constexpr (NT)
+                v[u] = __builtin_nontemporal_load(table + (row * LPR + sub));
+            else
+                v[u] = table[row * LPR + sub];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -69,10 +74,10 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint64_t* __restrict_
         sink[0] = acc;
 }
 
-template <int LPR>
+template <int LPR, bool NT>
 static int run(int U, const uint64_t* table, uint64_t n_rows, uint64_t trips, uint64_t* sink, unsigned blocks, hipStream_t st)
 {
-#define LAUNCH(UU) hipLaunchKernelGGL((gather_kernel<LPR, UU>), dim3(blocks), dim3(256), 0, st, table, n_rows, trips, 42ull, sink)
+#define LAUNCH(UU) hipLaunchKernelGGL((gather_kernel<LPR, UU, NT>), dim3(blocks), dim3(256), 0, st, table, n_rows, trips, 42ull, sink)
     switch (U)
     {
         case 1: LAUNCH(1); break;
@@ -92,7 +97,7 @@ int main(int argc, char** argv)
 {
     if (argc < 4)
     {
-        fprintf(stderr, "usage: %s <table MiB> <row bytes> <row requests, millions> [loads in flight] [blocks per CU]\n", argv[0]);
+        fprintf(stderr, "usage: %s <table MiB> <row bytes> <row requests, millions> [loads in flight] [blocks per CU] [plain|nt]\n", argv[0]);
         return 2;
     }
     const uint64_t table_bytes = (uint64_t)atoll(argv[1]) << 20;
@@ -100,6 +105,13 @@ int main(int argc, char** argv)
     const uint64_t want        = (uint64_t)(atof(argv[3]) * 1e6);
     const int      U           = argc > 4 ? atoi(argv[4]) : 8;
     const int      bpc         = argc > 5 ? atoi(argv[5]) : 8;
+    const char*    policy      = argc > 6 ? argv[6] : "plain";
+    const bool     nt          = strcmp(policy, "nt") == 0;
+    if (!nt && strcmp(policy, "plain") != 0)
+    {
+        fprintf(stderr, "policy: plain nt\n");
+        return 2;
+    }
     const int      lpr         = row_bytes / 8;
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
@@ -126,13 +138,13 @@ int main(int argc, char** argv)
         int rc = 1;
         switch (lpr)
         {
-            case 1: rc = run<1>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 2: rc = run<2>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 4: rc = run<4>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 8: rc = run<8>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 16: rc = run<16>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 32: rc = run<32>(U, table, n_rows, trips, sink, blocks, st); break;
-            case 64: rc = run<64>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 1: rc = nt ? run<1, true>(U, table, n_rows, trips, sink, blocks, st) : run<1, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 2: rc = nt ? run<2, true>(U, table, n_rows, trips, sink, blocks, st) : run<2, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 4: rc = nt ? run<4, true>(U, table, n_rows, trips, sink, blocks, st) : run<4, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 8: rc = nt ? run<8, true>(U, table, n_rows, trips, sink, blocks, st) : run<8, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 16: rc = nt ? run<16, true>(U, table, n_rows, trips, sink, blocks, st) : run<16, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 32: rc = nt ? run<32, true>(U, table, n_rows, trips, sink, blocks, st) : run<32, false>(U, table, n_rows, trips, sink, blocks, st); break;
+            case 64: rc = nt ? run<64, true>(U, table, n_rows, trips, sink, blocks, st) : run<64, false>(U, table, n_rows, trips, sink, blocks, st); break;
             default: fprintf(stderr, "row bytes: 8 16 32 64 128 256 512\n");
         }
         if (rc)
@@ -149,10 +161,10 @@ int main(int argc, char** argv)
         }
     }
     const double bytes = (double)n_req * row_bytes;
-    printf("{\"table_mib\": %llu, \"row_bytes\": %d, \"row_requests_per_launch\": %llu, \"algorithmic_bytes_per_launch\": %.0f, "
+    printf("{\"table_mib\": %llu, \"row_bytes\": %d, \"policy\": \"%s\", \"row_requests_per_launch\": %llu, \"algorithmic_bytes_per_launch\": %.0f, "
            "\"loads_in_flight_per_lane\": %d, \"blocks_per_cu\": %d, \"timed_launches\": %d, \"launches_total\": %d, \"ms_avg\": %.4f, "
            "\"ms_best\": %.4f, \"algorithmic_gbs\": %.1f, \"line128_gbs\": %.1f}\n",
-           (unsigned long long)(table_bytes >> 20), row_bytes, (unsigned long long)n_req, bytes, U, bpc, reps, reps + 1, sum / reps, best,
+           (unsigned long long)(table_bytes >> 20), row_bytes, policy, (unsigned long long)n_req, bytes, U, bpc, reps, reps + 1, sum / reps, best,
            bytes / (sum / reps) / 1e6, (double)n_req * (row_bytes < 128 ? 128 : row_bytes) / (sum / reps) / 1e6);
     return 0;
 }
