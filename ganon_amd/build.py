@@ -25,7 +25,7 @@ BUILD_SHARED = ("seq_io.cpp", "pgzip.cpp", "filter_io.cpp")  # what ganon-build 
 REASSIGN_ONLY = ("reassign.cpp", "reassign_main.cpp")  # ganon-reassign (the EM over .all)
 
 HIP_SOURCES = ["gn_kernels.hip", "gn_split.hip", "gn_minimiser_lpr.hip", "gn_hibf.hip", "gn_postfilter.hip", "gn_build.hip", "gn_build_hibf.hip", "gn_build_sketch.hip", "gn_gather.hip", "gn_fastq.hip", "gn_genome.hip", "gn_reassign.hip", "gn_inflate.hip", "gn_capi.hip"]
-HIP_HEADERS = ["gn_internal.h", "gn_devmem.h", "gn_scan.h", "gn_build_row.h", "gn_bin_spans.h", "gn_fold_table.h", "gn_screen_table.h", "gn_stray_probe.h", "gn_row_policy.h", "gn_count_fast_body.inc", "gn_count_lean_body.inc", "gn_emplace_window.h", "gn_packed_set.h", "gn_path_window.h", os.path.join(ROOT, "include", "ganon_hip.h"), os.path.join(ROOT, "include", "ganon_ibf_hash.h")]
+HIP_HEADERS = ["gn_internal.h", "gn_devmem.h", "gn_scan.h", "gn_build_row.h", "gn_bin_spans.h", "gn_fold_table.h", "gn_screen_table.h", "gn_stray_probe.h", "gn_row_policy.h", "gn_count_plan.h", "gn_count_fast_body.inc", "gn_count_lean_body.inc", "gn_emplace_window.h", "gn_packed_set.h", "gn_path_window.h", os.path.join(ROOT, "include", "ganon_hip.h"), os.path.join(ROOT, "include", "ganon_ibf_hash.h")]
 
 
 def _hipcc() -> str:

@@ -1281,29 +1281,19 @@ __global__ void gn_fake_count_kernel(gn_match* matches, uint64_t* seg_begin, uin
         atomicMax(cursor, (unsigned long long)((hi + 1) >> 1));
 }
 
-// count + select over reads [lo, hi) on the stream's main HIP stream (the match cursor is NOT reset here)
-static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
+// the filter and batch fields of a count launch over reads [lo, hi): what every count kernel reads, the dense tap's launch included
+static void gn_count_fill(GnCountParams& p, const gn_stream* s, uint32_t lo, uint32_t hi)
 {
-    if (lo == 0)
-        s->rows_streamed = false; // (set where the fast launch is made)
-    gn_filter* f = s->f;
-    GnCountParams p{};
+    const gn_filter* f = s->f;
     p.rows       = f->ibf.d_rows;
     p.S          = f->ibf.S;
     p.W          = (uint32_t)f->ibf.W;
     p.B          = (uint32_t)f->ibf.B;
     p.shift      = f->ibf.shift;
-    p.tgt_off    = f->identity ? nullptr : f->d_tgt_off;
+    p.tgt_off    = f->identity ? nullptr : f->d_tgt_off.get();
     p.tgt_bins   = f->d_tgt_bins;
     p.tgt_lds    = f->d_tgt_lds;
     p.tgt_rec    = f->d_tgt_rec;
-    p.bin_tgt    = f->d_bin_tgt;
-    p.bin_nb2    = gn_sw().cand_select ? nullptr : f->d_bin_nb2;
-    p.nbtab_off  = (uint32_t)f->geom.nbtab_off;
-    p.candcnt_off = (uint32_t)f->geom.candcnt_off;
-    p.big_list   = f->d_big_list;
-    p.n_big      = f->n_big;
-    p.tgt_ids    = nullptr;
     p.n_targets  = f->n_targets;
     p.hashes     = s->v_hashes;
     p.slot_off   = s->v_slot_off;
@@ -1312,125 +1302,129 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
     p.n_reads    = hi;
     p.read_begin = lo;
     p.rel_cutoff = s->rel_cutoff;
-    if (gn_sw().fake_count)
-    {
-        if (lo == 0)
-            s->pf_predrop = false; // (every match is "written": a pre-pass judges them like any others)
-        if ((uint64_t)(hi + 1) / 2 <= s->match_cap && hi > lo)
-            hipLaunchKernelGGL(gn_fake_count_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, s->st, s->d_matches, s->d_seg_begin, s->d_seg_count,
-                               s->v_status, s->v_nh, lo, hi, (uint32_t)f->geom.wpr, f->n_targets ? f->n_targets : 1u, s->d_ctr);
-        GN_HIP(hipGetLastError());
-        return GN_OK;
-    }
     p.wpr        = f->geom.wpr;
     p.gp_log2    = f->geom.gp_log2;
     p.slice_dwords = f->geom.slice_dwords;
     p.matches    = s->d_matches;
-    p.match_cap  = s->match_cap;
-    p.cursor     = s->d_ctr;
-    p.seg_begin  = s->d_seg_begin;
-    p.seg_count  = s->d_seg_count;
-    p.dense      = nullptr;
-    p.max_blocks = (uint32_t)f->n_cu * 16u;
-    // persistent grid = a whole number of resident rounds: 8-byte-lane variant holds 4 blocks per CU, 16-byte one 3
-    p.max_blocks_fast = (uint32_t)f->n_cu * (f->geom.lw == 1 ? 8u : 6u);
-    p.max_blocks_lean = (uint32_t)f->n_cu * 10u; // (the screen-only kernel holds 5 blocks per CU)
-    p.max_blocks_list = p.max_blocks_fast;
-    p.emit_probe = gn_sw().emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
-    p.early_exit = gn_sw().early_exit ? 0u : 1u; // (bench.py's every-row measurement and the parity tests of the exit)
-    p.skip_ctr   = s->d_ctr + 7;
-    p.probe_hashes = gn_sw().stray_masks ? 0u : GN_PROBE_HASHES; // (0: the finish's one-stage probe, for the A/B and the parity tests)
-    if (f->identity && p.early_exit && !gn_sw().row_screen && (f->geom.lw == 1 || p.W > 128)) // (the instances that screen: gn_launch_fast_one)
-    {
-        // per launch: how many hashes a read of n minimisers is screened on with two of its rows (gn_screen_table.h; all zero = the flow
-        // without a screen, which is also what "every row" needs)
-        uint8_t ds[GN_SCREEN_NMAX + 1];
-        gn_screen_table(p.rel_cutoff, f->ibf.h, (uint32_t)std::min<uint64_t>(f->ibf.W, 64u * f->geom.lw) * 64u, ds);
-        memcpy(p.screen, ds, sizeof(p.screen));
-    }
-    if (lo == 0) // (a re-run after a match-buffer regrow starts the tally again)
-        GN_HIP(hipMemsetAsync(s->d_ctr + 7, 0, sizeof(unsigned long long), s->st));
-    p.sl_nbr = f->d_sl_nbr;
-    p.csr_identity = f->csr_identity && !gn_sw().csr_identity ? 1u : 0u;
-    p.uniform_nb   = p.csr_identity && !gn_sw().uniform_select ? f->uniform_nb : 0u;
-    p.run_select   = p.csr_identity && f->run_ok && !p.uniform_nb && !gn_sw().run_select ? 1u : 0u;
-    p.max_first    = gn_sw().max_first ? 0u : 1u;
-    p.const_nb     = p.uniform_nb && !gn_sw().const_nb ? p.uniform_nb : (p.run_select ? 4u : 0u);
-    const bool split = !f->identity && f->d_sl_nbr != nullptr && !gn_sw().split_kernel;
-    const bool fast = f->identity;
-    // with a filter_matches pre-pass on the stream the fast and the split-bin kernel do not write matches the --rel-filter rule is bound to
-    // drop (not for a merging level: there the minimum follows the entries that got in, which only the merge knows)
-    const bool predrop = (fast || split) && s->pf_on && !s->pf_merge && s->pf.d_segmin && s->pf_rel_filter >= 0.0 && s->pf_rel_filter < 1.0 &&
-                         (uint64_t)hi * f->geom.wpr <= s->pf.segmin_cap && !gn_sw().predrop;
+}
+
+// what gn_count_plan (gn_count_plan.h) decides from: the filter, the stream, the range and the switches, as plain values
+static GnCountPlanIn gn_count_plan_in(const gn_stream* s, uint32_t lo, uint32_t hi)
+{
+    const gn_filter*  f  = s->f;
+    const GnSwitches& sw = gn_sw();
+    GnCountPlanIn     in;
+    in.is_hibf = f->is_hibf, in.identity = f->identity, in.h = f->ibf.h, in.W = f->ibf.W, in.S = f->ibf.S;
+    in.lw = f->geom.lw, in.wpr = f->geom.wpr, in.gp_log2 = f->geom.gp_log2, in.rpb = f->geom.rpb, in.block = f->geom.block;
+    in.lds_bytes = f->geom.lds_bytes, in.split_lds_bytes = gn_split_lds_bytes(f->geom, f->ibf.h);
+    in.n_cu = (uint32_t)f->n_cu, in.split_bpc = f->split_bpc, in.split_table = f->d_sl_nbr != nullptr;
+    in.csr_identity = f->csr_identity, in.run_ok = f->run_ok, in.uniform_nb = f->uniform_nb;
+    in.stream_rows_min_bytes = f->stream_rows_min_bytes;
+    in.unit_list = s->d_unit_list != nullptr, in.long_reads = s->long_reads;
+    in.prev_count_deferred = s->prev_count_deferred, in.prev_unit_deferred = s->prev_unit_deferred;
+    in.pf_on = s->pf_on, in.pf_merge = s->pf_merge, in.pf_joint = s->pf_joint, in.pf_segmin = s->pf.d_segmin != nullptr;
+    in.pf_segmin_cap = s->pf.segmin_cap, in.pf_rel_filter = s->pf_rel_filter;
+    in.lo = lo, in.hi = hi, in.n_reads = s->n_reads, in.rel_cutoff = s->rel_cutoff;
+    in.sw.early_exit = sw.early_exit, in.sw.row_screen = sw.row_screen, in.sw.lean_screen = sw.lean_screen, in.sw.stream_rows = sw.stream_rows;
+    in.sw.stray_masks = sw.stray_masks, in.sw.cand_select = sw.cand_select, in.sw.csr_identity = sw.csr_identity;
+    in.sw.uniform_select = sw.uniform_select, in.sw.run_select = sw.run_select, in.sw.max_first = sw.max_first, in.sw.const_nb = sw.const_nb;
+    in.sw.split_kernel = sw.split_kernel, in.sw.predrop = sw.predrop, in.sw.deferred_grids = sw.deferred_grids, in.sw.on_demand = sw.on_demand;
+    in.sw.fake_count = sw.fake_count, in.sw.emit_probe = sw.emit_probe;
+    return in;
+}
+
+// count + select over reads [lo, hi) on the stream's main HIP stream (the match cursor is NOT reset here): the fields every launch
+// shares, the plan, the counters it names, its launches in order
+static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
+{
+    gn_filter*  f = s->f;
+    GnCountPlan pl;
+    gn_count_plan(gn_count_plan_in(s, lo, hi), &pl);
     if (lo == 0)
-        s->pf_predrop = predrop;
-    if (predrop)
     {
-        if (lo == 0)
-            GN_HIP(hipMemsetAsync(s->pf.d_pre, 0, sizeof(unsigned long long), s->st));
-        GN_HIP(hipMemsetAsync(s->pf.d_segmin + (size_t)lo * f->geom.wpr, 0xFF, (size_t)(hi - lo) * f->geom.wpr * 4, s->st));
-        p.pre_mode = s->pf_joint ? 2u : 1u;
+        s->rows_streamed = false;
+        s->pf_predrop    = pl.predrop;
+    }
+    s->rows_streamed = s->rows_streamed || pl.streamed;
+    if (pl.fake_count)
+    {
+        if ((uint64_t)(hi + 1) / 2 <= s->match_cap && hi > lo)
+            hipLaunchKernelGGL(gn_fake_count_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, s->st, s->d_matches, s->d_seg_begin, s->d_seg_count,
+                               s->v_status, s->v_nh, lo, hi, (uint32_t)f->geom.wpr, f->n_targets ? f->n_targets : 1u, s->d_ctr + GN_CTR_CURSOR);
+        GN_HIP(hipGetLastError());
+        return GN_OK;
+    }
+    GnCountParams p{};
+    gn_count_fill(p, s, lo, hi);
+    p.bin_tgt     = f->d_bin_tgt;
+    p.bin_nb2     = pl.bin_nb2 ? f->d_bin_nb2.get() : nullptr;
+    p.nbtab_off   = (uint32_t)f->geom.nbtab_off;
+    p.candcnt_off = (uint32_t)f->geom.candcnt_off;
+    p.big_list    = f->d_big_list;
+    p.n_big       = f->n_big;
+    p.sl_nbr      = f->d_sl_nbr;
+    p.match_cap   = s->match_cap;
+    p.cursor      = s->d_ctr + GN_CTR_CURSOR;
+    p.seg_begin   = s->d_seg_begin;
+    p.seg_count   = s->d_seg_count;
+    p.skip_ctr    = s->d_ctr + GN_CTR_SKIPPED_BYTES;
+    p.emit_probe  = pl.emit_probe; // (0 in the product; 64 / 128: the emission probe of the fast kernel's low-cutoff epilogue)
+    p.early_exit  = pl.early_exit; // (0: bench.py's every-row measurement and the parity tests of the exit)
+    p.probe_hashes = pl.probe_hashes; // (0: the finish's one-stage probe, for the A/B and the parity tests)
+    p.csr_identity = pl.csr_identity;
+    p.uniform_nb  = pl.uniform_nb;
+    p.run_select  = pl.run_select;
+    p.max_first   = pl.max_first;
+    p.const_nb    = pl.const_nb;
+    static_assert(sizeof(p.screen) == sizeof(pl.screen), "one byte per n");
+    memcpy(p.screen, pl.screen, sizeof(p.screen));
+    if (pl.predrop)
+    {
+        p.pre_mode = pl.pre_mode;
         p.pre_rel  = s->pf_rel_filter;
         p.seg_min  = s->pf.d_segmin;
         p.pre_ctr  = s->pf.d_pre;
     }
-    if (split)
+
+    const size_t one = sizeof(unsigned long long);
+    if (pl.clear & GN_CLEAR_SKIPPED)
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_SKIPPED_BYTES, 0, one, s->st));
+    if (pl.clear & GN_CLEAR_PRE)
+        GN_HIP(hipMemsetAsync(s->pf.d_pre, 0, one, s->st));
+    if (pl.clear & GN_CLEAR_SEGMIN)
+        GN_HIP(hipMemsetAsync(s->pf.d_segmin + (size_t)lo * f->geom.wpr, 0xFF, (size_t)(hi - lo) * f->geom.wpr * 4, s->st));
+    if (pl.clear & GN_CLEAR_DEFERRED)
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_COUNT_DEFERRED, 0, one, s->st));
+    if (pl.clear & GN_CLEAR_UNIT_CURSOR)
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_UNIT_CURSOR, 0, one, s->st));
+    if (pl.clear & GN_CLEAR_UNITS_LEFT)
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_UNITS_LEFT, 0, one, s->st));
+    if (pl.clear & GN_CLEAR_LONG)
+        GN_HIP(hipMemsetAsync(s->d_long_count, 0, one, s->st));
+
+    for (uint32_t i = 0; i < pl.n_launches; ++i)
     {
-        // split-bin maps: register counters + byte image for reads with <= 127 minimisers, the rest lands in d_deferred
-        GN_HIP(hipMemsetAsync(s->d_ctr + 4, 0, sizeof(unsigned long long), s->st));
-        p.work_list_out  = s->d_deferred;
-        p.work_count_out = s->d_ctr + 4;
-        const uint32_t keep = p.max_blocks;
-        p.max_blocks        = (uint32_t)f->n_cu * (f->split_bpc ? f->split_bpc : 1u) * 2u;
-        GN_HIP(gn_launch_count_split(p, f->geom, f->ibf.h, s->st));
-        p.max_blocks = keep;
-        p.work_list  = s->d_deferred;
-        p.work_count = s->d_ctr + 4;
-    }
-    if (fast)
-    {
-        // register-resident fast path for reads with <= 127 minimisers; the rest lands in d_deferred
-        GN_HIP(hipMemsetAsync(s->d_ctr + 4, 0, sizeof(unsigned long long), s->st));
-        p.work_list_out  = s->d_deferred;
-        p.work_count_out = s->d_ctr + 4;
-        if (!gn_sw().on_demand)
+        const GnCountLaunch& L = pl.launch[i];
+        // the lists of this launch: reads deferred to the generic kernel (d_deferred), units left to the list launch (d_unit_list)
+        const bool in_reads = L.list_in == GN_LIST_DEFERRED, in_units = L.list_in == GN_LIST_UNITS, out_units = L.list_out == GN_LIST_UNITS;
+        const bool out_reads = L.list_out != GN_LIST_NONE;
+        p.work_list      = in_reads ? s->d_deferred.get() : nullptr;
+        p.work_count     = in_reads ? s->d_ctr + GN_CTR_COUNT_DEFERRED : nullptr;
+        p.unit_list      = in_units ? s->d_unit_list.get() : nullptr;
+        p.unit_count     = in_units ? s->d_ctr + GN_CTR_UNITS_LEFT : nullptr;
+        p.work_list_out  = out_reads ? s->d_deferred.get() : nullptr;
+        p.work_count_out = out_reads ? s->d_ctr + GN_CTR_COUNT_DEFERRED : nullptr;
+        p.unit_list_out  = out_units ? s->d_unit_list.get() : nullptr;
+        p.unit_count_out = out_units ? s->d_ctr + GN_CTR_UNITS_LEFT : nullptr;
+        p.grab           = L.grab ? s->d_ctr + GN_CTR_UNIT_CURSOR : nullptr;
+        switch (L.family)
         {
-            GN_HIP(hipMemsetAsync(s->d_ctr + 72, 0, sizeof(unsigned long long), s->st));
-            p.grab = s->d_ctr + 72;
+            case GN_COUNT_SPLIT: GN_HIP(gn_launch_count_split(p, f->geom, f->ibf.h, L.blocks, s->st)); break;
+            case GN_COUNT_LEAN:
+            case GN_COUNT_FAST: GN_HIP(gn_launch_count_fast(L, p, s->st)); break;
+            case GN_COUNT_GENERIC: GN_HIP(gn_launch_count(p, f->geom, f->ibf.h, L.blocks, s->st)); break;
+            case GN_COUNT_LONG: GN_HIP(gn_launch_count_long(p, f->ibf.h, s->d_long_list, s->d_long_count, s->d_long_scratch, L.blocks, s->st)); break;
         }
-        // the screen-only kernel where the screening instance <4,1,true,false,true> would run (gn_launch_fast_one; switch lean_screen):
-        // what it leaves goes to d_unit_list and is run by the launch that follows it
-        if (s->d_unit_list && !gn_sw().lean_screen)
-        {
-            GN_HIP(hipMemsetAsync(s->d_ctr + 73, 0, sizeof(unsigned long long), s->st));
-            p.unit_list_out  = s->d_unit_list;
-            p.unit_count_out = s->d_ctr + 73;
-            if (s->prev_unit_deferred != ~0ull && lo == 0 && hi == s->n_reads && !gn_sw().deferred_grids)
-                // a grid for twice the last batch's list (four units a block)
-                p.max_blocks_list = (uint32_t)std::min<uint64_t>(p.max_blocks_list, std::max<uint64_t>((uint64_t)f->n_cu, s->prev_unit_deferred / 2 + 1));
-        }
-        GnRowPolicy pol; // (gn_row_policy.h: non-temporal row loads for a filter far past the caches)
-        pol.flat       = !f->is_hibf;
-        pol.plain_only = gn_sw().stream_rows;
-        pol.row_bytes  = f->ibf.S * f->ibf.W * 8ull;
-        pol.min_bytes  = f->stream_rows_min_bytes;
-        bool streamed  = false;
-        GN_HIP(gn_launch_count_fast(p, f->geom, f->ibf.h, pol, s->st, &streamed));
-        s->rows_streamed = s->rows_streamed || streamed;
-        p.unit_list_out = nullptr;
-        p.grab       = nullptr; // (the generic kernel that takes the deferred reads hands out its rounds as before)
-        p.work_list  = s->d_deferred;
-        p.work_count = s->d_ctr + 4;
-    }
-    if ((fast || split) && s->prev_count_deferred != ~0ull && lo == 0 && hi == s->n_reads && !gn_sw().deferred_grids)
-        // the generic kernel only takes what the fast / split kernel deferred: a grid for twice the last batch's list (one block per read)
-        p.max_blocks = (uint32_t)std::min<uint64_t>(p.max_blocks, std::max<uint64_t>((uint64_t)f->n_cu, s->prev_count_deferred * 2));
-    GN_HIP(gn_launch_count(p, f->geom, f->ibf.h, s->st));
-    if (s->long_reads) // reads the kernels above skipped as GN_READ_BIG: 32-bit counters, one workgroup each
-    {
-        GN_HIP(hipMemsetAsync(s->d_long_count, 0, sizeof(unsigned long long), s->st));
-        p.work_list = nullptr;
-        GN_HIP(gn_launch_count_long(p, f->ibf.h, s->d_long_list, s->d_long_count, s->d_long_scratch, GN_LONG_BLOCKS, s->st));
     }
     return GN_OK;
 }
@@ -1438,7 +1432,7 @@ static int gn_run_count_range(gn_stream* s, uint32_t lo, uint32_t hi)
 // whole batch in one go (HIBF, and the re-run after a match-buffer overflow)
 static int gn_run_count(gn_stream* s)
 {
-    GN_HIP(hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), s->st)); // cursor
+    GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_CURSOR, 0, sizeof(unsigned long long), s->st));
     s->rows_streamed = false;
     if (s->f->is_hibf)
         return gn_hibf_classify(s, s->f, s->st);
@@ -1466,15 +1460,15 @@ static int gn_run_group(gn_stream* s)
     s->segmented = s->f->identity && s->f->geom.wpr == 1 && !s->long_reads && !gn_sw().seg_result && gn_sw().chunk == 0;
     s->compacted = !s->segmented;
     if (nseg && s->segmented)
-        hipLaunchKernelGGL(gn_seg_order_kernel, dim3(64), dim3(256), 0, s->st, s->d_deferred, s->d_ctr + 4, s->d_matches, s->d_sorted, s->d_seg_begin,
-                           s->d_seg_count, s->d_seg_off, s->d_ctr, s->match_cap);
+        hipLaunchKernelGGL(gn_seg_order_kernel, dim3(64), dim3(256), 0, s->st, s->d_deferred, s->d_ctr + GN_CTR_COUNT_DEFERRED, s->d_matches, s->d_sorted, s->d_seg_begin,
+                           s->d_seg_count, s->d_seg_off, s->d_ctr + GN_CTR_CURSOR, s->match_cap);
     if (nseg && !s->segmented)
         hipLaunchKernelGGL(gn_gather_kernel, dim3((unsigned)((s->n_reads + 255) / 256)), dim3(256), 0, s->st, s->d_matches,
                            s->d_sorted, s->d_seg_begin, s->d_seg_count, s->d_seg_off, (uint64_t)s->n_reads,
-                           (uint32_t)s->f->geom.wpr, s->d_ctr, s->match_cap);
+                           (uint32_t)s->f->geom.wpr, s->d_ctr + GN_CTR_CURSOR, s->match_cap);
     GN_HIP(hipGetLastError());
     // exact number of matches = scan total (the cursor counts allocated space including chunk holes)
-    GN_HIP(hipMemcpyAsync(s->d_ctr + 6, s->d_seg_off + nseg, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
+    GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_EXACT_TOTAL, s->d_seg_off + nseg, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
     return GN_OK;
 }
 
@@ -1491,7 +1485,7 @@ int gn_result_compact(gn_stream* s)
     GN_HIP(hipEventRecord(s->ev_cmp[0], s->st));
     if (s->n_reads)
         hipLaunchKernelGGL(gn_gather_kernel, dim3((unsigned)((s->n_reads + 255) / 256)), dim3(256), 0, s->st, s->d_matches, s->d_sorted,
-                           s->d_seg_begin, s->d_seg_count, s->d_seg_off, (uint64_t)s->n_reads, 1u, s->d_ctr, s->match_cap);
+                           s->d_seg_begin, s->d_seg_count, s->d_seg_off, (uint64_t)s->n_reads, 1u, s->d_ctr + GN_CTR_CURSOR, s->match_cap);
     GN_HIP(hipGetLastError());
     GN_HIP(hipEventRecord(s->ev_cmp[1], s->st));
     s->compacted = true;
@@ -1543,18 +1537,18 @@ static int gn_run_minimisers_range(gn_stream* s, uint32_t lo, uint32_t hi, hipSt
     mp.hashes       = s->d_hashes;
     mp.n_hashes     = s->d_nh;
     mp.status       = s->d_status;
-    mp.total_hashes = s->d_ctr + 8; // 64 shards
+    mp.total_hashes = s->d_ctr + GN_CTR_HASH_SHARDS;
     mp.work_hint     = ~0u;
     if (w - k + 1 <= 65)
     {
         // short reads: lane-per-read kernel; longer ones are deferred to the wave-per-read kernel below
-        GN_HIP(hipMemsetAsync(s->d_ctr + 5, 0, sizeof(unsigned long long), st));
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_MIN_DEFERRED, 0, sizeof(unsigned long long), st));
         mp.lpr_max_len = 640;
         mp.defer_list  = s->d_mdeferred;
-        mp.defer_count = s->d_ctr + 5;
+        mp.defer_count = s->d_ctr + GN_CTR_MIN_DEFERRED;
         GN_HIP(gn_launch_minimiser_lpr(mp, st));
         mp.work_list  = s->d_mdeferred;
-        mp.work_count = s->d_ctr + 5;
+        mp.work_count = s->d_ctr + GN_CTR_MIN_DEFERRED;
         if (s->prev_min_deferred != ~0ull && lo == 0 && hi == s->n_reads && !gn_sw().deferred_grids)
             mp.work_hint = (uint32_t)std::min<uint64_t>(s->prev_min_deferred * 2, 0x7FFFFFFFull); // (twice what the last batch deferred)
     }
@@ -1745,25 +1739,25 @@ static int gn_finish(gn_stream* s)
         const bool stale = !s->ctr_copied || (s->pf_joint && s->pf_joint_done);
         if (stale)
             GN_HIP(hipMemcpy(s->h_ctr, s->d_ctr, GN_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        const uint64_t need = s->h_ctr[0];
+        const uint64_t need = s->h_ctr[GN_CTR_CURSOR];
         if (gn_sw().debug)
             fprintf(stderr, "[gn_finish] attempt %d need %llu cap %llu nh %llu\n", attempt, (unsigned long long)need,
-                    (unsigned long long)s->match_cap, (unsigned long long)s->h_ctr[1]);
+                    (unsigned long long)s->match_cap, (unsigned long long)s->h_ctr[GN_CTR_HIBF_LINES]);
         if (need <= s->match_cap)
         {
-            s->n_matches = s->h_ctr[6]; // exact (the cursor `need` counts allocated space including chunk holes)
+            s->n_matches = s->h_ctr[GN_CTR_EXACT_TOTAL]; // exact (the cursor `need` counts allocated space including chunk holes)
             if (s->pf_on && (!s->pf_joint || s->pf_joint_done)) // the batch's result is what the device-side filter_matches pre-pass left
             {
                 if (stale)
-                    GN_HIP(hipMemcpy(s->pf.h_ctr, s->pf.d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                s->n_matches = s->pf.h_ctr[2];
+                    GN_HIP(hipMemcpy(s->pf.h_ctr, s->pf.d_ctr, GN_PF_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+                s->n_matches = s->pf.h_ctr[GN_PF_CTR_SURVIVORS];
             }
             if (!s->f->is_hibf)
             {
-                s->prev_count_deferred = s->h_ctr[4];
-                s->prev_unit_deferred  = s->h_ctr[73];
+                s->prev_count_deferred = s->h_ctr[GN_CTR_COUNT_DEFERRED];
+                s->prev_unit_deferred  = s->h_ctr[GN_CTR_UNITS_LEFT];
                 if (!s->src)
-                    s->prev_min_deferred = s->h_ctr[5];
+                    s->prev_min_deferred = s->h_ctr[GN_CTR_MIN_DEFERRED];
             }
             return GN_OK;
         }
@@ -1911,9 +1905,9 @@ extern "C" int gn_fetch_postfilter(gn_stream* s, uint32_t* max_count, uint64_t* 
     if (max_count && s->n_reads)
         GN_HIP(hipMemcpy(max_count, s->pf.d_max, (size_t)s->n_reads * 4, hipMemcpyDeviceToHost));
     if (dropped_rel_filter)
-        *dropped_rel_filter = s->pf.h_ctr[0];
+        *dropped_rel_filter = s->pf.h_ctr[GN_PF_CTR_DROPPED_REL];
     if (dropped_fpr_query)
-        *dropped_fpr_query = s->pf.h_ctr[1];
+        *dropped_fpr_query = s->pf.h_ctr[GN_PF_CTR_DROPPED_FPR];
     return GN_OK;
 }
 
@@ -1995,12 +1989,8 @@ extern "C" int gn_stream_dense_counts(gn_stream* s, uint32_t read_begin, uint32_
     unsigned long long saved[GN_NCTR];
     memcpy(saved, s->h_ctr, sizeof(saved));
     GnCountParams p{};
-    p.rows = f->ibf.d_rows; p.S = f->ibf.S; p.W = (uint32_t)f->ibf.W; p.B = (uint32_t)f->ibf.B; p.shift = f->ibf.shift;
-    p.tgt_off = f->identity ? nullptr : f->d_tgt_off; p.tgt_bins = f->d_tgt_bins; p.tgt_lds = f->d_tgt_lds; p.tgt_rec = f->d_tgt_rec; p.n_targets = f->n_targets;
-    p.hashes = s->v_hashes; p.slot_off = s->v_slot_off; p.n_hashes = s->v_nh; p.status = s->v_status;
-    p.n_reads = s->n_reads; p.rel_cutoff = s->rel_cutoff; p.wpr = f->geom.wpr; p.gp_log2 = f->geom.gp_log2;
-    p.slice_dwords = f->geom.slice_dwords;
-    p.matches = s->d_matches; p.match_cap = 0; // no writes
+    gn_count_fill(p, s, 0, s->n_reads);
+    p.match_cap = 0; // no writes
     GnDev<unsigned long long> dctr;
     GnDev<uint64_t>           segb;
     GnDev<uint32_t>           segc;
@@ -2010,8 +2000,7 @@ extern "C" int gn_stream_dense_counts(gn_stream* s, uint32_t read_begin, uint32_
     hipMemsetAsync(dctr, 0, 8, s->st);
     p.cursor = dctr; p.seg_begin = segb; p.seg_count = segc;
     p.dense = dd; p.dense_begin = read_begin; p.dense_end = read_end;
-    p.max_blocks = (uint32_t)f->n_cu * 16u;
-    hipError_t e  = gn_launch_count(p, f->geom, f->ibf.h, s->st);
+    hipError_t e  = gn_launch_count(p, f->geom, f->ibf.h, gn_generic_grid(s->n_reads, f->geom.rpb, (uint32_t)f->n_cu), s->st);
     hipError_t e2 = hipStreamSynchronize(s->st);
     if (e == hipSuccess && e2 == hipSuccess)
         e = hipMemcpy(counts, dd, nel * 2, hipMemcpyDeviceToHost);
@@ -2033,15 +2022,15 @@ extern "C" int gn_stream_timings(gn_stream* s, gn_timings* t)
     hipEventElapsedTime(&tm.ms_count, s->ev_count0, s->ev[2]); // first count kernel start -> last count kernel end
     hipEventElapsedTime(&tm.ms_total, s->ev[0], s->ev[3]);
     tm.n_hashes = 0;
-    for (int i = 8; i < 8 + 64; ++i) // 64 shards (the minimiser kernels of the batch ran on the stream the reads were uploaded to)
+    for (uint32_t i = GN_CTR_HASH_SHARDS; i < GN_CTR_HASH_SHARDS + GN_CTR_N_HASH_SHARDS; ++i) // (the minimiser kernels of the batch ran on the stream the reads were uploaded to)
         tm.n_hashes += (s->src ? s->src : s)->h_ctr[i];
     tm.n_matches = s->n_matches;
     tm.n_count_launches = s->n_chunks;
     if (s->f->is_hibf)
-        tm.algo_bytes = s->h_ctr[2];
+        tm.algo_bytes = s->h_ctr[GN_CTR_ALGO_BYTES];
     else
         tm.algo_bytes = tm.n_hashes * (uint64_t)s->f->ibf.h * s->f->ibf.W * 8ull;
-    tm.fetched_bytes = tm.algo_bytes - (s->f->is_hibf ? 0ull : (uint64_t)s->h_ctr[7]);
+    tm.fetched_bytes = tm.algo_bytes - (s->f->is_hibf ? 0ull : (uint64_t)s->h_ctr[GN_CTR_SKIPPED_BYTES]);
     if (s->cmp_timed && hipEventSynchronize(s->ev_cmp[1]) == hipSuccess)
         hipEventElapsedTime(&tm.ms_compact, s->ev_cmp[0], s->ev_cmp[1]);
     *t = tm;
@@ -2071,6 +2060,6 @@ extern "C" int gn_stream_screen_deferred(gn_stream* s, uint64_t* units)
     int rc = gn_finish(s);
     if (rc)
         return rc;
-    *units = s->f->is_hibf ? 0ull : (uint64_t)s->h_ctr[73]; // (the batch's last count range)
+    *units = s->f->is_hibf ? 0ull : (uint64_t)s->h_ctr[GN_CTR_UNITS_LEFT]; // (the batch's last count range)
     return GN_OK;
 }

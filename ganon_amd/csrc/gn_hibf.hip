@@ -108,7 +108,7 @@ struct GnHibfLevelParams
     uint32_t                  lds_region;   // packed kernel: 8-byte words of dynamic LDS per wave
     uint32_t                  stage_hashes; // packed kernel: the first GN_HIBF_NQ minimisers of every item are staged in LDS (classes of at
                                             // most 4 lanes per row; lds_region holds (64 >> narrowest class) items' worth)
-    unsigned long long*       lvl_bytes; // this level's algorithmic bytes / line bytes (beside the batch totals ctr[2] / ctr[1]): the
+    unsigned long long*       lvl_bytes; // this level's algorithmic bytes / line bytes (beside the batch totals GN_CTR_ALGO_BYTES / GN_CTR_HIBF_LINES): the
     unsigned long long*       lvl_lines; // per-level figures of gn_stream_hibf_levels need no copy between the levels
     uint32_t                  wide;      // the reference's -DLONGREADS build (value_t = uint32_t): sums do not wrap at 2^16 and reads
                                          // of more than 65535 minimisers (GN_READ_BIG) are counted like the others
@@ -182,7 +182,7 @@ struct GnHibfAppender
                 mq_chunk                = mq_chunk < GN_HIBF_CHUNK_MAX ? mq_chunk * 2u : mq_chunk;
                 unsigned long long nb   = 0;
                 if (lane == 0)
-                    nb = atomicAdd(&p.ctr[0], (unsigned long long)take);
+                    nb = atomicAdd(&p.ctr[GN_CTR_CURSOR], (unsigned long long)take);
                 mq_base = gn_hibf_bcast64(nb);
                 mq_left = take;
             }
@@ -205,7 +205,7 @@ struct GnHibfAppender
         close_work(p, lane);
         close_matches(p, lane);
         if (lane == 0 && n_matches)
-            atomicAdd(&p.ctr[6], n_matches);
+            atomicAdd(&p.ctr[GN_CTR_EXACT_TOTAL], n_matches);
     }
 };
 
@@ -746,8 +746,8 @@ __global__ __launch_bounds__(256) GN_PACK_ATTR void gn_hibf_pack_kernel(GnHibfLe
     }
     if (lane == 0 && my_bytes)
     {
-        atomicAdd(&p.ctr[2], my_bytes);
-        atomicAdd(&p.ctr[1], my_lines);
+        atomicAdd(&p.ctr[GN_CTR_ALGO_BYTES], my_bytes);
+        atomicAdd(&p.ctr[GN_CTR_HIBF_LINES], my_lines);
         atomicAdd(p.lvl_bytes, my_bytes);
         atomicAdd(p.lvl_lines, my_lines);
     }
@@ -1101,8 +1101,8 @@ __global__ __launch_bounds__(256) void gn_hibf_reg_kernel(GnHibfLevelParams p)
     app.finish(p, lane);
     if (lane == 0 && my_bytes)
     {
-        atomicAdd(&p.ctr[2], my_bytes);
-        atomicAdd(&p.ctr[1], my_lines);
+        atomicAdd(&p.ctr[GN_CTR_ALGO_BYTES], my_bytes);
+        atomicAdd(&p.ctr[GN_CTR_HIBF_LINES], my_lines);
         atomicAdd(p.lvl_bytes, my_bytes);
         atomicAdd(p.lvl_lines, my_lines);
     }
@@ -1207,8 +1207,8 @@ __global__ __launch_bounds__(256) void gn_hibf_level_kernel(GnHibfLevelParams p)
     app.finish(p, lane);
     if (lane == 0 && my_bytes)
     {
-        atomicAdd(&p.ctr[2], my_bytes);
-        atomicAdd(&p.ctr[1], my_lines);
+        atomicAdd(&p.ctr[GN_CTR_ALGO_BYTES], my_bytes);
+        atomicAdd(&p.ctr[GN_CTR_HIBF_LINES], my_lines);
         atomicAdd(p.lvl_bytes, my_bytes);
         atomicAdd(p.lvl_lines, my_lines);
     }
@@ -1848,8 +1848,8 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
     const uint32_t rd_bits = std::max(1u, gn_bits_for(n)); // a read index is < n <= 2^rd_bits - 1: below the all-ones sentinel
     if (ub_bits + rd_bits > 64)
         return gn_fail(GN_ERANGE, "read index and user bin do not fit one 64-bit sort key");
-    GN_HIP(hipMemsetAsync(s->d_ctr + 1, 0, 3 * sizeof(unsigned long long), st)); // line bytes, algo bytes, (unused)
-    GN_HIP(hipMemsetAsync(s->d_ctr + 6, 0, sizeof(unsigned long long), st));     // exact match count
+    GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_HIBF_LINES, 0, 3 * sizeof(unsigned long long), st)); // ... GN_CTR_ALGO_BYTES, GN_CTR_HIBF_WORK
+    GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_EXACT_TOTAL, 0, sizeof(unsigned long long), st));
     GN_HIP(hipMemsetAsync(s->d_hctr, 0, (37 * NL + 2) * sizeof(unsigned long long), st)); // queues, per-level bytes, [4NL] output base, [4NL+2..] per-level line bytes, [5NL+2..] per level: 8 class counts, 8 bases, (8 unused), [29NL+2..] batch cursors of the packed kernel
     GN_HIP(hipMemsetAsync(s->d_seg_count, 0, ((size_t)n + 1) * 4, st));
     unsigned long long* d_out_base = s->d_hctr + 4 * NL;
@@ -1880,7 +1880,7 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
 
     // the levels of reads [lo, lo + cnt): queue lengths and the match cursor come back to the host (one sync)
     auto run_levels = [&](uint32_t lo, uint32_t cnt, bool stamp) -> int {
-        GN_HIP(hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), st));
+        GN_HIP(hipMemsetAsync(s->d_ctr + GN_CTR_CURSOR, 0, sizeof(unsigned long long), st));
         GN_HIP(hipMemsetAsync(s->d_hctr, 0, 3 * NL * sizeof(unsigned long long), st));
         GN_HIP(hipMemsetAsync(s->d_hctr + 5 * NL + 2, 0, 32 * NL * sizeof(unsigned long long), st));
         GN_HIP(hipMemsetAsync(s->d_hsub, 0, (size_t)NL * 384 * sizeof(unsigned long long), st));
@@ -2032,9 +2032,9 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
     };
 
     s->hibf_levels_run = 0;
-    uint64_t need_cap = 0;       // capacity the caller has to provide if this run does not fit (-> d_ctr[0], see gn_finish)
+    uint64_t need_cap = 0;       // capacity the caller has to provide if this run does not fit (-> GN_CTR_CURSOR, see gn_finish)
     uint64_t out_upper = 0;      // matches appended so far, holes of the sorted ranges included (an upper bound of *d_out_base)
-    uint64_t done_bytes = 0, done_exact = 0, done_lines = 0; // ctr[2] / ctr[6] / ctr[1] after the ranges that are through (a range that is run again starts from them)
+    uint64_t done_bytes = 0, done_exact = 0, done_lines = 0; // GN_CTR_ALGO_BYTES / GN_CTR_EXACT_TOTAL / GN_CTR_HIBF_LINES after the ranges that are through (a range that is run again starts from them)
     uint32_t n_ranges = 0;
     uint32_t step = s->hibf_range_reads && s->hibf_range_reads < n ? s->hibf_range_reads : n; // (what fitted the last batch)
     uint32_t lo = 0;
@@ -2047,11 +2047,11 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
         uint64_t worst = 0;
         for (uint32_t i = 0; i < 3 * NL; ++i) // (the fourth row holds byte counts, not queue lengths)
             worst = std::max<uint64_t>(worst, s->h_hctr[i]);
-        const uint64_t nm = s->h_ctr[0];
+        const uint64_t nm = s->h_ctr[GN_CTR_CURSOR];
         auto restore = [&]() -> int { // the range is run again: what it added to the batch totals goes
-            GN_HIP(hipMemcpyAsync(s->d_ctr + 2, &done_bytes, 8, hipMemcpyHostToDevice, st));
-            GN_HIP(hipMemcpyAsync(s->d_ctr + 1, &done_lines, 8, hipMemcpyHostToDevice, st));
-            GN_HIP(hipMemcpyAsync(s->d_ctr + 6, &done_exact, 8, hipMemcpyHostToDevice, st));
+            GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_ALGO_BYTES, &done_bytes, 8, hipMemcpyHostToDevice, st));
+            GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_HIBF_LINES, &done_lines, 8, hipMemcpyHostToDevice, st));
+            GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_EXACT_TOTAL, &done_exact, 8, hipMemcpyHostToDevice, st));
             GN_HIP(hipStreamSynchronize(st));
             return GN_OK;
         };
@@ -2142,9 +2142,9 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
             GN_HIP(hipGetLastError());
             out_upper += ns;
         }
-        done_bytes = s->h_ctr[2];
-        done_lines = s->h_ctr[1];
-        done_exact = s->h_ctr[6];
+        done_bytes = s->h_ctr[GN_CTR_ALGO_BYTES];
+        done_lines = s->h_ctr[GN_CTR_HIBF_LINES];
+        done_exact = s->h_ctr[GN_CTR_EXACT_TOTAL];
         ++n_ranges;
         if (n_ranges == 1 && cnt == n)
             s->hibf_levels_run = depth;
@@ -2159,14 +2159,14 @@ int gn_hibf_classify(gn_stream* s, gn_filter* f, hipStream_t st)
     {
         // gn_finish() reads the cursor, sees that it exceeds the capacity, grows the buffers and runs the batch again
         const unsigned long long v = need_cap;
-        GN_HIP(hipMemcpyAsync(s->d_ctr, &v, sizeof(v), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_CURSOR, &v, sizeof(v), hipMemcpyHostToDevice, st));
         GN_HIP(hipStreamSynchronize(st));
         return GN_OK;
     }
     {
         // the cursor of a batch that went through: within the capacity (the gather / pre-pass kernels look at it)
         const unsigned long long v = out_upper;
-        GN_HIP(hipMemcpyAsync(s->d_ctr, &v, sizeof(v), hipMemcpyHostToDevice, st));
+        GN_HIP(hipMemcpyAsync(s->d_ctr + GN_CTR_CURSOR, &v, sizeof(v), hipMemcpyHostToDevice, st));
         GN_HIP(hipStreamSynchronize(st));
     }
     size_t tmp = s->scan_tmp_bytes;

@@ -11,6 +11,7 @@
 #include "../../include/ganon_ibf_hash.h"
 #include "gn_devmem.h"
 #include "gn_packed_set.h"
+#include "gn_count_plan.h"
 #include "gn_row_policy.h"
 
 #define GN_MAX_CHUNKS 64 // pipeline chunks per batch (minimiser on the side stream || count on the main stream)
@@ -20,9 +21,26 @@
 #define GN_HIBF_TIMED_LEVELS 8 // tree levels with a time stamp of their own (gn_stream_hibf_levels)
 #define GN_PF_MAX_JOINT 16   // filters of one hierarchy level in a joint filter_matches pre-pass, per device
 #define GN_PF_MAX_DEVICES 16 // devices a joint pass spans (column parts of a bin-range partitioned filter)
-#define GN_LONG_BLOCKS 128u // workgroups (and uint32 count slabs) of the long-read kernel
-#define GN_NCTR 74 // device counters: [0] match cursor [2] algo bytes [3] hibf work [4] count-deferred [5] minimiser-deferred
-                   // [6] exact match total [8..71] total-hashes shards [72] unit cursor of the fast count kernel [73] units the screen-only fast kernel left to its list
+// slots of gn_stream::d_ctr / h_ctr (device counters of a batch and their pinned copy)
+enum GnCtr : uint32_t
+{
+    GN_CTR_CURSOR         = 0,  // match cursor
+    GN_CTR_HIBF_LINES     = 1,  // HIBF: line bytes of the row requests
+    GN_CTR_ALGO_BYTES     = 2,  // HIBF: algorithmic bytes
+    GN_CTR_HIBF_WORK      = 3,  // HIBF: work count (cleared with the two above; no kernel writes it)
+    GN_CTR_COUNT_DEFERRED = 4,  // reads the fast / split count kernel left to the generic one
+    GN_CTR_MIN_DEFERRED   = 5,  // reads the lane-per-read minimiser kernel left to the wave-per-read one
+    GN_CTR_EXACT_TOTAL    = 6,  // exact match total
+    GN_CTR_SKIPPED_BYTES  = 7,  // row bytes the fast count kernels did not fetch
+    GN_CTR_HASH_SHARDS    = 8,  // total hashes, the first of GN_CTR_N_HASH_SHARDS shards
+    GN_CTR_UNIT_CURSOR    = 72, // unit cursor of the fast count kernel
+    GN_CTR_UNITS_LEFT     = 73, // units the screen-only fast kernel left to its list
+    GN_NCTR               = 74
+};
+constexpr uint32_t GN_CTR_N_HASH_SHARDS = 64;
+static_assert(GN_CTR_HASH_SHARDS + GN_CTR_N_HASH_SHARDS == GN_CTR_UNIT_CURSOR, "the shards end where the unit cursor begins");
+// slots of GnPostfilterBufs::d_ctr / h_ctr (the filter_matches pre-pass)
+enum GnPfCtr : uint32_t { GN_PF_CTR_DROPPED_REL = 0, GN_PF_CTR_DROPPED_FPR = 1, GN_PF_CTR_SURVIVORS = 2, GN_PF_CTR_BIG = 3 /* joint pass: length of its list */, GN_PF_NCTR = 4 };
 
 // ---- switches ---------------------------------------------------------------------------------
 // The ONE place the library reads its environment: $GANON_HIP_ABLATE, a comma list of the names below, parsed once when
@@ -149,10 +167,6 @@ struct GnCountParams
     const unsigned long long* unit_count;
     uint32_t*                 unit_list_out;
     unsigned long long*       unit_count_out;
-    uint32_t                  max_blocks_lean; // screen-only fast kernel: persistent grid size (five blocks a CU)
-    uint32_t                  max_blocks_list; // ... and the grid of the launch over its list
-    uint32_t                  max_blocks; // generic kernel: persistent grid size
-    uint32_t                  max_blocks_fast; // fast kernel: persistent grid size
     uint32_t                  emit_probe;      // fast kernel: GnSwitches::emit_probe (0 in the product)
     // generic kernel, candidate-driven select (split bins): bin -> CSR target, and (bins of the bin's target, capped
     // at 255) as u16 pairs in the layout of the LDS count area; nullptr = scan every target
@@ -208,13 +222,13 @@ bool gn_count_geometry(uint64_t W, uint32_t hash_funs, GnCountGeometry* g, const
 uint32_t gn_count_lds_index(const GnCountGeometry& g, uint32_t b);
 
 hipError_t gn_launch_minimiser(const GnMinimiserParams& p, int n_cu, hipStream_t st);
-hipError_t gn_launch_count(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st);
-// (pol: gn_row_policy.h; *streamed: whether the launch took the stream kernels, i.e. non-temporal row loads)
-hipError_t gn_launch_count_fast(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, const GnRowPolicy& pol, hipStream_t st, bool* streamed);
+// the count launchers take their grid (and the fast family its kernel and LDS) from the plan, gn_count_plan.h: they decide nothing
+hipError_t gn_launch_count(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, uint32_t blocks, hipStream_t st);
+hipError_t gn_launch_count_fast(const GnCountLaunch& L, const GnCountParams& p, hipStream_t st); // families lean and fast
 // split-bin maps, reads with <= 127 minimisers, rows of at least one wave (gn_split.hip)
 hipError_t gn_launch_count_long(const GnCountParams& p, uint32_t hash_funs, uint32_t* list, unsigned long long* count, uint32_t* scratch,
                                 uint32_t blocks, hipStream_t st);
-hipError_t gn_launch_count_split(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st);
+hipError_t gn_launch_count_split(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, uint32_t blocks, hipStream_t st);
 size_t     gn_split_lds_bytes(const GnCountGeometry& g, uint32_t hash_funs);
 
 // ---- HIBF -----------------------------------------------------------------------------------
@@ -350,7 +364,7 @@ struct GnPostfilterBufs
     uint64_t                  segmin_cap = 0;
     GnDev<unsigned long long> d_pre;  // [0] matches the count kernel did not write (they count as dropped by rel_filter) [1] HIBF: cursor
     GnDev<uint32_t>           d_rmax; // HIBF: largest count per read over the raw pairs (gn_hibf_premax_kernel)
-    GnDev<unsigned long long> d_ctr;  // [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+    GnDev<unsigned long long> d_ctr;  // GnPfCtr
     GnPinned<unsigned long long> h_ctr; // pinned copy
     GnDev<uint8_t>            d_scan;
     size_t                    scan_bytes = 0;
@@ -483,7 +497,7 @@ struct gn_stream
     gn_match*           pf_out     = nullptr; // where the pre-pass put its survivors (d_matches, or d_sorted when it read segments)
     hipEvent_t          ev_cmp[2]{};          // around the last contiguous copy (gn_timings.ms_compact)
     bool                cmp_timed  = false;
-    GnDev<unsigned long long> d_ctr; // [0] cursor [1] total_hashes [2] algo_bytes [3] work count
+    GnDev<unsigned long long> d_ctr; // GnCtr
     GnDev<uint64_t>     d_seg_begin;
     GnDev<uint32_t>     d_seg_count;
     GnDev<uint64_t>     d_seg_off;   // n*wpr+1 exclusive scan of seg_count

@@ -1051,8 +1051,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
     } // rounds
 }
 
-// build-time tuning knobs of the fast kernel (defaults = what was measured best on MI355X)
-#define GN_FAST_LIST 512u // matches of a unit the fast kernel's epilogue lists in LDS before it writes them out (2 KiB a wave)
+// build-time tuning knobs of the fast kernel (defaults = what was measured best on MI355X; GN_FAST_LIST: gn_count_plan.h)
 #ifndef GN_FAST_WPE_LW1
 #define GN_FAST_WPE_LW1 4 // waves per SIMD the register allocator must reach, 8-byte lanes
 #endif
@@ -1088,14 +1087,12 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(MAXT > 512
 // bin in one (7 300 cycles a finish).  The screening instances ask for the next unit's metadata with the unit's first rows in flight.
 // WIDE =rows of more than 128 words (1 KiB) with 16-byte lanes: there the third wave a SIMD bought +0.3 % (128 GiB filter, 4 KiB rows) for
 // 64 bytes of scratch per lane, so those rows get the two-wave build with nothing spilled; narrower rows keep three waves (+4 .. 7 %).
-// SCRN = the instance with the screen.  It is launched only when the launch's table has an entry (gn_launch_fast_one): a launch
+// SCRN = the instance with the screen.  It is launched only when the launch's table has an entry (gn_count_plan.h): a launch
 // whose table is empty -- a low cutoff, row_screen ablated, h != 4 -- runs the instance without it, in which everything the screen added folds away
 // at compile time: the kernel as it was before the screen, but for the byte tally's wrapping sum (at --rel-cutoff 0.2 the screening instance on its unscreened path was 0.8 %
 // slower than that one, 2 % with the wrapper's defaults: a select in every issue, a branch in every consume).
 // EE launches only happen where "a wave is one hash group" (rows of 64 lanes and more); the screening instances take that as a
-// compile-time fact, which spares them registers.  Kernel and launcher both read it from here.
-constexpr uint32_t GN_FAST_EE_GP_LOG2 = 6;
-static_assert((1u << GN_FAST_EE_GP_LOG2) == GN_WAVE, "the EE instances of the fast kernel: one hash group a wave");
+// compile-time fact, which spares them registers (GN_FAST_EE_GP_LOG2: kernel and plan both read it from gn_count_plan.h).
 template <int HF, int LW, bool EE, bool WIDE = false, bool SCRN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW == 1 ? GN_FAST_WPE_LW1 : (HF <= 4 && !WIDE ? GN_FAST_WPE_LW2_H4 : GN_FAST_WPE_LW2)) : 1))) void gn_ibf_count_fast_kernel(GnCountParams p)
 {
@@ -1106,7 +1103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
 // The same instance with non-temporal row loads (gn_row_policy.h says which launches take it).  The body is one text, included in
 // both kernels with GN_ROWS_NT set: as a __forceinline__ function called from two kernels it is optimised on its own before it is
 // inlined, and the plain kernels then no longer compile to the registers they have (the screen-only kernel: 9 SGPRs spilled where
-// tests/test_lean_screen_cpu.py wants none).  Launched for <4,1,true,false,true> and <4,2,true,true,true> only (gn_launch_fast_instance).
+// tests/test_lean_screen_cpu.py wants none).  Launched for <4,1,true,false,true> and <4,2,true,true,true> only (gn_launch_count_fast).
 template <int HF, int LW, bool EE, bool WIDE = false, bool SCRN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW == 1 ? GN_FAST_WPE_LW1 : (HF <= 4 && !WIDE ? GN_FAST_WPE_LW2_H4 : GN_FAST_WPE_LW2)) : 1))) void gn_ibf_count_stream_kernel(GnCountParams p)
 {
@@ -1128,7 +1125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EE ? (LW ==
 // lets it run at five waves a SIMD (96 registers) where the screening instance holds four.
 // A unit it does not take -- no screen for its n (ds == 0), or a survey that leaves more than GN_NARROW_MAX bins -- is appended
 // by unit number to p.unit_list_out (never more entries than units: a unit is appended at most once) and runs the unscreened flow
-// from hash 0 in the launch of <4, 1, true> over that list that follows (gn_launch_fast_one); an aborted unit's screen rows are
+// from hash 0 in the launch of <4, 1, true> over that list that follows (gn_count_plan.h); an aborted unit's screen rows are
 // subtracted from skipped_bytes here, as the screening instance does.  pre_mode needs nothing from a unit of this kernel: seg_min
 // and n_pre are touched only when more than six lanes report, and here at most GN_NARROW_MAX bins do.
 #ifndef GN_FAST_WPE_LEAN
@@ -1149,136 +1146,93 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GN_FAST_WPE
 }
 
 template <int HF, int LW, int MAXT>
-static hipError_t gn_launch_count_one(const GnCountParams& p, const GnCountGeometry& g, hipStream_t st)
+static hipError_t gn_launch_count_one(const GnCountParams& p, const GnCountGeometry& g, uint32_t blocks, hipStream_t st)
 {
-    uint32_t blocks = (p.n_reads - p.read_begin + g.rpb - 1) / g.rpb;
-    if (blocks > p.max_blocks)
-        blocks = p.max_blocks;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gn_ibf_count_kernel<HF, LW, MAXT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes);
     hipLaunchKernelGGL((gn_ibf_count_kernel<HF, LW, MAXT>), dim3(blocks), dim3(g.block), g.lds_bytes, st, p);
     return hipGetLastError();
 }
 
-// One instance of the fast kernel under the launch's row policy (gn_row_policy.h): the stream kernel is the same instance with
-// non-temporal row loads, and exists for the shapes gn_stream_instance() names.
-template <int HF, int LW, bool EE, bool WIDE = false, bool SCRN = false>
-static void gn_launch_fast_instance(bool stream, uint32_t blocks, size_t lds, hipStream_t st, const GnCountParams& p)
+// The fast family's one entry point: the record (gn_count_plan.h) names the kernel -- the screen-only one, or the instance
+// <HF, LW, EE, WIDE, SCRN> -- its stream twin where there is one (gn_stream_instance), the grid and the LDS.  Nothing is decided here;
+// a key without an instance is an error.
+constexpr uint32_t gn_fast_key(uint32_t lw, bool ee, bool wide, bool scrn, bool stream)
 {
-    if constexpr (HF == 4 && EE && SCRN && (LW == 1 ? !WIDE : WIDE)) // (gn_stream_instance)
-        if (stream)
-        {
-            hipLaunchKernelGGL((gn_ibf_count_stream_kernel<HF, LW, EE, WIDE, SCRN>), dim3(blocks), dim3(256), lds, st, p);
-            return;
-        }
-    hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, LW, EE, WIDE, SCRN>), dim3(blocks), dim3(256), lds, st, p);
+    return lw << 4 | (ee ? 8u : 0u) | (wide ? 4u : 0u) | (scrn ? 2u : 0u) | (stream ? 1u : 0u);
 }
-
-template <int HF, int LW>
-static hipError_t gn_launch_fast_one(const GnCountParams& p, const GnRowPolicy& pol, hipStream_t st, bool* streamed)
+template <int HF>
+static hipError_t gn_launch_fast_hf(const GnCountLaunch& L, const GnCountParams& p, hipStream_t st)
 {
-    // the early-exit variant only where a wave is one hash group (no cross-lane sums in its check)
-    const bool ee = p.early_exit && p.gp_log2 == GN_FAST_EE_GP_LOG2; // (the kernel's EE instances do not read p.gp_log2)
-    const uint64_t units  = (uint64_t)(p.n_reads - p.read_begin) * p.wpr;
-    uint32_t       blocks = (uint32_t)((units + 3) / 4);
-    if (blocks > p.max_blocks_fast)
-        blocks = p.max_blocks_fast;
-    const size_t   lds    = 4 * (128 * (HF <= 4 ? 4 : 8) + GN_FAST_LIST) * 4; // per wave: the row table + the epilogue's match list
-    const size_t   lds_pm = 4 * (GN_PROBE_HASHES * 2 * LW * GN_WAVE) * 4;     // ... the screening instances: + the probe's hit masks
-    // the screening instance only for a launch whose table gives some read a screen (gn_capi.hip fills it for the shapes that have one)
-    bool scr = false;
-    if constexpr (HF == 4)
-        for (uint32_t w : p.screen)
-            scr = scr || w != 0;
-    scr = scr && ee;
-    // non-temporal row loads where the launch rule says so (the list launch behind the screen-only kernel always loads plain)
-    const bool stream = gn_rows_stream(pol, HF, LW, ee, LW == 2 && p.W > 128, scr);
-    if (streamed)
-        *streamed = stream;
-    if constexpr (HF == 4 && LW == 2)
-        if (scr && p.W > 128)
-        {
-            gn_launch_fast_instance<HF, LW, true, true, true>(stream, blocks, lds + lds_pm, st, p);
-            return hipGetLastError();
-        }
-    if constexpr (HF == 4 && LW == 1)
-        if (scr && p.unit_list_out != nullptr)
-        {
-            // the screen-only kernel (its LDS: the row table and the probe's hit masks, 16 KiB a block), then the instance without a screen over the units it left: the list
-            // is usually short (reads whose n has no table entry, aborted screens), so that grid follows the last batch's list
-            uint32_t lean_blocks = (uint32_t)((units + 3) / 4);
-            if (lean_blocks > p.max_blocks_lean)
-                lean_blocks = p.max_blocks_lean;
-            if (stream)
-                hipLaunchKernelGGL(gn_ibf_count_stream_kernel_lean, dim3(lean_blocks), dim3(256), 4 * (128 * HF + GN_PROBE_HASHES * 2 * GN_WAVE) * 4, st, p);
+    const dim3   grid(L.blocks), block(256);
+    const size_t lds = (size_t)L.lds_bytes;
+    switch (gn_fast_key(L.LW, L.EE, L.WIDE, L.SCRN, L.stream))
+    {
+        case gn_fast_key(1, false, false, false, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, 1, false>), grid, block, lds, st, p); break;
+        case gn_fast_key(2, false, false, false, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, 2, false>), grid, block, lds, st, p); break;
+        case gn_fast_key(1, true, false, false, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, 1, true>), grid, block, lds, st, p); break;
+        case gn_fast_key(2, true, false, false, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, 2, true>), grid, block, lds, st, p); break;
+        case gn_fast_key(2, true, true, false, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<HF, 2, true, true>), grid, block, lds, st, p); break;
+        default:
+            if constexpr (HF == 4) // the instances that screen, and their stream twins
+                switch (gn_fast_key(L.LW, L.EE, L.WIDE, L.SCRN, L.stream))
+                {
+                    case gn_fast_key(1, true, false, true, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<4, 1, true, false, true>), grid, block, lds, st, p); break;
+                    case gn_fast_key(1, true, false, true, true): hipLaunchKernelGGL((gn_ibf_count_stream_kernel<4, 1, true, false, true>), grid, block, lds, st, p); break;
+                    case gn_fast_key(2, true, true, true, false): hipLaunchKernelGGL((gn_ibf_count_fast_kernel<4, 2, true, true, true>), grid, block, lds, st, p); break;
+                    case gn_fast_key(2, true, true, true, true): hipLaunchKernelGGL((gn_ibf_count_stream_kernel<4, 2, true, true, true>), grid, block, lds, st, p); break;
+                    default: return hipErrorInvalidValue;
+                }
             else
-                hipLaunchKernelGGL(gn_ibf_count_fast_kernel_lean, dim3(lean_blocks), dim3(256), 4 * (128 * HF + GN_PROBE_HASHES * 2 * GN_WAVE) * 4, st, p);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess)
-                return e;
-            GnCountParams q = p;
-            q.unit_list     = p.unit_list_out;
-            q.unit_count    = p.unit_count_out;
-            q.grab          = nullptr;
-            if (blocks > p.max_blocks_list)
-                blocks = p.max_blocks_list;
-            gn_launch_fast_instance<HF, LW, true>(stream, blocks ? blocks : 1u, lds, st, q);
-            return hipGetLastError();
-        }
-    if constexpr (HF == 4 && LW == 1)
-        if (scr)
-        {
-            gn_launch_fast_instance<HF, LW, true, false, true>(stream, blocks, lds + lds_pm, st, p);
-            return hipGetLastError();
-        }
-    if (ee && LW == 2 && p.W > 128)
-        gn_launch_fast_instance<HF, LW, true, LW == 2>(stream, blocks, lds, st, p);
-    else if (ee)
-        gn_launch_fast_instance<HF, LW, true>(stream, blocks, lds, st, p);
-    else
-        gn_launch_fast_instance<HF, LW, false>(false, blocks, lds, st, p);
+                return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
-hipError_t gn_launch_count_fast(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, const GnRowPolicy& pol, hipStream_t st, bool* streamed)
+hipError_t gn_launch_count_fast(const GnCountLaunch& L, const GnCountParams& p, hipStream_t st)
 {
-    if (streamed)
-        *streamed = false;
-    if (p.n_reads <= p.read_begin)
-        return hipSuccess;
-    const bool two = g.lw == 2;
-    switch (hash_funs)
+    if (L.family == GN_COUNT_LEAN)
     {
-        case 1: return two ? gn_launch_fast_one<1, 2>(p, pol, st, streamed) : gn_launch_fast_one<1, 1>(p, pol, st, streamed);
-        case 2: return two ? gn_launch_fast_one<2, 2>(p, pol, st, streamed) : gn_launch_fast_one<2, 1>(p, pol, st, streamed);
-        case 3: return two ? gn_launch_fast_one<3, 2>(p, pol, st, streamed) : gn_launch_fast_one<3, 1>(p, pol, st, streamed);
-        case 4: return two ? gn_launch_fast_one<4, 2>(p, pol, st, streamed) : gn_launch_fast_one<4, 1>(p, pol, st, streamed);
-        case 5: return two ? gn_launch_fast_one<5, 2>(p, pol, st, streamed) : gn_launch_fast_one<5, 1>(p, pol, st, streamed);
+        if (L.stream)
+            hipLaunchKernelGGL(gn_ibf_count_stream_kernel_lean, dim3(L.blocks), dim3(256), (size_t)L.lds_bytes, st, p);
+        else
+            hipLaunchKernelGGL(gn_ibf_count_fast_kernel_lean, dim3(L.blocks), dim3(256), (size_t)L.lds_bytes, st, p);
+        return hipGetLastError();
+    }
+    if (L.family != GN_COUNT_FAST)
+        return hipErrorInvalidValue;
+    switch (L.HF)
+    {
+        case 1: return gn_launch_fast_hf<1>(L, p, st);
+        case 2: return gn_launch_fast_hf<2>(L, p, st);
+        case 3: return gn_launch_fast_hf<3>(L, p, st);
+        case 4: return gn_launch_fast_hf<4>(L, p, st);
+        case 5: return gn_launch_fast_hf<5>(L, p, st);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <int HF>
-static hipError_t gn_launch_count_hf(const GnCountParams& p, const GnCountGeometry& g, hipStream_t st)
+static hipError_t gn_launch_count_hf(const GnCountParams& p, const GnCountGeometry& g, uint32_t blocks, hipStream_t st)
 {
     if (g.block <= 256)
-        return g.lw == 2 ? gn_launch_count_one<HF, 2, 256>(p, g, st) : gn_launch_count_one<HF, 1, 256>(p, g, st);
+        return g.lw == 2 ? gn_launch_count_one<HF, 2, 256>(p, g, blocks, st) : gn_launch_count_one<HF, 1, 256>(p, g, blocks, st);
     if (g.block <= 512) // 8 waves per read: two waves per SIMD, the whole register file is available (no spills)
-        return g.lw == 2 ? gn_launch_count_one<HF, 2, 512>(p, g, st) : gn_launch_count_one<HF, 1, 512>(p, g, st);
-    return g.lw == 2 ? gn_launch_count_one<HF, 2, 1024>(p, g, st) : gn_launch_count_one<HF, 1, 1024>(p, g, st);
+        return g.lw == 2 ? gn_launch_count_one<HF, 2, 512>(p, g, blocks, st) : gn_launch_count_one<HF, 1, 512>(p, g, blocks, st);
+    return g.lw == 2 ? gn_launch_count_one<HF, 2, 1024>(p, g, blocks, st) : gn_launch_count_one<HF, 1, 1024>(p, g, blocks, st);
 }
 
-hipError_t gn_launch_count(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st)
+hipError_t gn_launch_count(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, uint32_t blocks, hipStream_t st)
 {
     if (p.n_reads <= p.read_begin)
         return hipSuccess;
     switch (hash_funs)
     {
-        case 1: return gn_launch_count_hf<1>(p, g, st);
-        case 2: return gn_launch_count_hf<2>(p, g, st);
-        case 3: return gn_launch_count_hf<3>(p, g, st);
-        case 4: return gn_launch_count_hf<4>(p, g, st);
-        case 5: return gn_launch_count_hf<5>(p, g, st);
+        case 1: return gn_launch_count_hf<1>(p, g, blocks, st);
+        case 2: return gn_launch_count_hf<2>(p, g, blocks, st);
+        case 3: return gn_launch_count_hf<3>(p, g, blocks, st);
+        case 4: return gn_launch_count_hf<4>(p, g, blocks, st);
+        case 5: return gn_launch_count_hf<5>(p, g, blocks, st);
         default: return hipErrorInvalidValue;
     }
 }

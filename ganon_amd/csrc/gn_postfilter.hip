@@ -51,7 +51,7 @@ struct GnPostfilterParams
     uint32_t*           minc;       // [n_reads] STATS mode: min count (starts at the read's minimiser count, :704)
     const uint32_t*     gmax;       // APPLY mode: the level's max / min per read (several filters, see gn_streams_postfilter_joint)
     const uint32_t*     gmin;
-    unsigned long long* ctr;        // [0] dropped by rel_filter [1] dropped by fpr_query
+    unsigned long long* ctr;        // GnPfCtr: dropped by rel_filter, dropped by fpr_query
     const unsigned long long* cursor; // match cursor and capacity: an overflowed batch holds no matches yet (gn_finish re-runs)
     uint64_t            cap;
     uint64_t            n_targets;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void gn_postfilter_kernel(GnPostfilterParams p
     {
         p.keep[r] = 0;
         if (MODE != 3 && p.pre_ctr && *p.pre_ctr)
-            atomicAdd(&p.ctr[0], *p.pre_ctr);
+            atomicAdd(&p.ctr[GN_PF_CTR_DROPPED_REL], *p.pre_ctr);
     }
     uint64_t heavy = __ballot(valid && c > GN_PF_SMALL);
     while (heavy)
@@ -339,9 +339,9 @@ __global__ __launch_bounds__(256) void gn_postfilter_kernel(GnPostfilterParams p
     if (lane == 0)
     {
         if (n_fil)
-            atomicAdd(&p.ctr[0], (unsigned long long)n_fil);
+            atomicAdd(&p.ctr[GN_PF_CTR_DROPPED_REL], (unsigned long long)n_fil);
         if (n_fpr)
-            atomicAdd(&p.ctr[1], (unsigned long long)n_fpr);
+            atomicAdd(&p.ctr[GN_PF_CTR_DROPPED_FPR], (unsigned long long)n_fpr);
     }
 }
 
@@ -382,7 +382,7 @@ __global__ void gn_postfilter_compact_kernel(const gn_match* __restrict__ in, gn
 }
 
 // queued on the stream right after the grouping pass; results: s->d_matches (compacted survivors), s->d_slot_cnt (n+1
-// offsets), s->pf.d_max, s->pf.d_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+// offsets), s->pf.d_max, s->pf.d_ctr (GnPfCtr: dropped rel_filter, dropped fpr_query, survivors)
 static GnPostfilterParams gn_pf_params(gn_stream* s)
 {
     GnPostfilterParams p{};
@@ -401,7 +401,7 @@ static GnPostfilterParams gn_pf_params(gn_stream* s)
     p.maxc       = s->pf.d_max;
     p.minc       = s->pf.d_min;
     p.ctr        = s->pf.d_ctr;
-    p.cursor     = s->d_ctr;
+    p.cursor     = s->d_ctr + GN_CTR_CURSOR;
     p.cap        = s->match_cap;
     p.n_targets  = s->f->is_hibf ? s->f->n_user_bins : s->f->n_targets;
     p.seg_min    = s->pf_predrop ? s->pf.d_segmin : nullptr;
@@ -419,21 +419,21 @@ static int gn_pf_finish(gn_stream* s, const GnPostfilterParams& p)
     // survivors go to the buffer the pre-pass did not read: d_matches after a contiguous copy, d_sorted after segments
     gn_match* out = p.m == s->d_sorted ? s->d_matches : s->d_sorted;
     hipLaunchKernelGGL(gn_postfilter_compact_kernel, dim3(blocks), dim3(256), 0, s->st, p.m, out, s->d_seg_off, p.begin, p.stride,
-                       s->pf.d_keep, s->d_slot_cnt, n, s->d_ctr, s->match_cap);
+                       s->pf.d_keep, s->d_slot_cnt, n, s->d_ctr + GN_CTR_CURSOR, s->match_cap);
     s->pf_out = out;
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(s->pf.d_ctr + 2, s->d_slot_cnt + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
-    GN_HIP(hipMemcpyAsync(s->pf.h_ctr, s->pf.d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st));
+    GN_HIP(hipMemcpyAsync(s->pf.d_ctr + GN_PF_CTR_SURVIVORS, s->d_slot_cnt + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s->st));
+    GN_HIP(hipMemcpyAsync(s->pf.h_ctr, s->pf.d_ctr, GN_PF_NCTR * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st));
     return GN_OK;
 }
 
 // queued on the stream right after the grouping pass; results: s->d_matches (compacted survivors), s->d_slot_cnt (n+1
-// offsets), s->pf.d_max, s->pf.d_ctr [0] dropped rel_filter [1] dropped fpr_query [2] survivors
+// offsets), s->pf.d_max, s->pf.d_ctr (GnPfCtr: dropped rel_filter, dropped fpr_query, survivors)
 int gn_run_postfilter(gn_stream* s)
 {
     if (!s->pf_on || s->pf_joint) // (a joint pass is run by gn_streams_postfilter_joint, after every stream of the level)
         return GN_OK;
-    GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+    GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, GN_PF_NCTR * sizeof(unsigned long long), s->st));
     const GnPostfilterParams p = gn_pf_params(s);
     const unsigned blocks = (unsigned)(((uint64_t)s->n_reads + 1 + 255) / 256);
     hipLaunchKernelGGL(gn_postfilter_kernel<0>, dim3(blocks), dim3(256), 0, s->st, p);
@@ -485,7 +485,7 @@ struct GnPfMergeParams
     uint32_t        n_reads;
     const uint32_t* nh;
     double          rel_filter, fpr_query;
-    unsigned long long* ctr; // stream 0's: [0] dropped rel_filter [1] dropped fpr_query [3] length of `big`
+    unsigned long long* ctr; // stream 0's GnPfCtr: dropped rel_filter, dropped fpr_query, length of `big`
     uint32_t*           big; // reads with more matches than a wave's table takes: done by the block-per-read launch
 };
 
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void gn_pf_merge_kernel(GnPfMergeParams p)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
     };
-    const uint32_t n_items = BLOCK ? (uint32_t)p.ctr[3] : p.n_reads;
+    const uint32_t n_items = BLOCK ? (uint32_t)p.ctr[GN_PF_CTR_BIG] : p.n_reads;
     for (uint32_t it = BLOCK ? blockIdx.x : blockIdx.x * 4 + grp; it < n_items; it += BLOCK ? gridDim.x : gridDim.x * 4)
     {
         const uint32_t r = BLOCK ? p.big[it] : it;
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(256) void gn_pf_merge_kernel(GnPfMergeParams p)
             {
                 for (uint32_t f = 0; f < p.k; ++f)
                     p.maxc[f][r] = 0x80000000u;
-                p.big[atomicAdd(&p.ctr[3], 1ull)] = r;
+                p.big[atomicAdd(&p.ctr[GN_PF_CTR_BIG], 1ull)] = r;
             }
             continue;
         }
@@ -655,9 +655,9 @@ __global__ __launch_bounds__(256) void gn_pf_merge_kernel(GnPfMergeParams p)
     if ((threadIdx.x & 63u) == 0)
     {
         if (n_fil)
-            atomicAdd(&p.ctr[0], (unsigned long long)n_fil);
+            atomicAdd(&p.ctr[GN_PF_CTR_DROPPED_REL], (unsigned long long)n_fil);
         if (n_fpr)
-            atomicAdd(&p.ctr[1], (unsigned long long)n_fpr);
+            atomicAdd(&p.ctr[GN_PF_CTR_DROPPED_FPR], (unsigned long long)n_fpr);
     }
 }
 
@@ -704,7 +704,7 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
             int rc = gn_finish_batch(s);
             if (rc)
                 return rc;
-            GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+            GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, GN_PF_NCTR * sizeof(unsigned long long), s->st));
             if ((rc = gn_result_compact(s)) != GN_OK) // (the merge kernel walks contiguous per-read ranges)
                 return rc;
             mp.m[i]         = s->d_sorted;
@@ -778,7 +778,7 @@ extern "C" int gn_streams_postfilter_joint(gn_stream* const* streams, uint32_t n
         if (rc)
             return rc;
         GN_HIP(hipSetDevice(s->device));
-        GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, 4 * sizeof(unsigned long long), s->st));
+        GN_HIP(hipMemsetAsync(s->pf.d_ctr, 0, GN_PF_NCTR * sizeof(unsigned long long), s->st));
         hipLaunchKernelGGL(gn_postfilter_kernel<1>, dim3(blocks), dim3(256), 0, s->st, gn_pf_params(s));
         GN_HIP(hipGetLastError());
     }
@@ -898,14 +898,14 @@ extern "C" int gn_stream_set_postfilter(gn_stream* s, const gn_postfilter* pf)
         GN_HIP(b.d_min.alloc(nr));
         GN_HIP(b.d_gmax.alloc(nr));
         GN_HIP(b.d_gmin.alloc(nr));
-        GN_HIP(b.d_ctr.alloc(4));
+        GN_HIP(b.d_ctr.alloc(GN_PF_NCTR));
         GN_HIP(b.d_pre.alloc(2));
         b.segmin_cap = ((uint64_t)s->max_reads + 1) * (s->f->is_hibf ? 1u : s->f->geom.wpr);
         GN_HIP(b.d_segmin.alloc(b.segmin_cap));
         if (s->f->is_hibf)
             GN_HIP(b.d_rmax.alloc(nr));
         GN_HIP(b.d_fpr.alloc(nt));
-        GN_HIP(b.h_ctr.alloc(4));
+        GN_HIP(b.h_ctr.alloc(GN_PF_NCTR));
         size_t tmp = 0;
         gn_scan_counts(nullptr, tmp, b.d_keep.get(), s->d_slot_cnt.get(), (int)(s->max_reads + 1), s->st);
         GN_HIP(b.d_scan.alloc(tmp));

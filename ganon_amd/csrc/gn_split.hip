@@ -1069,11 +1069,8 @@ size_t gn_split_lds_bytes(const GnCountGeometry& g, uint32_t hash_funs)
 }
 
 template <int HF, int LW, int MAXT, int RS>
-static hipError_t gn_launch_split_rs(const GnCountParams& p, const GnCountGeometry& g, hipStream_t st)
+static hipError_t gn_launch_split_rs(const GnCountParams& p, const GnCountGeometry& g, uint32_t blocks, hipStream_t st)
 {
-    uint32_t blocks = (p.n_reads - p.read_begin + g.rpb - 1) / g.rpb;
-    if (blocks > p.max_blocks)
-        blocks = p.max_blocks;
     const size_t lds = gn_split_lds_bytes(g, HF);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gn_ibf_count_split_kernel<HF, LW, MAXT, RS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1082,39 +1079,39 @@ static hipError_t gn_launch_split_rs(const GnCountParams& p, const GnCountGeomet
 }
 
 template <int HF, int LW, int MAXT>
-static hipError_t gn_launch_split_one(const GnCountParams& p, const GnCountGeometry& g, hipStream_t st)
+static hipError_t gn_launch_split_one(const GnCountParams& p, const GnCountGeometry& g, uint32_t blocks, hipStream_t st)
 {
     if constexpr (GN_SPLIT_RUN_SELECT(MAXT))
     {
         if (p.const_nb && p.uniform_nb)
-            return gn_launch_split_rs<HF, LW, MAXT, 2>(p, g, st);
+            return gn_launch_split_rs<HF, LW, MAXT, 2>(p, g, blocks, st);
         if (p.const_nb)
-            return gn_launch_split_rs<HF, LW, MAXT, 1>(p, g, st);
+            return gn_launch_split_rs<HF, LW, MAXT, 1>(p, g, blocks, st);
     }
-    return gn_launch_split_rs<HF, LW, MAXT, 0>(p, g, st);
+    return gn_launch_split_rs<HF, LW, MAXT, 0>(p, g, blocks, st);
 }
 
 template <int HF>
-static hipError_t gn_launch_split_hf(const GnCountParams& p, const GnCountGeometry& g, hipStream_t st)
+static hipError_t gn_launch_split_hf(const GnCountParams& p, const GnCountGeometry& g, uint32_t blocks, hipStream_t st)
 {
     if (g.block <= 256)
-        return g.lw == 2 ? gn_launch_split_one<HF, 2, 256>(p, g, st) : gn_launch_split_one<HF, 1, 256>(p, g, st);
+        return g.lw == 2 ? gn_launch_split_one<HF, 2, 256>(p, g, blocks, st) : gn_launch_split_one<HF, 1, 256>(p, g, blocks, st);
     if (g.block <= 512)
-        return g.lw == 2 ? gn_launch_split_one<HF, 2, 512>(p, g, st) : gn_launch_split_one<HF, 1, 512>(p, g, st);
-    return g.lw == 2 ? gn_launch_split_one<HF, 2, 1024>(p, g, st) : gn_launch_split_one<HF, 1, 1024>(p, g, st);
+        return g.lw == 2 ? gn_launch_split_one<HF, 2, 512>(p, g, blocks, st) : gn_launch_split_one<HF, 1, 512>(p, g, blocks, st);
+    return g.lw == 2 ? gn_launch_split_one<HF, 2, 1024>(p, g, blocks, st) : gn_launch_split_one<HF, 1, 1024>(p, g, blocks, st);
 }
 
-hipError_t gn_launch_count_split(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, hipStream_t st)
+hipError_t gn_launch_count_split(const GnCountParams& p, const GnCountGeometry& g, uint32_t hash_funs, uint32_t blocks, hipStream_t st)
 {
     if (p.n_reads <= p.read_begin)
         return hipSuccess;
     switch (hash_funs)
     {
-        case 1: return gn_launch_split_hf<1>(p, g, st);
-        case 2: return gn_launch_split_hf<2>(p, g, st);
-        case 3: return gn_launch_split_hf<3>(p, g, st);
-        case 4: return gn_launch_split_hf<4>(p, g, st);
-        case 5: return gn_launch_split_hf<5>(p, g, st);
+        case 1: return gn_launch_split_hf<1>(p, g, blocks, st);
+        case 2: return gn_launch_split_hf<2>(p, g, blocks, st);
+        case 3: return gn_launch_split_hf<3>(p, g, blocks, st);
+        case 4: return gn_launch_split_hf<4>(p, g, blocks, st);
+        case 5: return gn_launch_split_hf<5>(p, g, blocks, st);
         default: return hipErrorInvalidValue;
     }
 }
